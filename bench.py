@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- LERC encode + decode round trip on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, ms_per_step, the timed steps' per-kernel
+table, the roofline of their dominant kernel).  Everything that takes runs of its own -- step_ms, sync_per_call, cache_cold,
+the measured copy ceiling, the CPU baseline and the blob compared with the reference's, c5_1gpu, c3 / c4 / c2_masked /
+c2_ragged / c2_flat -- runs only with --full.  --dump-outputs DIR writes what the last timed step computed as DIR/*.npy.
 
 N = 1 (default workload c2, BASELINE configs[1] -- the configuration the metric is quoted on): one step = lerc_encode +
 lerc_decode of one 8192 x 8192 float32 raster (1 band, MaxZError 0.01) that is already resident in HBM, through the
@@ -56,12 +61,18 @@ def parse_args():
     ap.add_argument("--tiles", type=int, default=0, help="tiles of the whole mosaic for --workload c5 (default: all 65536, on one GPU too -- 17 GB of pixels)")
     ap.add_argument("--no-c5-anchor", action="store_true",
                     help="default c2 line on one GPU: leave out `c5_1gpu`, the N = 1 point of the mosaic's strong-scaling curve")
-    ap.add_argument("--rotate", type=int, default=3, help="buffer sets of the cache-cold pass (0: skip it)")
+    ap.add_argument("--rotate", type=int, default=3, help="buffer sets of the cache-cold pass (--full; 0: skip it)")
     ap.add_argument("--mode", choices=("async", "sync"), default="async",
                     help="c2: async (default) -- every step's encode and decode are ENQUEUED on the HIP stream (lerc_amd_*_device_async; the decode "
                          "reads the blob's size from its header on the device) and the host waits once, at the end of the K steps, the way any "
                          "stream of GPU work is driven; sync -- lerc_amd_encode_device / lerc_amd_decode_device, each waiting for its own result "
                          "(reported beside it as `sync_per_call` in async mode)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: step_ms, sync_per_call, cache_cold, the copy ceiling, "
+                         "the CPU baseline and the reference's blob, c5_1gpu, c3 / c4 / c2_masked / c2_ragged / c2_flat (off: the K timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64; a fixed, "
+                         "seeded sample of the decoded raster and of the blob)")
     return ap.parse_args()
 
 
@@ -416,6 +427,31 @@ def c5_single_gpu(torch, api, synth, codec, dev, max_z_err, total_tiles, steps=3
     return res
 
 
+DUMP_SAMPLE = 1 << 22    # decoded pixels / blob bytes kept by --dump-outputs: 16 MB each as float32
+
+
+def dump_outputs(torch, directory, y, blob=None, tile_sizes=None):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files.  decoded.npy: the decoded pixels at DUMP_SAMPLE
+    fixed, seeded places (float32, exact); blob.npy: the blob's bytes at DUMP_SAMPLE seeded places below its size (the byte values
+    as float32) and blob_bytes.npy its size (float64); tile_blob_bytes.npy: every tile's blob size (float64, tile workloads)."""
+    import numpy as np
+
+    def places(n, seed):
+        if n <= DUMP_SAMPLE:
+            return torch.arange(n, device=y.device)
+        idx = np.unique(np.random.default_rng(seed).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+        return torch.from_numpy(idx).to(y.device)
+
+    os.makedirs(directory, exist_ok=True)
+    flat = y.reshape(-1)
+    np.save(os.path.join(directory, "decoded.npy"), flat[places(flat.numel(), 1234)].to(torch.float32).cpu().numpy())
+    if blob is not None:
+        np.save(os.path.join(directory, "blob.npy"), blob[places(blob.numel(), 4321)].to(torch.float32).cpu().numpy())
+        np.save(os.path.join(directory, "blob_bytes.npy"), np.array([blob.numel()], np.float64))
+    if tile_sizes is not None:
+        np.save(os.path.join(directory, "tile_blob_bytes.npy"), np.asarray(tile_sizes, np.float64))
+
+
 def main():
     args = parse_args()
     import numpy as np
@@ -486,7 +522,7 @@ def main():
             rc, sizes = api.encode_tiles_device_slots(codec, x, args.max_z_err, out, TILE_SLOT_BYTES)
             if rc != 0:
                 raise RuntimeError(f"tile encode failed: status {rc}: {codec.last_error()}")
-            state["blob_bytes"] = int(sizes.sum())
+            state["blob_bytes"], state["tile_sizes"] = int(sizes.sum()), sizes
             rc = api.decode_tiles_device_slots(codec, out, TILE_SLOT_BYTES, sizes, y)
             if rc != 0:
                 raise RuntimeError(f"tile decode failed: status {rc}: {codec.last_error()}")
@@ -497,7 +533,7 @@ def main():
             if rc != 0:
                 raise RuntimeError(f"tile encode failed: status {rc}: {codec.last_error()}")
             te1 = time.perf_counter()
-            state["blob_bytes"] = int(sizes.sum())
+            state["blob_bytes"], state["tile_sizes"] = int(sizes.sum()), sizes
             flight = None
             if world > 1:
                 # the exchange step: all ranks' blobs on rank 0.  The transfers are enqueued here and run beside what this rank
@@ -597,10 +633,13 @@ def main():
                      "decode_ms": round(float(table[r, 1]) / k * 1e3, 4), "gather_ms_start_to_arrival": round(float(table[r, 2]) / k * 1e3, 4),
                      "gather_ms_waited_behind_decode": round(float(table[r, 3]) / k * 1e3, 4)} for r in range(world)]
     timed_blob_bytes = int(state["blob_bytes"])    # of the TIMED pass (buffer set 0); later passes must not overwrite it
-    # the blob the timed pass left in set 0's buffer (its last step's), before anything else writes there
+    # what the timed pass's last step left in set 0's buffers, before anything else writes there
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, sets[0][2], blob=None if tiles_mode else sets[0][1][:timed_blob_bytes],
+                     tile_sizes=state.get("tile_sizes") if tiles_mode else None)
     import hashlib
     timed_blob_sha = None
-    if not tiles_mode:
+    if args.full and not tiles_mode:
         timed_blob_sha = hashlib.sha256(sets[0][1][:timed_blob_bytes].cpu().numpy().tobytes()).hexdigest()
 
     # correctness of what was timed (outside the timed region)
@@ -611,7 +650,7 @@ def main():
     # the same steps once more with an event behind every step (outside the timed region: an event record between kernels is
     # not free): the spread of the single steps -- median and fastest next to the timed region's mean
     step_ms = None
-    if not tiles_mode:
+    if args.full and not tiles_mode:
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
         evs[0].record()
         for i in range(args.steps):
@@ -624,14 +663,14 @@ def main():
                    "note": "one event per step on the stream, measured in a pass of its own behind the timed region"}
 
     sync_run = None
-    if state["async"]:
+    if args.full and state["async"]:
         state["async"] = False
         sync_run = timed(1)
         state["async"] = True
-    ceiling = measured_ceiling(torch, x0, torch.empty_like(x0)) if not tiles_mode else None
+    ceiling = measured_ceiling(torch, x0, torch.empty_like(x0)) if args.full and not tiles_mode else None
 
     cold = None
-    if args.rotate >= 2:
+    if args.full and args.rotate >= 2:
         try:
             while len(sets) < args.rotate:
                 sets.append(make_set(len(sets)))
@@ -644,7 +683,7 @@ def main():
     # the N = 1 point of the mosaic's strong-scaling curve (BASELINE configs[4]: all 65 536 tiles on this one GPU), so that a
     # driver record holds it next to the c2 line
     c5_anchor = None
-    if world == 1 and not tiles_mode and not args.no_c5_anchor and n == 8192:
+    if args.full and world == 1 and not tiles_mode and not args.no_c5_anchor and n == 8192:
         try:
             del sets[1:]
             torch.cuda.empty_cache()
@@ -654,7 +693,7 @@ def main():
 
     # BASELINE configs[2] and configs[3] beside it (parity-test cases with their own timing: not the line's value)
     others = None
-    if world == 1 and not tiles_mode and not args.no_other_configs and n == 8192:
+    if args.full and world == 1 and not tiles_mode and not args.no_other_configs and n == 8192:
         others = {}
         del sets[1:]
         torch.cuda.empty_cache()
@@ -803,7 +842,7 @@ def main():
                 cc["roofline"] = {"kernel": cdom, "achieved": round(alg.get(cdom, b_enc) / avg_s / 1e9, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                   "frac": round(alg.get(cdom, b_enc) / avg_s / 1e9 / HBM_PEAK_GBS, 5)}
             res["cache_cold"] = cc
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline_tiles(x0[:64].cpu().numpy(), args.max_z_err) if tiles_mode else cpu_baseline(x0.cpu().numpy(), args.max_z_err)
             cb = res["cpu_baseline"]
             if cb and not tiles_mode and cb.get("blob_sha256"):

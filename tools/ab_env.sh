@@ -7,7 +7,7 @@ N=$1; shift
 : > "$OUT/ab_env.txt"
 for r in $(seq 1 $N); do
   for E in "$@"; do
-    env $(echo $E | tr ',' ' ') timeout 300 python bench.py --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-c5-anchor ${OTHERS:---no-other-configs} --rotate 0 2>"$OUT/ab_env.err" | python -c "
+    env $(echo $E | tr ',' ' ') timeout 300 python bench.py --full --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-c5-anchor ${OTHERS:---no-other-configs} --rotate 0 2>"$OUT/ab_env.err" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 s='$E ms_per_step %s frac %s verified %s %s' % (d['ms_per_step'], d['roundtrip']['frac_of_hbm_peak_wall'], d['config']['verified'], ' '.join(f\"{k}={v['avg_ms']*1000:.1f}\" for k,v in d['kernels'].items()))
