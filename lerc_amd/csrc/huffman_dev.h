@@ -44,6 +44,10 @@ void launchHuffInitStarts(u64* starts, u64* prevStarts, u32 nSub, u32 subWords, 
 void launchHuffSync(const u32* stream, u32 mis, u64 nWords, u64 streamBits, const HuffDecodeTable* table, u32 nSub, u32 subWords, u64* starts,
                     u64* prevStarts, u64* exits, u32* counts, u32* bad, bool firstRound, hipStream_t st);
 void launchHuffChain(u32 nSub, u64* starts, const u64* exits, u32* changed, hipStream_t st);
+// all starts at once from the sub-sequences' entry -> exit maps (span = the longest code length; mapA / mapB: (nSub - 1) * span
+// bytes each); false: nothing enqueued (a single sub-sequence, or no such span)
+bool launchHuffResolve(const u32* stream, u32 mis, u64 nWords, const HuffDecodeTable* table, u32 nSub, u32 subWords, u32 span,
+                       u8* mapA, u8* mapB, u64* starts, hipStream_t st);
 void launchValidIndex(const u8* maskBits, const u32* groupBase, i64 nPix, u32* validIdx, hipStream_t st);
 void launchHuffEmit(int dt, const u32* stream, u32 mis, u64 nWords, u64 streamBits, const HuffDecodeTable* table, u32 nSub, u32 subWords, const u64* starts,
                     const u64* symBase, const HuffGeom& g, int mode, u64 nSymbols, u32 numValid, const u32* validIdx, bool planar,

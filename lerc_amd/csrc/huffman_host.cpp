@@ -542,11 +542,25 @@ u32 decodeHuffman(Context& ctx, int dt, const u8* hBlob, const u8* dBlob, u32 da
     { ProfScope ps(ctx, "huff_emit"); launchHuffEmit(dt, dStream, mis, nWords, streamBits, dTab, nSub, subWords, dStarts, dSymBase, g, imageMode, nSymbols, numValid, dValidIdx, false, dOut, st); }
     if (imageMode == IEM_DeltaHuffman) { ProfScope ps(ctx, "huff_undelta"); launchHuffUndelta(dt, dOut, dMaskBits, g, st); }
   };
+  // (a correction is needed: the second round takes every start from the composed entry -> exit maps instead of moving the
+  // correction on by a workgroup a round -- codes that never fall into step; later rounds, a broken stream's, go on by the chain)
+  u32 span = 0;
+  for (const HCode& c : table) span = std::max<u32>(span, c.first);
+  const size_t mark = ctx.used();
   const int kMaxRounds = 4096;
   int round = 0;
   u64 total = 0;
   for (; round < kMaxRounds; round++)
   {
+    if (round == 1 && nSub > 1)
+    {
+      const size_t mapBytes = (size_t)(nSub - 1) * span;
+      u8* mapA = ctx.allocT<u8>(mapBytes + 16);
+      u8* mapB = ctx.allocT<u8>(mapBytes + 16);
+      if (!mapA || !mapB) { ctx.lastError = "Huffman decode: no room for the sub-sequence maps"; return kFailed; }
+      ProfScope ps(ctx, "huff_map");
+      launchHuffResolve(dStream, mis, nWords, dTab, nSub, subWords, span, mapA, mapB, dStarts, st);
+    }
     { ProfScope ps(ctx, "huff_sync");
       hipMemsetAsync(dFlags, 0, 4, st);
       launchHuffSync(dStream, mis, nWords, streamBits, dTab, nSub, subWords, dStarts, dPrev, dExits, dCounts, dFlags + 1, round == 0, st);
@@ -558,6 +572,7 @@ u32 decodeHuffman(Context& ctx, int dt, const u8* hBlob, const u8* dBlob, u32 da
     const bool ok = ctx.sync();
     if (!ok) return kFailed;
     memcpy(&total, pin + 2, 8);
+    if (round == 1) ctx.rewind(mark);    // (the maps served their round, which has been waited for)
     if (!pin[0]) break;
   }
   if (round == kMaxRounds) { ctx.lastError = "Huffman stream did not synchronise"; return kFailed; }

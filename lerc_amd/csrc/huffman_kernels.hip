@@ -694,7 +694,8 @@ __device__ __forceinline__ int decodeOne(const HuffLdsTable& s, u32 top, int& sy
 // words early and takes the first code word boundary at or behind its first bit as starts[t].  Where the warm-up did not
 // catch on, the sub-sequence in front ends somewhere else than this one begins: the workgroup sees that in LDS and lets
 // such threads start over from their predecessor's exit until its sub-sequences fit together.  If the chain of exits
-// (k_huff_chain) then fits across the workgroups as well, which is the normal case, that was the only round.
+// (k_huff_chain) then fits across the workgroups as well, which is the normal case, that was the only round.  Otherwise the
+// second round takes every start from composed entry -> exit maps (k_huff_map, below).
 __global__ void __launch_bounds__(kHuffDecThreads)
 k_huff_sync(const u32* __restrict__ stream, u32 mis, u64 nWords, u64 streamBits, const HuffDecodeTable* __restrict__ table, u32 nSub, u32 subWords,
             u64* __restrict__ starts, u64* __restrict__ prevStarts, u64* __restrict__ exits, u32* __restrict__ counts,
@@ -783,6 +784,88 @@ k_huff_chain(u32 nSub, u64* __restrict__ starts, const u64* __restrict__ exits, 
   if (t + 1 >= nSub) return;
   const u64 e = exits[t];
   if (starts[t + 1] != e) { starts[t + 1] = e; atomicOr(changed, 1u); }
+}
+
+// The warm-up's promise fails for codes that never fall into step: a complete code whose words all have one length L that
+// does not divide the sub-sequence length (8 classes in 3 bits, 7-bit noise) keeps a decoder that started out of phase out of
+// phase for good, and the chain above then moves the correction on by one workgroup a round.  Instead: the code word that
+// ends sub-sequence t begins before its end and is at most `span` (the longest code) bits long, so where sub-sequence t + 1
+// is entered lies in [its first bit, its first bit + span).  Sub-sequence t's map records, for every entry offset e in that
+// window, the exit offset into the next one's window (kHuffMapBroken: no code word matched) -- a workgroup per entry offset
+// (blockIdx.y), each stages the same slice.  The maps are composed by pointer jumping (log2(nSub) launches), and sub-sequence
+// 0's entry (offset 0) then gives every start at once.
+static const u8 kHuffMapBroken = 0xFFu;
+
+__global__ void __launch_bounds__(kHuffDecThreads)
+k_huff_map(const u32* __restrict__ stream, u32 mis, u64 nWords, const HuffDecodeTable* __restrict__ table, u32 nSub, u32 subWords,
+           u32 span, u8* __restrict__ map)
+{
+  __shared__ HuffLdsTable s_tab;
+  __shared__ u32 s_str[kHuffStageWords];
+  stageLut(table, s_tab);
+  stageStream(stream, mis, nWords, subWords, s_str);
+  __syncthreads();
+  const u32 t = blockIdx.x * (u32)kHuffDecThreads + threadIdx.x;
+  if (t + 1 >= nSub) return;    // (the last sub-sequence hands nothing on; every other one ends inside the stream)
+  const u32 endLocal = ((u32)kHuffWarmWords + (threadIdx.x + 1u) * subWords) * 32u;
+  StagedBits in;
+  in.start(s_str, ((u32)kHuffWarmWords + threadIdx.x * subWords) * 32u + blockIdx.y);
+  u8 r = 0;
+  while (in.pos < endLocal)
+  {
+    int sym;
+    const int len = decodeOne(s_tab, in.top(), sym);
+    if (len == 0) { r = kHuffMapBroken; break; }
+    in.skip(len);
+  }
+  if (r != kHuffMapBroken) r = (u8)(in.pos - endLocal);    // (< span: the last code word began in front of endLocal)
+  map[(size_t)t * span + blockIdx.y] = r;
+}
+
+// one pointer-jumping step over the nMaps = nSub - 1 maps: out_t = in_t o in_(t - d) (in_t already covers t - d + 1 .. t)
+__global__ void __launch_bounds__(256)
+k_huff_map_jump(const u8* __restrict__ in, u8* __restrict__ out, u32 nMaps, u32 span, u32 d)
+{
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (i >= (u64)nMaps * span) return;
+  const u32 t = (u32)(i / span), e = (u32)(i - (u64)t * span);
+  u8 v = in[i];
+  if (t >= d)
+  {
+    const u8 x = in[(u64)(t - d) * span + e];
+    v = (x == kHuffMapBroken) ? kHuffMapBroken : in[(u64)t * span + x];
+  }
+  out[i] = v;
+}
+
+// composed maps -> starts: sub-sequence t + 1 is entered where sub-sequences 0 .. t lead from offset 0 (a broken chain
+// leaves its start as it is: the rounds behind this one go on as before and the symbol count refuses the blob)
+__global__ void __launch_bounds__(256)
+k_huff_map_starts(const u8* __restrict__ composed, u32 nSub, u32 span, u32 subWords, u64* __restrict__ starts)
+{
+  const u32 t = blockIdx.x * 256u + threadIdx.x;
+  if (t + 1 >= nSub) return;
+  const u8 x = composed[(u64)t * span];
+  if (x != kHuffMapBroken) starts[t + 1] = (u64)(t + 1) * subWords * 32u + x;
+}
+
+bool launchHuffResolve(const u32* stream, u32 mis, u64 nWords, const HuffDecodeTable* table, u32 nSub, u32 subWords, u32 span,
+                       u8* mapA, u8* mapB, u64* starts, hipStream_t st)
+{
+  if (nSub < 2 || span == 0 || span > 32) return false;
+  const u32 nMaps = nSub - 1;
+  const dim3 grid((nSub + kHuffDecThreads - 1) / kHuffDecThreads, span);
+  hipLaunchKernelGGL(k_huff_map, grid, dim3(kHuffDecThreads), 0, st, stream, mis, nWords, table, nSub, subWords, span, mapA);
+  const u64 n = (u64)nMaps * span;
+  u8* in = mapA;
+  u8* out = mapB;
+  for (u32 d = 1; d < nMaps; d <<= 1)
+  {
+    hipLaunchKernelGGL(k_huff_map_jump, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const u8*)in, out, nMaps, span, d);
+    u8* const tmp = in; in = out; out = tmp;
+  }
+  hipLaunchKernelGGL(k_huff_map_starts, dim3((nMaps + 255) / 256), dim3(256), 0, st, (const u8*)in, nSub, span, subWords, starts);
+  return true;
 }
 
 // pixel index of every valid pixel, in scan order (rank -> pixel)

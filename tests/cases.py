@@ -512,6 +512,157 @@ def huffman_stress_cases(scale=1):
     return out
 
 
+def _balanced_walk(h, w, rng, n_depth=1, steps=8, mask=None):
+    """8-bit planes whose delta predictor residuals are uniform over `steps` values, the first pixel's included: the delta
+    Huffman code book of such a raster has `steps` equally long codes.  The predictor is the reference's
+    (Lerc2::ComputeHistoForHuffman): the left neighbour if valid, else the pixel above if valid, else the last valid pixel
+    (0 before the first); invalid pixels are 0."""
+    d = rng.integers(-(steps // 2), steps - steps // 2, (h, w, n_depth))
+    if mask is None:
+        col0 = np.cumsum(d[:, 0], axis=0)
+        a = np.cumsum(np.concatenate([col0[:, None], d[:, 1:]], axis=1), axis=1) & 255
+    else:
+        a = np.zeros((h, w, n_depth), np.int64)
+        for m in range(n_depth):
+            prev = 0
+            for i in range(h):
+                for j in range(w):
+                    if not mask[i, j]:
+                        continue
+                    if j > 0 and mask[i, j - 1]: p = prev
+                    elif i > 0 and mask[i - 1, j]: p = a[i - 1, j, m]
+                    else: p = prev
+                    prev = a[i, j, m] = (p + d[i, j, m]) & 255
+    a = a.astype(np.uint8)
+    return a if n_depth > 1 else a[:, :, 0]
+
+
+def huffman_matrix_cases(scale=1, big=False):
+    """8-bit rasters for the Huffman decoder's speculative sync, as (name, arr, kw, image mode the reference picks, kind):
+    kind "equal" -- all code words of one length; "long" -- codes beyond the look-up table, self-synchronising; "span" --
+    the packer's long span.
+    Code books whose words all have one length L (2^L balanced values, L = 1 .. 7; nearly balanced counts; two symbols) --
+    a decoder that starts out of phase in such a stream stays out of phase whenever L does not divide the sub-sequence
+    length -- in the plain and the delta mode, at 1, 3, 5, 16 and 17 values per pixel, widths that are no multiples of 8,
+    masks, int8 and uint8; code books longer than the 12-bit look-up table; a stream whose symbols average more than 10
+    bits over a packer workgroup's span; code tables of several lengths (the stream begins 0 .. 3 bytes into a word).
+    `scale` multiplies the row counts; `big` adds a 4096^2 x 3 raster and an 8192^2 one of 128 values (device only)."""
+    rng = np.random.default_rng(4242)
+    out = []
+
+    def add(name, arr, mode, kind="equal", **kw):
+        out.append((name, arr, kw, mode, kind))
+
+    def i8(a):
+        return a.astype(np.uint8).view(np.int8)
+
+    s = scale
+    # equal lengths, plain mode: 2^L values, uniform (L = 8 does not occur: 256 codes of 8 bits cost what the values
+    # themselves do, and the encoder stores such a raster raw, in one sweep)
+    for L in range(1, 8):
+        cols = (200, 203, 256, 129, 333, 96, 250)[L - 1]
+        rows = max(8, (60000 * s) // (L * cols))
+        x = rng.integers(0, 1 << L, (rows, cols)).astype(np.uint8)
+        if L in (3, 7):
+            x += 60
+        add(f"eq{L}-u8-{rows}x{cols}", x, 2)
+        if L in (2, 3, 5):
+            add(f"eq{L}-i8-{rows}x{cols}", i8(x + 100), 2)
+    # nearly balanced counts: the code lengths come out equal without the counts being
+    for k in (8, 32, 128):
+        rows = max(8, (60000 * s) // (int(np.log2(k)) * 211))
+        n = rows * 211
+        cnt = np.floor(n / k * (1.0 + 0.2 * np.linspace(-1, 1, k))).astype(np.int64)    # (exact counts: no sampling noise)
+        cnt[:n - cnt.sum()] += 1
+        vals = rng.permutation(256)[:k]
+        add(f"near{k}-u8-{rows}x211", rng.permutation(np.repeat(vals, cnt)).reshape(rows, 211).astype(np.uint8), 2)
+    # two symbols far apart (a wide code table range) and two skewed ones (still 1-bit codes)
+    add("two-far-u8", rng.choice(np.array([3, 200], np.uint8), (150 * s, 300)), 2)
+    add("two-skewed-i8", i8(rng.choice(np.array([7, 8], np.uint8), (150 * s, 301), p=[0.8, 0.2])), 2)
+    # plain mode at 3 values per pixel, with a mask
+    add("eq3-u8-depth3", rng.integers(0, 8, (70 * s, 97, 3)).astype(np.uint8), 2, n_depth=3)
+    m = (rng.random((120 * s, 170)) < 0.8).astype(np.uint8)
+    x = (rng.integers(0, 8, (120 * s, 170)) + 40).astype(np.uint8)
+    x[m == 0] = 0
+    add("eq3-u8-masked", x, 2, mask=m)
+    # delta mode, balanced residuals: 8 delta values -> 3-bit codes
+    for nd, cols in ((1, 203), (3, 120), (5, 64), (16, 24), (17, 21)):
+        rows = max(8, (24000 * s) // (nd * cols))
+        x = _balanced_walk(rows, cols, rng, nd)
+        kw = dict(n_depth=nd) if nd > 1 else {}
+        add(f"delta8-u8-depth{nd}-{rows}x{cols}", x, 1, **kw)
+        if nd in (1, 3, 17):
+            add(f"delta8-i8-depth{nd}-{rows}x{cols}", i8(x), 1, **kw)
+    for nd in (1, 3):
+        rows = 90 * s
+        m = np.ones((rows, 131), np.uint8)
+        m[rng.random((rows, 131)) < 0.01] = 0
+        m[10:14, 20:60] = 0
+        m[:, 0] = 0
+        x = _balanced_walk(rows, 131, rng, nd, mask=m)
+        add(f"delta8-u8-depth{nd}-masked", x, 1, mask=m, **(dict(n_depth=nd) if nd > 1 else {}))
+    # long code words (self-synchronising): the huff-steps rasters of huffman_stress_cases
+    h, w = 192 * s, 256
+    walk = np.cumsum(rng.choice([-1, 0, 0, 0, 1], size=(h, w)), axis=1)
+    jump = (rng.random((h, w)) < 0.02) * np.minimum(rng.geometric(0.07, (h, w)), 120) * rng.choice([-1, 1], (h, w))
+    steps = (walk + np.cumsum(jump, axis=1)) & 255
+    add("steps-u8", steps.astype(np.uint8), 1, "long")
+    add("steps-i8", i8(steps), 1, "long")
+    # a packer span of 32 768 symbols averaging over 10 bits: a background of four values (1/2, 1/4, 1/8, 1/16) and rare others,
+    # and 64 K pixels of noise in a row (the rare values' codes are 11 - 12 bits long)
+    h, w = 1024 * max(1, min(s, 4) // 2), 1024
+    vals = np.concatenate([np.array([9, 77, 150, 201]), np.setdiff1d(np.arange(256), [9, 77, 150, 201])])
+    p = np.concatenate([[0.5, 0.25, 0.125, 0.0625], np.full(252, 0.0625 / 252)])
+    x = vals[rng.choice(256, (h, w), p=p / p.sum())].astype(np.uint8)
+    x[h // 4: h // 4 + 64] = rng.integers(0, 256, (64, w))
+    add(f"span-noise-u8-{h}x{w}", x, 2, "span")
+    if big:
+        add("delta8-u8-4096x4096x3", _balanced_walk(4096, 4096, rng, 3), 1, n_depth=3)
+        add("eq7-u8-8192x8192", rng.integers(0, 128, (8192, 8192)).astype(np.uint8), 2)
+    return out
+
+
+def check_huffman_matrix_case(R, P, decode, name, arr, kw, mode, kind, compute_units, threads):
+    """One case of huffman_matrix_cases: size query and blob byte-identical to the reference's, the image mode the case was
+    made for, decode (through `decode(blob, arr, kw) -> (status, pixels, mask, sync rounds, error text)`) equal to the input
+    and to the reference's decode, masks included, and the decoder's sync rounds (host round trips) within
+    2 + ceil(log2(sub-sequences)) -- exactly 1 for the self-synchronising long codes.  Returns (stream offset mod 4, rounds, cap)."""
+    import huffblob
+    kw = dict(kw)
+    assert P.compute_size(arr, 0, **kw) == R.compute_size(arr, 0, **kw), name
+    rc, blob = R.encode(arr, 0, **kw)
+    assert rc == 0, name
+    rc, blob_p = P.encode(arr, 0, **kw)
+    assert rc == 0 and blob_p == blob, (name, "blob differs from the reference's")
+    info = huffblob.parse(blob)
+    assert info["mode"] == mode, (name, "image mode", info["mode"], "wanted", mode)
+    if kind == "equal":
+        assert info["n_codes"] == 1 << info["max_len"], (name, "code lengths not all equal", info)
+    elif kind == "long":
+        assert info["max_len"] > 12, (name, info)
+    else:
+        assert info["max_len"] > 10, (name, info)
+    n = huffblob.n_sub(info, compute_units, threads)
+    cap = huffblob.round_cap(n)
+    rc, dec, msk, rounds, err = decode(blob, arr, kw)
+    print(f"{name}: {arr.shape} mode {mode} max_len {info['max_len']} mis {info['stream_begin'] & 3} sub-sequences {n} "
+          f"sync rounds {rounds} (cap {cap}) rc {rc} {err}")
+    assert rc == 0, (name, rc, err)
+    rc_r, dec_r, msk_r = R.decode(blob)
+    assert rc_r == 0, name
+    assert np.array_equal(np.asarray(dec).reshape(arr.shape), arr), (name, "decode differs from the input")
+    assert np.array_equal(np.asarray(dec).reshape(arr.shape), np.asarray(dec_r).reshape(arr.shape)), (name, "decode differs from the reference's")
+    if "mask" in kw:
+        assert msk is not None and msk_r is not None
+        assert np.array_equal(np.asarray(msk).reshape(kw["mask"].shape), np.asarray(msk_r).reshape(kw["mask"].shape)), name
+        assert np.array_equal(np.asarray(msk).reshape(kw["mask"].shape) != 0, kw["mask"] != 0), name
+    if kind == "long":
+        assert rounds == 1, (name, f"{rounds} sync rounds for self-synchronising content")
+    else:
+        assert rounds <= cap, (name, f"{rounds} sync rounds for {n} sub-sequences, cap {cap}")
+    return info["stream_begin"] & 3, rounds, cap
+
+
 def byte_tiling_cases():
     """8-bit rasters of whole 8 x 8 blocks, every pixel valid, 1 .. 4 values per pixel: the encoder prices the tiling with a
     lane per block position (k_tile_sizes_bytes).  Content that makes blocks constant, bit-stuffed, LUT coded (long runs of

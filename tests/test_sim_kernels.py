@@ -10,6 +10,7 @@ import pytest
 
 import capi
 import cases
+import huffblob
 
 
 @pytest.fixture(scope="module")
@@ -1025,6 +1026,60 @@ def test_sim_huffman_long_codes_and_many_subsequences(libs):
         assert r1 == r2 == 0 and b1 == b2, name
         d = S.decode(b1)
         assert d[0] == 0 and np.array_equal(np.asarray(d[1]).reshape(arr.shape), arr), name
+
+
+def _huff_device_decoder(S):
+    """decode(blob, arr, kw) for cases.check_huffman_matrix_case: lerc_amd_decode_device through the emulator on a context with
+    the profile on; the sync rounds are its huff_sync launches (one per host round trip of the sync loop)"""
+    import ctypes as ct
+    L = S.lib
+    L.lerc_amd_create.restype = ct.c_void_p
+    L.lerc_amd_create.argtypes = [ct.c_void_p]
+    L.lerc_amd_destroy.argtypes = [ct.c_void_p]
+    L.lerc_amd_last_error.argtypes = [ct.c_void_p]
+    L.lerc_amd_last_error.restype = ct.c_char_p
+    L.lerc_amd_profile_enable.argtypes = [ct.c_void_p, ct.c_int]
+    L.lerc_amd_profile_read.argtypes = [ct.c_void_p, ct.c_char_p, ct.c_int, ct.c_int]
+    L.lerc_amd_decode_device.restype = ct.c_uint
+    L.lerc_amd_decode_device.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int, ct.c_void_p, ct.c_int, ct.c_int, ct.c_int,
+                                         ct.c_int, ct.c_uint, ct.c_void_p]
+
+    def decode(blob, arr, kw):
+        h = L.lerc_amd_create(None)
+        assert h
+        try:
+            nd = kw.get("n_depth", 1)
+            rows, cols = arr.shape[0], arr.shape[1]
+            src = _aligned(len(blob), 256)
+            src[:] = np.frombuffer(blob, np.uint8)
+            out = _aligned(arr.nbytes).view(arr.dtype)
+            has_mask = "mask" in kw
+            valid = _aligned(rows * cols) if has_mask else None
+            L.lerc_amd_profile_enable(h, 1)
+            rc = L.lerc_amd_decode_device(h, src.ctypes.data, len(blob), 1 if has_mask else 0, valid.ctypes.data if has_mask else None,
+                                          nd, cols, rows, 1, capi.dt_code(arr.dtype), out.ctypes.data)
+            buf = ct.create_string_buffer(1 << 16)
+            L.lerc_amd_profile_read(h, buf, len(buf), 1)
+            rounds = sum(int(ln.split()[2]) for ln in buf.value.decode().splitlines() if ln.split()[0] == "huff_sync")
+            return rc, out.copy(), (valid.copy() if has_mask else None), rounds, L.lerc_amd_last_error(h).decode()
+        finally:
+            L.lerc_amd_destroy(h)
+    return decode
+
+
+def test_sim_huffman_sync_matrix(libs):
+    """cases.huffman_matrix_cases on the emulator (16 decoder threads a workgroup, 1 warm-up word): blob == the real reference's,
+    decode == input == the reference's decode, and the sync takes at most 2 + ceil(log2(sub-sequences)) rounds -- code books
+    whose words all have one length never fall into step on their own.  The stream offsets cover all four byte phases."""
+    O, S = libs
+    R = capi.ref() or O    # (the oracle only where the real reference was not built)
+    dec = _huff_device_decoder(S)
+    phases = set()
+    for name, arr, kw, mode, kind in cases.huffman_matrix_cases(4):
+        mis, _, _ = cases.check_huffman_matrix_case(R, S, dec, name, arr, kw, mode, kind, compute_units=256,
+                                                    threads=huffblob.DEC_THREADS_SIM)
+        phases.add(mis)
+    assert phases == {0, 1, 2, 3}, phases
 
 
 def test_sim_byte_rasters_priced_by_the_lane_per_block_kernel(libs):
