@@ -53,7 +53,7 @@ LERC_AMD_API lerc_status lerc_amd_decode_device_async(lerc_amd_context* ctx, con
 LERC_AMD_API lerc_status lerc_amd_finish(lerc_amd_context* ctx, unsigned int ticket, unsigned int* nBytes);
 
 /* Tile mosaics: nTiles rasters of one shape, contiguous on the device ([nTiles][nRows][nCols], 1 band, nDepth 1,
- * no masks), in ONE call (tiles are independent blobs; ranks of a multi-GPU job take tile ranges).
+ * no masks -- see the _masked calls below), in ONE call (tiles are independent blobs; ranks of a multi-GPU job take tile ranges).
  * Tile t becomes exactly the blob lerc_encode() would make of it, at dArena + offsets[t] (16-byte aligned), sizes[t]
  * bytes long; offsets / sizes / arenaUsed are HOST arrays the caller provides.  BufferTooSmall(3) if the arena is
  * too small (lerc_computeCompressedSize bounds a tile; nRows * nCols * sizeof(T) + 128 per tile always suffices).
@@ -72,6 +72,30 @@ LERC_AMD_API lerc_status lerc_amd_encode_tiles_device_slots(lerc_amd_context* ct
     int nRows, int nTiles, double maxZErr, unsigned char* dSlots, unsigned long long slotBytes, unsigned int* sizes);
 LERC_AMD_API lerc_status lerc_amd_decode_tiles_device_slots(lerc_amd_context* ctx, const unsigned char* dSlots, unsigned long long slotBytes,
     const unsigned int* sizes, int nTiles, int nCols, int nRows, unsigned int dataType, void* dTiles);
+
+/* Masked mosaics: nTiles rasters of one shape AND their validity masks, one call.  dValidBytes: device, [nTiles][nRows][nCols] bytes,
+ * 0 = invalid (as lerc_encode's pValidBytes with nMasks == 1, per tile); NULL = all valid (then identical to lerc_amd_encode_tiles_device /
+ * _slots).  slotBytes == 0: packed arena, offsets[t] 16-byte aligned; slotBytes != 0 (a multiple of 16): tile t at dArena + t * slotBytes,
+ * offsets[t] is set to that (arenaCapacity >= nTiles * slotBytes).  Tile t's blob is byte for byte what lerc_encode(tile t, nMasks = 1,
+ * mask t) makes; a tile without an invalid pixel gets no mask section.  The batch's own launches (one set per sub-batch, one host wait)
+ * take float32, float64 and the 16- and 32-bit integer types, tiles of up to 131 072 pixels and 4 096 blocks (256 x 256, 257 x 257), and
+ * write header, mask section (run-length coded on the device), ranges, block stream and checksum.  Tiles whose outcome is decided
+ * elsewhere -- no valid pixel, a constant tile, NaN, the 16 x 16 retry of the low-bit-rate rule, one sweep -- and 8-bit types, larger tiles, maxZErr == 777 or 0 on float values are encoded inside the call, one by
+ * one, with the same result.  Status codes as for the unmasked calls. */
+LERC_AMD_API lerc_status lerc_amd_encode_tiles_device_masked(lerc_amd_context* ctx, const void* dTiles, unsigned int dataType, int nCols, int nRows,
+    int nTiles, const unsigned char* dValidBytes, double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity,
+    unsigned long long slotBytes, unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed);
+/* The way back.  dValidBytes: device, [nTiles][nRows][nCols], written 1 / 0 for EVERY tile (all ones for a blob without a mask section,
+ * all zeros for a blob without valid pixels); NULL: the call is lerc_amd_decode_tiles_device (WrongParam(2) as soon as a blob carries a
+ * mask).  Pixels: exactly what lerc_amd_decode_device writes for that blob (0 at invalid pixels).  The batch's launches take codec 6
+ * blobs in 8 x 8 tiling mode of the types and sizes above, with or without a mask section; every other blob (16 x 16 blocks, one sweep,
+ * constant, empty, older codecs, damaged ...) is decoded by itself inside the call.  A blob that fails leaves its tile zeroed, mask
+ * too; the other tiles are decoded all the same, and the call returns the first such status. */
+LERC_AMD_API lerc_status lerc_amd_decode_tiles_device_masked(lerc_amd_context* ctx, const unsigned char* dArena, const unsigned long long* offsets,
+    const unsigned int* sizes, int nTiles, int nCols, int nRows, unsigned int dataType, void* dTiles, unsigned char* dValidBytes);
+/* Diagnostics of the tile batch calls (masked or not): out[0] tiles whose blob the batch's own launches made, out[1] tiles encoded one by
+ * one behind the batch, out[2] / out[3] the same for decodes. */
+LERC_AMD_API void lerc_amd_tile_batch_counters(lerc_amd_context* ctx, unsigned long long out[4]);
 
 /* Per-kernel timing with HIP events on the context's stream (used by bench.py for the roofline of the
  * dominant kernel).  lerc_amd_profile_read writes lines "kernel_group total_ms launches" into buf. */

@@ -67,6 +67,12 @@ def load_library():
     lib.lerc_amd_decode_tiles_device_slots.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_ulonglong, ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_uint,
                                                        ct.c_void_p]
     lib.lerc_amd_build_info.restype = ct.c_char_p
+    lib.lerc_amd_encode_tiles_device_masked.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int, ct.c_int, ct.c_int, ct.c_void_p, ct.c_double,
+                                                        ct.c_void_p, ct.c_ulonglong, ct.c_ulonglong, ct.c_void_p, ct.c_void_p, ct.c_void_p]
+    lib.lerc_amd_decode_tiles_device_masked.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_uint,
+                                                        ct.c_void_p, ct.c_void_p]
+    lib.lerc_amd_tile_batch_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_ulonglong)]
+    lib.lerc_amd_tile_batch_counters.restype = None
     lib.lerc_amd_encode_device_async.argtypes = [ct.c_void_p] + enc + [ct.c_void_p, ct.c_uint, u32p]
     lib.lerc_amd_decode_device_async.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int, ct.c_void_p, ct.c_int, ct.c_int,
                                                  ct.c_int, ct.c_int, ct.c_uint, ct.c_void_p, u32p]
@@ -74,7 +80,7 @@ def load_library():
     for n in ("lerc_computeCompressedSize", "lerc_encode", "lerc_getBlobInfo", "lerc_getDataRanges", "lerc_decode",
               "lerc_amd_encode_device", "lerc_amd_decode_device", "lerc_amd_encode_tiles_device", "lerc_amd_decode_tiles_device",
               "lerc_amd_encode_device_async", "lerc_amd_decode_device_async", "lerc_amd_finish", "lerc_amd_encode_tiles_device_slots",
-              "lerc_amd_decode_tiles_device_slots"):
+              "lerc_amd_decode_tiles_device_slots", "lerc_amd_encode_tiles_device_masked", "lerc_amd_decode_tiles_device_masked"):
         getattr(lib, n).restype = ct.c_uint
     _LIB = lib
     return lib
@@ -224,6 +230,29 @@ class DeviceCodec:
         self.lib.lerc_amd_decode_refusals(self.h, out)
         return list(out)
 
+    def tile_batch_counters(self):
+        """tiles of the batch calls of this context: [encoded by the batch's own launches, encoded one by one behind the batch, decoded by
+        the batch's launches, decoded one by one]"""
+        out = (ct.c_ulonglong * 4)()
+        self.lib.lerc_amd_tile_batch_counters(self.h, out)
+        return list(out)
+
+    def encode_tiles_masked(self, d_tiles, dt_code, n_cols, n_rows, n_tiles, d_valid, max_z_err, d_arena, arena_cap, slot_bytes=0):
+        """raw device addresses -> (status, offsets uint64[nTiles], sizes uint32[nTiles], arena bytes used); d_valid 0 / None: all valid"""
+        offsets = np.zeros(n_tiles, np.uint64)
+        sizes = np.zeros(n_tiles, np.uint32)
+        used = ct.c_ulonglong(0)
+        rc = self.lib.lerc_amd_encode_tiles_device_masked(self.h, d_tiles, dt_code, n_cols, n_rows, n_tiles, d_valid or None, float(max_z_err),
+                                                          d_arena, int(arena_cap), int(slot_bytes), offsets.ctypes.data, sizes.ctypes.data,
+                                                          ct.byref(used))
+        return rc, offsets, sizes, int(used.value)
+
+    def decode_tiles_masked(self, d_arena, offsets, sizes, n_tiles, n_cols, n_rows, dt_code, d_tiles, d_valid):
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        sizes = np.ascontiguousarray(sizes, np.uint32)
+        return self.lib.lerc_amd_decode_tiles_device_masked(self.h, d_arena, offsets.ctypes.data, sizes.ctypes.data, n_tiles, n_cols, n_rows,
+                                                            dt_code, d_tiles, d_valid or None)
+
     def last_note(self):
         """why the last call that left the streaming kernels (or went down a streaming tier) did so; "" if none did"""
         self.lib.lerc_amd_last_note.argtypes = [ct.c_void_p]
@@ -337,3 +366,22 @@ def decode_tiles_device(codec, arena, offsets, sizes, out):
     sizes = np.ascontiguousarray(sizes, np.uint32)
     return codec.lib.lerc_amd_decode_tiles_device(codec.h, arena.data_ptr(), offsets.ctypes.data, sizes.ctypes.data, n_tiles, n_cols, n_rows,
                                                   _torch_dt_code(out), out.data_ptr())
+
+
+def encode_tiles_device_masked(codec, tiles, valid, max_z_err, arena, slot_bytes=0):
+    """tiles: CUDA(HIP) tensor [nTiles, nRows, nCols]; valid: uint8 CUDA tensor of the same shape (0 = invalid) or None; arena: uint8
+    CUDA tensor.  One blob per tile, each exactly what encode() makes of that tile with its mask; slot_bytes != 0 (a multiple of 16):
+    tile t's blob at arena[t * slot_bytes :].  -> (status, offsets uint64[nTiles], sizes uint32[nTiles], arena bytes used)"""
+    n_tiles, n_rows, n_cols = (int(v) for v in tiles.shape)
+    if valid is not None:
+        assert tuple(valid.shape) == tuple(tiles.shape) and valid.element_size() == 1 and valid.is_contiguous()
+    return codec.encode_tiles_masked(tiles.data_ptr(), _torch_dt_code(tiles), n_cols, n_rows, n_tiles, valid.data_ptr() if valid is not None else 0,
+                                     max_z_err, arena.data_ptr(), arena.numel(), slot_bytes)
+
+
+def decode_tiles_device_masked(codec, arena, offsets, sizes, out, valid_out):
+    """out: CUDA(HIP) tensor [nTiles, nRows, nCols]; valid_out: uint8 CUDA tensor of the same shape, written 1 / 0 for every tile (None:
+    decode_tiles_device, which refuses blobs with a mask).  A tile whose blob fails is left zeroed, mask too."""
+    n_tiles, n_rows, n_cols = (int(v) for v in out.shape)
+    return codec.decode_tiles_masked(arena.data_ptr(), offsets, sizes, n_tiles, n_cols, n_rows, _torch_dt_code(out), out.data_ptr(),
+                                     valid_out.data_ptr() if valid_out is not None else 0)

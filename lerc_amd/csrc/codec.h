@@ -84,6 +84,7 @@ public:
 
   // which kernels served the calls so far: [0] encode streaming, [1] encode general, [2] decode streaming, [3] decode general
   unsigned long long pathCount[4] = { 0, 0, 0, 0 };
+  unsigned long long tileBatchCount[4] = { 0, 0, 0, 0 };    // tiles of batch calls (lerc_amd_tile_batch_counters): [0] encoded by the batch's own launches, [1] encoded one by one behind it, [2] / [3] the same for decodes
   bool lastDecodeStreamed = false;
   unsigned long long formCount[4] = { 0, 0, 0, 0 };    // bands / tiles decoded by streaming form 1, 2, 3 (lerc_amd_decode_forms)
   unsigned long long refusalCount[4] = { 0, 0, 0, 0 };    // attempts thrown away (lerc_amd_decode_refusals): [0] the decode kernels refused the masked scan's block offsets, [1] the masked scan handed a band on, [2] a streaming decode tier handed a band on, [3] unused
@@ -176,6 +177,7 @@ struct TilesEncodeRequest
   u64* hOffsets = nullptr;            // host [nTiles]: where tile t's blob starts in the arena (16-byte aligned)
   u32* hSizes = nullptr;              // host [nTiles]
   u64 slotBytes = 0;                  // != 0: tile t's blob goes to dArena + t * slotBytes (a multiple of 16), nothing is moved afterwards
+  const u8* dValidBytes = nullptr;    // device [nTiles][nRows][nCols], 0 = invalid: a mask per tile (encodeTilesDeviceMasked); nullptr: every pixel valid
 };
 struct TilesDecodeRequest
 {
@@ -184,6 +186,7 @@ struct TilesDecodeRequest
   const u32* hSizes = nullptr;        // host [nTiles]
   int dt = 0, nCols = 0, nRows = 0, nTiles = 0;
   void* dOut = nullptr;               // device: [nTiles][nRows][nCols]
+  u8* dValidBytes = nullptr;          // device [nTiles][nRows][nCols], written 1 / 0 for every tile (decodeTilesDeviceMasked); nullptr: blobs with a mask are refused
 };
 
 struct DecodeRequest
@@ -215,6 +218,9 @@ bool decodeStreamingVerdict(Context& ctx, const u8* slot, u32 epoch, u32* bits =
 u32 decodeSpeculativeToHost(Context& ctx, const DecodeRequest& rq, void* hOut, size_t outBytes, u8* hMask, size_t maskBytes, bool& handled, bool& tried);    // tried: the streaming kernels were enqueued (and may have written pixels)
 u32 encodeTilesDevice(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed);
 u32 decodeTilesDevice(Context& ctx, const TilesDecodeRequest& rq);
+// the same with a validity mask per tile (codec_tiles_masked.cpp, tile_mask_batch.hip); without mask pointers they ARE the two calls above
+u32 encodeTilesDeviceMasked(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed);
+u32 decodeTilesDeviceMasked(Context& ctx, const TilesDecodeRequest& rq);
 
 // header-only queries (host)
 struct BlobInfo

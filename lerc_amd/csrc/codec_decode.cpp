@@ -997,6 +997,7 @@ u32 decodeTilesDevice(Context& ctx, const TilesDecodeRequest& rq)
     one.maxForm = batchForm > 0 ? batchForm - 1 : 4;    // the batch's kernels have just been tried: the next form (or, if the batch was the two-launch form, the general kernels); no batch launch: every form
     one.noStreaming = one.maxForm <= 0;
     const u32 rc = decodeDevice(ctx, one);
+    ctx.tileBatchCount[3]++;
     if (rc == kFailed)    // (a failed decode leaves zeros, include/lerc_amd.h: the streaming kernels may have written pixels of a damaged blob)
     {
       hipMemsetAsync(one.dOut, 0, (size_t)tileElems * tbytes, ctx.activeStream());
@@ -1064,7 +1065,7 @@ u32 decodeTilesDevice(Context& ctx, const TilesDecodeRequest& rq)
     {
       const u32 bits = fastFlagBits(hfb + 4 * i, epoch);
       const bool good = hp[i].ok && !bits && hp[i].checksumOk;
-      if (good) { ctx.pathCount[2]++; ctx.formCount[std::min(batchForm, 3)]++; }
+      if (good) { ctx.pathCount[2]++; ctx.tileBatchCount[2]++; ctx.formCount[std::min(batchForm, 3)]++; }
       else
       {
         if (redo.empty())

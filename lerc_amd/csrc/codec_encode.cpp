@@ -1272,6 +1272,7 @@ u32 encodeTilesDevice(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed
     if (rc != kOk) return rc;
     rq.hOffsets[t] = end; rq.hSizes[t] = written;
     end += written;
+    ctx.tileBatchCount[1]++;
     return kOk;
   };
 
@@ -1393,7 +1394,7 @@ u32 encodeTilesDevice(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed
         }
         rq.hOffsets[t0 + i] = slotted ? (u64)(t0 + i) * slotBytes : off[i];
         rq.hSizes[t0 + i] = res[i].blobSize;
-        ctx.pathCount[0]++;
+        ctx.pathCount[0]++; ctx.tileBatchCount[0]++;
       }
       if (anyStuck) ctx.wipePersistentState();
       if (direct) { u64 claimed; memcpy(&claimed, pin + (size_t)n * sizeof(FastEncodeResult), 8); end += claimed; }    // (incl. the room of tiles that were handed back: holes)
@@ -1412,14 +1413,14 @@ u32 encodeTilesDevice(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed
     {
       const int n = std::min(maxBatch, rq.nTiles - t0);
       const u64 end0 = end;
-      const unsigned long long count0 = ctx.pathCount[0];
+      const unsigned long long count0 = ctx.pathCount[0], batch0 = ctx.tileBatchCount[0];
       u32 rc = runBatch(t0, n, slotBytes, back);
       if (rc != kOk) return rc;
       size_t tooBig = 0;
       for (const auto& r : back) if (r.second == 64u) tooBig++;    // (kRedoCapacity and nothing else)
       if (!slotted && !direct && tooBig > (size_t)std::max(8, n / 32))
       {
-        end = end0; ctx.pathCount[0] = count0;
+        end = end0; ctx.pathCount[0] = count0; ctx.tileBatchCount[0] = batch0;
         for (int s0 = t0; s0 < t0 + n; s0 += maxBig)
         {
           rc = runBatch(s0, std::min(maxBig, t0 + n - s0), slotBig, back);
@@ -1465,7 +1466,7 @@ u32 encodeTilesDevice(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed
       }
       rq.hOffsets[t0 + i] = off[i];
       rq.hSizes[t0 + i] = res[i].blobSize;
-      ctx.pathCount[0]++;
+      ctx.pathCount[0]++; ctx.tileBatchCount[0]++;
     }
     end = off[n];
     for (int t : redo) { const u32 rc = encodeOne(t); if (rc != kOk) return rc; }    // (reuses the workspace: the batch is done with it)

@@ -1,0 +1,75 @@
+// tile_mask_batch.h -- batches of MASKED tiles (tile_mask_batch.hip): what the host hands the kernels and reads back.
+#pragma once
+#include "lerc_common.h"
+
+namespace lerc {
+
+// why a tile left the batch (it is then encoded / decoded by itself behind the batch, with its mask)
+enum : u32
+{
+  kTmbEmpty = 1u,         // no valid pixel: a header-only blob
+  kTmbConst = 2u,         // every valid pixel has the same value
+  kTmbNaN = 4u,           // a NaN at a valid pixel (the mask changes)
+  kTmbRetry16 = 32u,      // the low-bit-rate rule asks for 16 x 16 blocks
+  kTmbCapacity = 64u,     // the blob does not fit its slot (encoded by itself, that tile says BufferTooSmall)
+  kTmbArenaFull = 128u,   // the blob does not fit what is left of the arena
+  kTmbOneSweep = 256u,    // the raw form is no longer than the blocks
+  kTmbRle = 512u,         // the mask's run-length stream outgrew its scratch
+  // decode
+  kTmbHeader = 1024u,     // not a header the batch takes (codec < 6, another shape or type, 16 x 16 blocks, a mode byte, ...)
+  kTmbChecksum = 2048u,   // Fletcher32 differs
+  kTmbMaskStream = 4096u, // the mask's run-length stream is damaged
+  kTmbBlocks = 8192u,     // the walk met a block header that cannot be, or the blocks do not end where the blob does
+  kTmbSibling = 16384u    // a block's decode failed (raised by the block kernel's waves)
+};
+
+struct TmbTile    // one per tile, device; copied home after the batch
+{
+  u32 flags;              // 0: the batch's kernels did the tile
+  u32 numValid;
+  u32 rleLen;             // bytes of the mask section's run-length stream (0: every pixel valid)
+  u32 nBytesTiling;       // bytes of the block stream
+  u32 blobSize;
+  u32 dataBegin;          // where the block stream begins in the blob
+  u64 offset;             // where the blob lies in the arena
+  u64 minBits, maxBits;   // range over the valid pixels, as raw values of the tile's type
+  double zMin, zMax;
+  double maxZErr;         // the tile's own error bound (encode: k_tmb_prelude decides it; decode: the header's)
+  u32 checksum;           // decode: the header's
+  u32 isInt;              // encode: float values that are all integers (header byte)
+};
+
+struct TmbGeom
+{
+  int nRows, nCols, nTV, nTH, dt;
+  u32 nTiles;
+  u32 bitStride;          // bytes between the tiles' bit masks (a multiple of 16)
+  u32 rleStride;          // bytes between the tiles' run-length scratch
+  u32 posStride;          // words between the tiles' block tables (>= nTV * nTH + 1)
+  u64 tileElems;
+};
+
+static const u32 kTmbMaxMaskBytes = 16384;    // a tile's bit mask in LDS: 128 K pixels (257 x 257 is 8 257 bytes)
+static const u32 kTmbMaxBlocks = 4096;
+
+struct TmbEncodeBuffers
+{
+  TmbTile* tiles;
+  u8* bits;               // [nTiles][bitStride]
+  u8* rle;                // [nTiles][rleStride]
+  u32* blockOff;          // [nTiles][posStride]: sizes, then their exclusive scan
+};
+// maxZErr: the header's for a tile whose statistics decide nothing else; cand: TryRaiseMaxZError candidates whose error bound beats it (bit c: factor c)
+void launchTmbEncode(const TmbGeom& g, const BandParams& bp, double maxZErr, u32 cand, const void* dTiles, const u8* dValidBytes, u8* dArena,
+                     u64 arenaBase, u64 arenaCapacity, u64 slotBytes, u64 firstTile, const TmbEncodeBuffers& b, hipStream_t st);
+
+struct TmbDecodeBuffers
+{
+  TmbTile* tiles;
+  u8* bits;               // [nTiles][bitStride]
+  u32* blockOff;          // [nTiles][posStride]
+};
+void launchTmbDecode(const TmbGeom& g, const u8* dArena, const u64* dOffsets, const u32* dSizes, void* dTiles, u8* dValidBytes,
+                     const TmbDecodeBuffers& b, hipStream_t st);
+
+}    // namespace lerc

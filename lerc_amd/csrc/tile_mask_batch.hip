@@ -1,0 +1,749 @@
+// tile_mask_batch.hip -- batches of MASKED tiles: nTiles rasters of one shape, each with a validity mask of its own, encoded into
+// (decoded from) nTiles independent Lerc2 blobs by ONE set of launches, a tile per blockIdx.y (or per workgroup) -- no launch, no
+// copy and no host wait per tile.
+//
+// Encode (launchTmbEncode), every section of a masked band's blob made on the device:
+//   1. k_tmb_prelude   a workgroup per tile: byte mask -> bit mask (BitMask's layout: most significant bit first) in LDS and in
+//                      global memory, the count of valid pixels, the range over them, NaN findings, the tile's own error bound (all-integer
+//                      float values, TryRaiseMaxZError), and the mask's run-length stream (RLE.cpp:123-254, the same bytes as rleEncode, codec_common.cpp)
+//   2. k_tmb_blocks<false>   a wave per 8 x 8 block: the block's size (the general encoder's decisions, tile_encode.hip)
+//   3. k_tmb_decide    a workgroup per tile: the sizes' exclusive scan, the 16 x 16 retry rule (Lerc2.cpp:333-357), one sweep, the
+//                      blob's size, the slot check;  k_tmb_arena: one workgroup places the blobs in a packed arena (16-byte aligned)
+//   4. k_tmb_blocks<true>    the blocks' bytes, and one more workgroup per tile that writes header, mask section, ranges and the
+//                      "not one sweep" byte
+//   5. k_tmb_checksum  a workgroup per tile: Fletcher32 over blob[14 ..) (Lerc2.cpp:1037-1064), stored into the header.  It reads
+//                      the finished blob, whatever the parity of the mask section's length.
+// Tiles whose outcome is decided elsewhere (TmbTile::flags) are left alone; the host encodes them one by one behind the batch.
+// No workgroup waits for another one inside a launch, so the emulator build runs the same path.
+//
+// Decode (launchTmbDecode):
+//   1. k_tmbd_parse    a workgroup per tile: header, Fletcher32, the mask's run-length stream expanded into LDS (bounded by the
+//                      section's length and the mask's size), valid counts per block by popcount, the caller's valid bytes, and the
+//                      walk over the block headers -- a block's length follows from its header and its valid count, which is known
+//                      here -- into a table of block offsets
+//   2. k_tmbd_blocks   a wave per block: the general decoder's block (tile_decode.hip), checked against the table
+// Every walk is bounded by the blob's size; whatever does not fit raises a flag and the host repeats that tile with the
+// single-blob decoder, which also yields the exact status of a damaged blob.
+#include <cstdio>
+#include <cstdlib>
+#include "kernels.h"
+#include "wave_utils.h"
+#include "block_plan.h"
+#include "tile_encode_dev.h"
+#include "tile_decode_dev.h"
+#include "tile_mask_batch.h"
+
+namespace lerc {
+
+static const u32 kHdr6 = 90;    // bytes of a codec 6 header (headerBytes(6), codec_common.cpp)
+
+template<class T> struct TmbAcc { typedef i64 type; static __device__ __forceinline__ i64 hi() { return 0x7FFFFFFFFFFFFFFFll; } static __device__ __forceinline__ i64 lo() { return -0x7FFFFFFFFFFFFFFFll - 1; } };
+template<> struct TmbAcc<float> { typedef double type; static __device__ __forceinline__ double hi() { return __builtin_huge_val(); } static __device__ __forceinline__ double lo() { return -__builtin_huge_val(); } };
+template<> struct TmbAcc<double> { typedef double type; static __device__ __forceinline__ double hi() { return __builtin_huge_val(); } static __device__ __forceinline__ double lo() { return -__builtin_huge_val(); } };
+
+// sums of a workgroup's 256 threads (s: 4 words of LDS); every thread gets the result
+__device__ __forceinline__ u64 blockSum(u64 v, u64* s)
+{
+  v = waveSum(v);
+  __syncthreads();
+  if (laneId() == 0) s[waveId()] = v;
+  __syncthreads();
+  return s[0] + s[1] + s[2] + s[3];
+}
+
+// Fletcher32 terms of bytes[0 .. len): byte p counts as byte << 8 where p is even, with weight p >> 1 (misc_kernels.hip:
+// k_fletcher); A, B mod 65535 in every thread.  16-byte loads from the first aligned address on.
+__device__ __forceinline__ void blockFletcher(const u8* __restrict__ bytes, u32 len, u64* s, u64& Aout, u64& Bout)
+{
+  u64 A = 0, B = 0;
+  const u32 head = min(len, (u32)((16u - ((u32)(uintptr_t)bytes & 15u)) & 15u));
+  const u32 nVec = (len - head) >> 4;
+  const uint4* vec = reinterpret_cast<const uint4*>(bytes + head);
+  for (u32 i = threadIdx.x; i < nVec; i += 256u)
+  {
+    const u32 q = head + (i << 4), odd = q & 1u;
+    const uint4 x = vec[i];
+    const u32 w[4] = { x.x, x.y, x.z, x.w };
+    u32 sumC = 0, inner = 0;
+#pragma unroll
+    for (u32 j = 0; j < 16u; j++)
+    {
+      const u32 byte = (w[j >> 2] >> (8u * (j & 3u))) & 255u;
+      const u32 c = byte << (((odd + j) & 1u) ? 0u : 8u);
+      sumC += c;
+      inner += ((odd + j) >> 1) * c;
+    }
+    A += sumC;
+    B += (u64)(q >> 1) * sumC + inner;
+  }
+  if (threadIdx.x == 0)
+  {
+    for (u32 p = 0; p < head; p++) { const u32 c = (u32)bytes[p] << ((p & 1u) ? 0 : 8); A += c; B += (u64)(p >> 1) * c; }
+    for (u32 p = head + (nVec << 4); p < len; p++) { const u32 c = (u32)bytes[p] << ((p & 1u) ? 0 : 8); A += c; B += (u64)(p >> 1) * c; }
+  }
+  A %= 65535u; B %= 65535u;
+  Aout = blockSum(A, s) % 65535u;
+  Bout = blockSum(B, s) % 65535u;
+}
+
+__device__ __forceinline__ u32 fletcherFold(u64 A, u64 B, u32 len)    // fletcherFinish (misc_kernels.hip)
+{
+  const u64 N = ((u64)len + 1) / 2;
+  u64 s1 = A % 65535u;
+  u64 s2 = ((N % 65535u) * s1 + 65535u - (B % 65535u)) % 65535u;
+  if (s1 == 0) s1 = 0xffff;
+  if (s2 == 0) s2 = 0xffff;
+  return (u32)((s2 << 16) | s1);
+}
+
+// ================================================================================================
+// encode
+// ================================================================================================
+template<class T>
+__global__ void __launch_bounds__(256)
+k_tmb_prelude(TmbGeom g, double maxZErr, u32 cand, const T* __restrict__ data, const u8* __restrict__ valid, TmbEncodeBuffers b)
+{
+  typedef typename TmbAcc<T>::type Acc;
+  constexpr bool isFlt = DtOf<T>::v >= DT_Float;
+  __shared__ __align__(16) u8 s_bits[kTmbMaxMaskBytes + 16];
+  __shared__ u64 s_red[4];
+  __shared__ Acc s_mn[4], s_mx[4];
+  __shared__ u64 s_raise[4][9];
+  const u32 t = blockIdx.x;
+  const u32 nPix = (u32)g.tileElems, nBytes = (nPix + 7u) >> 3;
+  const T* __restrict__ px = data + (u64)t * g.tileElems;
+  const u8* __restrict__ vb = valid + (u64)t * g.tileElems;
+  u8* __restrict__ bitsOut = b.bits + (u64)t * g.bitStride;
+  const int facCand[9] = { 1, 2, 10, 20, 100, 200, 1000, 2000, 10000 };
+
+  u32 cnt = 0, flags = 0;
+  Acc mn = TmbAcc<T>::hi(), mx = TmbAcc<T>::lo();
+  bool frac = false;
+  double rerr[9];
+#pragma unroll
+  for (int c = 0; c < 9; c++) rerr[c] = 0;
+  for (u32 by = threadIdx.x; by < nBytes; by += 256u)
+  {
+    u32 m = 0;
+    for (u32 j = 0; j < 8u; j++)
+    {
+      const u32 k = 8u * by + j;
+      if (k >= nPix) { m |= 0x80u >> j; continue; }    // tail bits stay set, like BitMask::SetAllValid + SetInvalid (Lerc.cpp:959-975)
+      if (vb[k] == 0) continue;
+      m |= 0x80u >> j;
+      cnt++;
+      const T v = px[k];
+      if (isFlt && v != v) { flags |= kTmbNaN; continue; }
+      const Acc a = (Acc)v;
+      mn = a < mn ? a : mn; mx = a > mx ? a : mx;
+      if (isFlt)
+      {
+        const double x = (double)v;
+        if (!(v == (T)floor(x + 0.5))) frac = true;    // Lerc.h:271 IsInt
+        // TryRaiseMaxZError (Lerc2.cpp:1233-1318): the largest rounding error per candidate factor.  Every factor is a multiple of
+        // the ones in front of it, so a value that one factor makes an integer adds nothing to the later ones either way.
+#pragma unroll
+        for (int c = 0; c < 9; c++)
+          if ((cand >> c) & 1u)
+          {
+            const double z = x * facCand[c];
+            const double dlt = fabs(floor(z + 0.5) - z);
+            rerr[c] = dlt > rerr[c] ? dlt : rerr[c];
+          }
+      }
+    }
+    s_bits[by] = (u8)m;
+    bitsOut[by] = (u8)m;
+  }
+  for (u32 by = nBytes + threadIdx.x; by < nBytes + 16u; by += 256u) s_bits[by] = 0;
+  const u32 numValid = (u32)blockSum((u64)cnt, s_red);
+  const u32 anyFlags = (u32)blockSum((u64)flags, s_red) ? kTmbNaN : 0u;    // (the only flag raised so far)
+  const u32 anyFrac = (u32)blockSum(frac ? 1ull : 0ull, s_red);
+  mn = waveMin(mn); mx = waveMax(mx);
+  if (isFlt && cand)
+  {
+#pragma unroll
+    for (int c = 0; c < 9; c++)
+    {
+      u64 bb; double r = rerr[c]; memcpy(&bb, &r, 8);    // non-negative doubles order like their bit patterns
+      bb = waveMax(bb);
+      if (laneId() == 0) s_raise[waveId()][c] = bb;
+    }
+  }
+  if (laneId() == 0) { s_mn[waveId()] = mn; s_mx[waveId()] = mx; }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+
+  for (int w = 1; w < 4; w++) { mn = s_mn[w] < mn ? s_mn[w] : mn; mx = s_mx[w] > mx ? s_mx[w] : mx; }
+  TmbTile ti;
+  memset(&ti, 0, sizeof(ti));
+  ti.numValid = numValid;
+  u32 fl = anyFlags;
+  if (numValid == 0) fl |= kTmbEmpty;
+  else if (!(mn < mx)) fl |= kTmbConst;
+  if (numValid)
+  {
+    ti.zMin = (double)mn; ti.zMax = (double)mx;
+    ti.minBits = typedBits(ti.zMin, g.dt); ti.maxBits = typedBits(ti.zMax, g.dt);
+  }
+  // ---- the tile's own error bound, as Lerc::FilterNoDataAndNaN and Lerc2::TryRaiseMaxZError decide it from the statistics
+  // (encodeBand, codec_encode.cpp, restated per tile): float values that are all integers inside the type's exact range make the
+  // tile an integer one (isInt in the header, bound max(0.5, floor)); else the first candidate bound every valid value agrees with
+  ti.maxZErr = maxZErr;
+  if (isFlt && numValid)
+  {
+    const double lim = (g.dt == DT_Float) ? (double)(1 << 23) : (double)(1ll << 53);
+    if (!anyFrac && ti.zMin >= -lim && ti.zMin <= lim && ti.zMax >= -lim && ti.zMax <= lim)
+    {
+      ti.isInt = 1u;
+      const double fl0 = floor(maxZErr);
+      ti.maxZErr = fl0 > 0.5 ? fl0 : 0.5;
+    }
+    else if (cand)
+    {
+      const double errCand[9] = { 1, 0.5, 0.1, 0.05, 0.01, 0.005, 0.001, 0.0005, 0.0001 };
+      for (int c = 0; c < 9; c++)
+        if ((cand >> c) & 1u)
+        {
+          u64 bb = 0;
+          for (int w = 0; w < 4; w++) bb = s_raise[w][c] > bb ? s_raise[w][c] : bb;
+          double r; memcpy(&r, &bb, 8);
+          if (r / facCand[c] <= maxZErr / 2) { ti.maxZErr = errCand[c] / 2; break; }
+        }
+    }
+  }
+
+  // ---- the mask's run-length stream: [int16 n][payload] ..., n > 0 literal bytes, n < 0 one byte -n times, -32768 ends it; a run
+  // is opened only where at least 5 equal bytes start and one more byte follows; segments are cut at 32767
+  u32 rleLen = 0;
+  if (fl == 0 && numValid < nPix)
+  {
+    u8* __restrict__ out = b.rle + (u64)t * g.rleStride;
+    const u32 cap = g.rleStride, n = nBytes;
+    u32 at = 0, i = 0;
+    bool fits = true;
+    while (i < n && fits)
+    {
+      const u32 litBeg = i;
+      while (i < n)
+      {
+        const bool runStarts = (i + 5 < n) && s_bits[i] == s_bits[i + 1] && s_bits[i] == s_bits[i + 2] && s_bits[i] == s_bits[i + 3] && s_bits[i] == s_bits[i + 4];
+        if (runStarts) break;
+        i++;
+      }
+      for (u32 p = litBeg; p < i && fits;)
+      {
+        const u32 len = min(32767u, i - p);
+        if (at + 2u + len + 8u > cap) { fits = false; break; }
+        out[at] = (u8)(len & 255u); out[at + 1] = (u8)(len >> 8); at += 2;
+        for (u32 q = 0; q < len; q++) out[at + q] = s_bits[p + q];
+        at += len; p += len;
+      }
+      if (i >= n || !fits) break;
+      u32 e = i;
+      while (e + 1 < n && s_bits[e + 1] == s_bits[i]) e++;
+      for (u32 left = e - i + 1; left > 0 && fits;)
+      {
+        const u32 len = min(32767u, left);
+        if (at + 3u + 8u > cap) { fits = false; break; }
+        const u32 neg = (u32)(-(int)len) & 0xFFFFu;
+        out[at] = (u8)(neg & 255u); out[at + 1] = (u8)(neg >> 8); out[at + 2] = s_bits[i]; at += 3;
+        left -= len;
+      }
+      i = e + 1;
+    }
+    if (fits && at + 2u <= cap) { out[at] = 0x00; out[at + 1] = 0x80; at += 2; rleLen = at; }
+    else fl |= kTmbRle;
+  }
+  ti.flags = fl;
+  ti.rleLen = rleLen;
+  ti.dataBegin = kHdr6 + 4u + rleLen + 2u * (u32)sizeof(T) + 1u;    // header, mask section, ranges, "not one sweep"
+  b.tiles[t] = ti;
+}
+
+// A wave per 8 x 8 block of a tile (blockIdx.y): k_encode_tiles (tile_encode.hip) for one value a pixel, with the tile's own mask,
+// "all valid" and place in the arena.  WRITE: the workgroup behind the last block writes what lies in front of the block stream.
+template<class T, bool WRITE>
+__global__ void __launch_bounds__(256)
+k_tmb_blocks(TmbGeom g, BandParams p, const T* __restrict__ data, u8* __restrict__ arena, TmbEncodeBuffers b)
+{
+  constexpr int NMAX = 64;
+  constexpr int OBW = (1 + NMAX * (int)sizeof(T) + 3) / 4 + 4;
+  __shared__ T s_val[4][NMAX];
+  __shared__ u32 s_obuf[4][WRITE ? OBW : 1];
+  __shared__ u32 s_lut[4][WRITE ? NMAX : 1];
+  __shared__ u8 s_hdr[WRITE ? 96 : 1];
+  const u32 t = blockIdx.y;
+  const TmbTile ti = b.tiles[t];
+  if (ti.flags) return;
+  const int nPos = g.nTV * g.nTH;
+  const u32 nPix = (u32)g.tileElems;
+  u8* __restrict__ blob = WRITE ? arena + ti.offset : nullptr;
+
+  if (WRITE && blockIdx.x == gridDim.x - 1)
+  {
+    // ---- header (Lerc2.cpp:724-786; checksum patched by k_tmb_checksum), mask section, ranges, "not one sweep"
+    if (threadIdx.x == 0)
+    {
+      u8* h = s_hdr;
+      const char magic[6] = { 'L', 'e', 'r', 'c', '2', ' ' };
+      for (int i = 0; i < 6; i++) h[i] = (u8)magic[i];
+      const int ints[10] = { kCodecVersion, 0, g.nRows, g.nCols, 1, (int)ti.numValid, 8, (int)ti.blobSize, g.dt, 0 };
+      for (int i = 0; i < 10; i++) putBytes(h + 6 + 4 * i, (u64)(u32)ints[i], 4);
+      putBytes(h + 46, ti.isInt ? 0x100ull : 0ull, 4);    // passNoData, isInt, two reserved bytes
+      const double dbl[5] = { ti.maxZErr, ti.zMin, ti.zMax, 0.0, 0.0 };
+      for (int i = 0; i < 5; i++) { u64 bits; memcpy(&bits, &dbl[i], 8); putBytes(h + 50 + 8 * i, bits, 8); }
+      putBytes(h + kHdr6, (u64)ti.rleLen, 4);
+    }
+    __syncthreads();
+    for (u32 i = threadIdx.x; i < kHdr6 + 4u; i += 256u) blob[i] = s_hdr[i];
+    const u8* __restrict__ rle = b.rle + (u64)t * g.rleStride;
+    for (u32 i = threadIdx.x; i < ti.rleLen; i += 256u) blob[kHdr6 + 4u + i] = rle[i];
+    if (threadIdx.x == 0)
+    {
+      u8* r = blob + kHdr6 + 4u + ti.rleLen;
+      putBytes(r, ti.minBits, (int)sizeof(T));
+      putBytes(r + sizeof(T), ti.maxBits, (int)sizeof(T));
+      r[2 * sizeof(T)] = 0;
+    }
+    return;
+  }
+
+  const int w = waveId(), lane = laneId();
+  const int pos = (int)blockIdx.x * 4 + w;
+  if (pos >= nPos) return;    // whole wave leaves together
+  p.allValid = (ti.numValid == nPix) ? 1 : 0;
+  p.maxZErr = ti.maxZErr; p.scale = 1 / (2 * ti.maxZErr); p.invScale = 2 * ti.maxZErr;    // (the tile's own bound: k_tmb_prelude)
+  const T* __restrict__ px = data + (u64)t * g.tileElems;
+  const u8* __restrict__ maskBits = b.bits + (u64)t * g.bitStride;
+  u32* __restrict__ table = b.blockOff + (u64)t * g.posStride;
+  const int it = pos / g.nTH, jt = pos - it * g.nTH;
+  const int i0 = it * 8, j0 = jt * 8;
+  const int tileH = min(8, g.nRows - i0), tileW = min(8, g.nCols - j0);
+  const int nElem = tileH * tileW;
+  const u64 lt = laneMaskLt();
+
+  int rank[1];
+  T v[1];
+  u32 q[1];
+  const bool inb = lane < nElem;
+  const int r = inb ? lane / tileW : 0, c = inb ? lane - r * tileW : 0;
+  const i64 pix = (i64)(i0 + r) * g.nCols + (j0 + c);
+  const bool valid = inb && (p.allValid || maskBit(maskBits, pix));
+  const u64 bal = __ballot(valid);
+  rank[0] = valid ? __popcll(bal & lt) : -1;
+  const int n = __popcll(bal);
+
+  if (n == 0)    // empty position: one "all zero" byte (Lerc2.cpp:1534-1538, :1960-1966)
+  {
+    if (WRITE) { if (lane == 0) blob[ti.dataBegin + table[pos]] = (u8)(((u32)(((j0 >> 3) & 15) << 2) & 0x38u) | 2u); }
+    else if (lane == 0) table[pos] = 1u;
+    return;
+  }
+  T* valBuf = s_val[w];
+  v[0] = T(0);
+  if (valid) { v[0] = px[pix]; valBuf[rank[0]] = v[0]; }
+  waveSync();
+
+  // --- statistics (GetValidDataAndStats)
+  T mn = valBuf[0], mx = valBuf[0];
+  if (valid) { mn = v[0]; mx = v[0]; }
+  mn = waveMinT(mn);
+  mx = waveMaxT(mx);
+  bool s = false;
+  if (rank[0] > 0) s = (v[0] == valBuf[rank[0] - 1]);
+  else if (rank[0] == 0) s = p.allValid ? (v[0] == T(0)) : false;    // prevVal starts at 0 (all-valid branch only)
+  const int same = __popcll(__ballot(s));
+  const bool tryLut = (n > 4) && ((double)mx > (double)mn + 3 * p.maxZErr) && (2 * same > n);
+
+  double mv = 0;
+  bool quantOk = false;
+  if (p.maxZErr > 0)
+  {
+    mv = ((double)mx - (double)mn) * p.scale;
+    quantOk = !(mv > (double)p.maxQ || (u32)(mv + 0.5) == 0);
+  }
+  u32 qMax = 0;
+  q[0] = 0;
+  if (quantOk)
+  {
+    if (valid) q[0] = p.intLossless ? quantLossless<T>(v[0], mn) : (u32)(((double)v[0] - (double)mn) * p.scale + 0.5);
+    qMax = waveMax(q[0]);
+  }
+  u32 nDistinct = 0;
+  if (tryLut && quantOk)
+  {
+    u32 idxTmp[1];
+    nDistinct = extractDistinct<1>(q, rank, nullptr, idxTmp);
+  }
+  const Plan plan = planBlock<T>(p, n, mn, mx, p.dt, tryLut, mv, qMax, nDistinct);
+  if (!WRITE) { if (lane == 0) table[pos] = (u32)plan.nBytes; return; }
+
+  u32* obuf = s_obuf[w];
+  composeBlock<T, 1>(obuf, s_lut[w], p, plan, n, j0, false, mn, v, q, rank, qMax);
+  const u8* ob8 = reinterpret_cast<const u8*>(obuf);
+  u8* __restrict__ dst = blob + ti.dataBegin + table[pos];
+  for (int i = lane; i < plan.nBytes; i += 64) dst[i] = ob8[i];
+}
+
+// exclusive scan of x[0 .. n) in place by one workgroup of 256 threads, x[n] = the total (s: 256 words of LDS)
+__device__ __forceinline__ u32 blockScanInPlace(u32* __restrict__ x, u32 n, u32* s)
+{
+  const u32 per = (n + 255u) / 256u, from = min(n, threadIdx.x * per), to = min(n, from + per);
+  u32 sum = 0;
+  for (u32 i = from; i < to; i++) sum += x[i];
+  s[threadIdx.x] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) { u32 run = 0; for (u32 i = 0; i < 256u; i++) { const u32 y = s[i]; s[i] = run; run += y; } s[256] = run; }
+  __syncthreads();
+  u32 run = s[threadIdx.x];
+  for (u32 i = from; i < to; i++) { const u32 y = x[i]; x[i] = run; run += y; }
+  const u32 total = s[256];
+  if (threadIdx.x == 0) x[n] = total;
+  return total;
+}
+
+__global__ void __launch_bounds__(256) k_tmb_decide(TmbGeom g, u32 tb, u64 slotBytes, u64 firstTile, TmbEncodeBuffers b)
+{
+  __shared__ u32 s_scan[257];
+  const u32 t = blockIdx.x;
+  if (b.tiles[t].flags) return;
+  const u32 nPos = (u32)(g.nTV * g.nTH);
+  const u32 nBytesTiling = blockScanInPlace(b.blockOff + (u64)t * g.posStride, nPos, s_scan);
+  if (threadIdx.x != 0) return;
+  TmbTile& ti = b.tiles[t];
+  const u64 nPix = g.tileElems, oneSweep = (u64)tb * ti.numValid;
+  u32 fl = 0;
+  // 16 x 16 blocks at low bit rates (Lerc2.cpp:333-357; nPix counts invalid pixels too)
+  if ((double)((u64)nBytesTiling * 8u) < (double)nPix * 1.5 && (u64)nBytesTiling < 4u * oneSweep && (g.nRows > 8 || g.nCols > 8)) fl |= kTmbRetry16;
+  if (oneSweep <= (u64)nBytesTiling) fl |= kTmbOneSweep;
+  ti.nBytesTiling = nBytesTiling;
+  ti.blobSize = ti.dataBegin + nBytesTiling;
+  if (slotBytes)
+  {
+    ti.offset = (firstTile + t) * slotBytes;
+    if ((u64)ti.blobSize > slotBytes) fl |= kTmbCapacity;
+  }
+  ti.flags = fl;
+}
+
+// packed arena: the batch's blobs back to back at 16-byte aligned offsets from arenaBase on, in tile order
+__global__ void __launch_bounds__(256) k_tmb_arena(u32 nTiles, u64 arenaBase, u64 arenaCapacity, TmbEncodeBuffers b)
+{
+  __shared__ u64 s_part[257];
+  const u32 per = (nTiles + 255u) / 256u, from = min(nTiles, threadIdx.x * per), to = min(nTiles, from + per);
+  u64 sum = 0;
+  for (u32 i = from; i < to; i++) if (!b.tiles[i].flags) sum += ((u64)b.tiles[i].blobSize + 15ull) & ~15ull;
+  s_part[threadIdx.x] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) { u64 run = 0; for (u32 i = 0; i < 256u; i++) { const u64 y = s_part[i]; s_part[i] = run; run += y; } s_part[256] = run; }
+  __syncthreads();
+  u64 run = arenaBase + s_part[threadIdx.x];
+  for (u32 i = from; i < to; i++)
+  {
+    TmbTile& ti = b.tiles[i];
+    if (ti.flags) continue;
+    ti.offset = run;
+    if (run + ti.blobSize > arenaCapacity) ti.flags |= kTmbArenaFull;
+    run += ((u64)ti.blobSize + 15ull) & ~15ull;
+  }
+}
+
+__global__ void __launch_bounds__(256) k_tmb_checksum(u8* __restrict__ arena, TmbEncodeBuffers b)
+{
+  __shared__ u64 s_red[4];
+  const TmbTile ti = b.tiles[blockIdx.x];
+  if (ti.flags) return;
+  u8* __restrict__ blob = arena + ti.offset;
+  u64 A, B;
+  blockFletcher(blob + 14, ti.blobSize - 14u, s_red, A, B);
+  if (threadIdx.x == 0) putBytes(blob + 10, (u64)fletcherFold(A, B, ti.blobSize - 14u), 4);
+}
+
+template<class T>
+static void tmbEncodeT(const TmbGeom& g, const BandParams& bp, double maxZErr, u32 cand, const void* dTiles, const u8* dValidBytes, u8* dArena,
+                       u64 arenaBase, u64 arenaCapacity, u64 slotBytes, u64 firstTile, const TmbEncodeBuffers& b, hipStream_t st)
+{
+  const int nPos = g.nTV * g.nTH;
+  const dim3 perTile(g.nTiles), blk(256);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_prelude<T>), perTile, blk, 0, st, g, maxZErr, cand, (const T*)dTiles, dValidBytes, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_blocks<T, false>), dim3((nPos + 3) / 4, g.nTiles), blk, 0, st, g, bp, (const T*)dTiles, (u8*)nullptr, b);
+  hipLaunchKernelGGL(k_tmb_decide, perTile, blk, 0, st, g, (u32)sizeof(T), slotBytes, firstTile, b);
+  if (!slotBytes) hipLaunchKernelGGL(k_tmb_arena, dim3(1), blk, 0, st, g.nTiles, arenaBase, arenaCapacity, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_blocks<T, true>), dim3((nPos + 3) / 4 + 1, g.nTiles), blk, 0, st, g, bp, (const T*)dTiles, dArena, b);
+  hipLaunchKernelGGL(k_tmb_checksum, perTile, blk, 0, st, dArena, b);
+}
+
+void launchTmbEncode(const TmbGeom& g, const BandParams& bp, double maxZErr, u32 cand, const void* dTiles, const u8* dValidBytes, u8* dArena,
+                     u64 arenaBase, u64 arenaCapacity, u64 slotBytes, u64 firstTile, const TmbEncodeBuffers& b, hipStream_t st)
+{
+  switch (g.dt)
+  {
+    case DT_Short:  tmbEncodeT<short>(g, bp, maxZErr, cand, dTiles, dValidBytes, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st); break;
+    case DT_UShort: tmbEncodeT<unsigned short>(g, bp, maxZErr, cand, dTiles, dValidBytes, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st); break;
+    case DT_Int:    tmbEncodeT<int>(g, bp, maxZErr, cand, dTiles, dValidBytes, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st); break;
+    case DT_UInt:   tmbEncodeT<unsigned int>(g, bp, maxZErr, cand, dTiles, dValidBytes, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st); break;
+    case DT_Float:  tmbEncodeT<float>(g, bp, maxZErr, cand, dTiles, dValidBytes, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st); break;
+    case DT_Double: tmbEncodeT<double>(g, bp, maxZErr, cand, dTiles, dValidBytes, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st); break;
+    default: break;
+  }
+}
+
+// ================================================================================================
+// decode
+// ================================================================================================
+template<class T>
+__global__ void __launch_bounds__(256)
+k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ offsets, const u32* __restrict__ sizes, u8* __restrict__ validOut,
+             TmbDecodeBuffers b)
+{
+  constexpr u32 TB = (u32)sizeof(T);
+  __shared__ __align__(16) u8 s_bits[kTmbMaxMaskBytes + 16];
+  __shared__ u16 s_nv[kTmbMaxBlocks];
+  __shared__ u64 s_red[4];
+  __shared__ TmbTile s_ti;
+  __shared__ u32 s_flags, s_nm;
+  const u32 t = blockIdx.x;
+  const u8* __restrict__ blob = arena + offsets[t];
+  const u32 sizeGiven = sizes[t];
+  const u32 nPix = (u32)g.tileElems, nBytes = (nPix + 7u) >> 3;
+  const u32 nPos = (u32)(g.nTV * g.nTH);
+
+  if (threadIdx.x == 0)
+  {
+    TmbTile ti;
+    memset(&ti, 0, sizeof(ti));
+    u32 fl = 0, nm = 0;
+    if (sizeGiven < kHdr6 + 4u + 2u * TB + 2u) fl = kTmbHeader;
+    else
+    {
+      const char magic[6] = { 'L', 'e', 'r', 'c', '2', ' ' };
+      for (int i = 0; i < 6; i++) if (blob[i] != (u8)magic[i]) fl = kTmbHeader;
+      int ints[10];
+      for (int i = 0; i < 10; i++) ints[i] = (int)(u32)getBytes(blob + 6 + 4 * i, 4);
+      double dbl[3];
+      for (int i = 0; i < 3; i++) { const u64 bits = getBytes(blob + 50 + 8 * i, 8); memcpy(&dbl[i], &bits, 8); }
+      const u32 flagBytes = (u32)getBytes(blob + 46, 4);    // passNoData, isInt, reserved
+      ti.checksum = (u32)ints[1];
+      ti.numValid = (u32)ints[5];
+      ti.blobSize = (u32)ints[7];
+      ti.maxZErr = dbl[0]; ti.zMin = dbl[1]; ti.zMax = dbl[2];
+      if (ints[0] != kCodecVersion || ints[2] != g.nRows || ints[3] != g.nCols || ints[4] != 1 || ints[5] <= 0 || (u32)ints[5] > nPix || ints[6] != 8
+        || ints[7] < (int)(kHdr6 + 4u + 2u * TB + 2u) || (u32)ints[7] > sizeGiven || ints[8] != g.dt || ints[9] != 0 || (flagBytes & 0xFFu) != 0u)
+        fl = kTmbHeader;
+      // (an error bound of 0 is the lossless float mode or a stream this decoder has not been pinned on; NaN fails every comparison)
+      if (!(ti.maxZErr > 0) || !(ti.maxZErr < 1e300) || !(ti.zMin < ti.zMax)) fl = kTmbHeader;
+      if (!fl)
+      {
+        nm = (u32)getBytes(blob + kHdr6, 4);
+        const bool allValid = ti.numValid == nPix;
+        if (allValid ? nm != 0u : (nm < 2u || nm > ti.blobSize)) fl = kTmbHeader;
+        else if ((u64)kHdr6 + 4u + nm + 2u * TB + 1u >= (u64)ti.blobSize) fl = kTmbHeader;
+        else
+        {
+          const u8* r = blob + kHdr6 + 4u + nm;
+          ti.minBits = getBytes(r, (int)TB); ti.maxBits = getBytes(r + TB, (int)TB);
+          if (ti.minBits == ti.maxBits || r[2 * TB] != 0) fl = kTmbHeader;    // constant, one sweep
+          ti.dataBegin = kHdr6 + 4u + nm + 2u * TB + 1u;
+          ti.rleLen = nm;
+        }
+      }
+    }
+    ti.flags = fl;
+    s_ti = ti; s_flags = fl; s_nm = nm;
+  }
+  __syncthreads();
+  if (s_flags) { if (threadIdx.x == 0) b.tiles[t] = s_ti; return; }
+  const u32 blobEnd = s_ti.blobSize, nm = s_nm;
+
+  // ---- Fletcher32 over blob[14 .. blobSize)
+  {
+    u64 A, B;
+    blockFletcher(blob + 14, blobEnd - 14u, s_red, A, B);
+    if (fletcherFold(A, B, blobEnd - 14u) != s_ti.checksum)
+    {
+      if (threadIdx.x == 0) { s_ti.flags = kTmbChecksum; b.tiles[t] = s_ti; }
+      return;
+    }
+  }
+
+  // ---- the mask: all ones, or the run-length stream expanded (rleDecode, codec_common.cpp: what it does not fill stays zero)
+  const bool allValid = s_ti.numValid == nPix;
+  for (u32 i = threadIdx.x; i < nBytes + 16u; i += 256u) s_bits[i] = (allValid && i < nBytes) ? (u8)0xFF : (u8)0;
+  __syncthreads();
+  if (!allValid && threadIdx.x == 0)
+  {
+    const u8* src = blob + kHdr6 + 4u;
+    u32 left = nm, at = 0, sp = 0;
+    bool ok = false;
+    for (;;)
+    {
+      if (left < 2u) break;
+      const int cnt = (int)(short)(u16)(src[sp] | (src[sp + 1] << 8));
+      sp += 2; left -= 2;
+      if (cnt == -32768) { ok = true; break; }
+      const u32 n = (u32)(cnt < 0 ? -cnt : cnt), payload = cnt > 0 ? n : 1u;
+      if (left < payload + 2u || at + n > nBytes) break;    // + 2: a count always follows (RLE.cpp:310)
+      if (cnt > 0) for (u32 k = 0; k < n; k++) s_bits[at + k] = src[sp + k];
+      else { const u8 v = src[sp]; for (u32 k = 0; k < n; k++) s_bits[at + k] = v; }
+      at += n; sp += payload; left -= payload;
+    }
+    if (!ok) s_flags = kTmbMaskStream;
+  }
+  __syncthreads();
+  if (s_flags) { if (threadIdx.x == 0) { s_ti.flags = s_flags; b.tiles[t] = s_ti; } return; }
+
+  // ---- valid pixels per block, the bit mask for the block kernel, the caller's valid bytes
+  for (u32 pos = threadIdx.x; pos < nPos; pos += 256u)
+  {
+    const u32 it = pos / (u32)g.nTH, jt = pos - it * (u32)g.nTH;
+    const u32 i1 = min((u32)g.nRows, it * 8u + 8u), j1 = min((u32)g.nCols, jt * 8u + 8u);
+    u32 n = 0;
+    for (u32 i = it * 8u; i < i1; i++)
+      for (u32 j = jt * 8u; j < j1; j++) { const u32 k = i * (u32)g.nCols + j; n += (s_bits[k >> 3] >> (7u - (k & 7u))) & 1u; }
+    s_nv[pos] = (u16)n;
+  }
+  u8* __restrict__ bitsOut = b.bits + (u64)t * g.bitStride;
+  for (u32 i = threadIdx.x; i < nBytes; i += 256u) bitsOut[i] = s_bits[i];
+  u8* __restrict__ vOut = validOut + (u64)t * g.tileElems;
+  for (u32 k = threadIdx.x; k < nPix; k += 256u) vOut[k] = (u8)((s_bits[k >> 3] >> (7u - (k & 7u))) & 1u);
+  __syncthreads();
+
+  // ---- the walk: block k + 1 starts where block k ends; a block's length follows from its header and its valid count
+  if (threadIdx.x == 0)
+  {
+    BandParams p;
+    memset(&p, 0, sizeof(p));
+    p.nRows = g.nRows; p.nCols = g.nCols; p.nDepth = 1; p.mb = 8; p.nTV = g.nTV; p.nTH = g.nTH; p.dt = g.dt; p.version = kCodecVersion;
+    u32* __restrict__ table = b.blockOff + (u64)t * g.posStride;
+    const u32 pattern = 14u;    // codec >= 5: bit 2 of the flag is the difference flag
+    u32 pos = s_ti.dataBegin, fl = 0;
+    for (u32 k = 0; k < nPos; k++)
+    {
+      table[k] = pos;
+      const u32 it = k / (u32)g.nTH, jt = k - it * (u32)g.nTH;
+      const u32 nElem = min(8u, (u32)g.nRows - it * 8u) * min(8u, (u32)g.nCols - jt * 8u);
+      BlkInfo bi;
+      const int rc = parseBlock<(int)TB>(blob, pos, blobEnd, p, (int)s_nv[k], nElem, bi);
+      // (a block of a position without valid pixels is the one "all zero" byte)
+      if (rc != 0 || bi.len == 0 || (((u32)bi.flag >> 2) & pattern) != (jt & pattern) || bi.diff || (s_nv[k] == 0 && bi.mode != 2)) { fl = kTmbBlocks; break; }
+      pos += bi.len;
+    }
+    if (!fl && pos != blobEnd) fl = kTmbBlocks;
+    table[nPos] = pos;
+    s_ti.flags = fl;
+    b.tiles[t] = s_ti;
+  }
+}
+
+// a wave per block: k_decode_tiles (tile_decode.hip) for one value a pixel, with the tile's own blob, mask and header values
+template<class T>
+__global__ void __launch_bounds__(256)
+k_tmbd_blocks(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ offsets, T* __restrict__ outAll, TmbDecodeBuffers b)
+{
+  __shared__ u32 s_lut[4][256];
+  __shared__ __align__(16) u8 s_head[4][64];
+  const u32 t = blockIdx.y;
+  if (b.tiles[t].flags & ~kTmbSibling) return;    // (whatever the parse kernel raised; a sibling wave's kTmbSibling: nothing to gain from leaving)
+  const int w = waveId(), lane = laneId();
+  const int pos = (int)blockIdx.x * 4 + w;
+  if (pos >= g.nTV * g.nTH) return;
+  const u32 blobEnd = b.tiles[t].blobSize;
+  const u32 nPix = (u32)g.tileElems;
+  BandParams p;
+  memset(&p, 0, sizeof(p));
+  p.nRows = g.nRows; p.nCols = g.nCols; p.nDepth = 1; p.mb = 8; p.nTV = g.nTV; p.nTH = g.nTH; p.dt = g.dt; p.version = kCodecVersion;
+  p.allValid = (b.tiles[t].numValid == nPix) ? 1 : 0;
+  p.invScale = 2 * b.tiles[t].maxZErr;
+  const double zMax = b.tiles[t].zMax;
+  const u8* __restrict__ blob = arena + offsets[t];
+  const u8* __restrict__ maskBits = b.bits + (u64)t * g.bitStride;
+  T* __restrict__ out = outAll + (u64)t * g.tileElems;
+  const int it = pos / g.nTH, jt = pos - it * g.nTH;
+  const int i0 = it * 8, j0 = jt * 8;
+  const int tileH = min(8, g.nRows - i0), tileW = min(8, g.nCols - j0);
+  const int nElem = tileH * tileW;
+  const u64 lt = laneMaskLt();
+
+  const bool inb = lane < nElem;
+  const int r = inb ? lane / tileW : 0, c = inb ? lane - r * tileW : 0;
+  const i64 px = (i64)(i0 + r) * g.nCols + (j0 + c);
+  const bool valid = inb && (p.allValid || maskBit(maskBits, px));
+  const u64 bal = __ballot(valid);
+  const int rank = __popcll(bal & lt), nValid = __popcll(bal);
+
+  const u32 off = b.blockOff[(u64)t * g.posStride + pos];
+  s_head[w][lane] = ((u64)off + (u64)lane < (u64)blobEnd) ? blob[(u64)off + lane] : (u8)0;
+  waveSync();
+  BlkInfo bi;
+  const int rc = (off < blobEnd) ? parseBlockWords<(int)sizeof(T)>(reinterpret_cast<const u32*>(s_head[w]), 0u, blobEnd - off, p, nValid, (u32)nElem, bi) : 1;
+  bool failed = rc != 0 || (((u32)bi.flag >> 2) & 14u) != (((u32)j0 >> 3) & 14u) || bi.diff;
+  if (!failed)
+  {
+    double offset = 0;
+    if (bi.mode == 1 || bi.mode == 3) offset = typedFromBits(getBytes(s_head[w] + 1, bi.offBytes), bi.dtUsed);
+    const u64 payloadBit = 8ull * ((u64)off + bi.payload);
+    const int nbIdx = bi.lut ? bitLen(bi.nLut) : 0;
+    u64 idxBit = 0;
+    if (bi.mode == 1 && bi.lut)
+    {
+      s_lut[w][0] = 0;
+      for (u32 i = (u32)lane; i < bi.nLut; i += 64) s_lut[w][i + 1] = unstuffElement(blob, payloadBit, i, bi.nb, bi.nLut, blobEnd, p.version);
+      idxBit = payloadBit + 8ull * (((u64)bi.nLut * bi.nb + 7) >> 3);
+      waveSync();
+    }
+    bool badIdx = false;
+    T val = T(0);
+    if (valid)
+    {
+      if (bi.mode == 2) val = T(0);
+      else if (bi.mode == 0)
+      {
+        const u64 bits = getBytes(blob + off + 1 + (u64)rank * sizeof(T), (int)sizeof(T));
+        memcpy(&val, &bits, sizeof(T));
+      }
+      else if (bi.mode == 3) val = (T)offset;
+      else
+      {
+        u32 q;
+        if (!bi.lut) q = unstuffElement(blob, payloadBit, (u32)rank, bi.nb, bi.cnt, blobEnd, p.version);
+        else
+        {
+          const u32 ix = unstuffElement(blob, idxBit, (u32)rank, nbIdx, bi.cnt, blobEnd, p.version);
+          if (ix > bi.nLut) { badIdx = true; q = 0; } else q = s_lut[w][ix];
+        }
+        const double z = offset + (double)q * p.invScale;
+        val = (T)(z < zMax ? z : zMax);    // std::min(z, zMax)
+      }
+    }
+    if (inb) out[px] = val;
+    failed = __any(badIdx);
+  }
+  if (failed && lane == 0) atomicOr(&b.tiles[t].flags, kTmbSibling);
+}
+
+template<class T>
+static void tmbDecodeT(const TmbGeom& g, const u8* dArena, const u64* dOffsets, const u32* dSizes, void* dTiles, u8* dValidBytes,
+                       const TmbDecodeBuffers& b, hipStream_t st)
+{
+  const int nPos = g.nTV * g.nTH;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_parse<T>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, dSizes, dValidBytes, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_blocks<T>), dim3((nPos + 3) / 4, g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, (T*)dTiles, b);
+}
+
+void launchTmbDecode(const TmbGeom& g, const u8* dArena, const u64* dOffsets, const u32* dSizes, void* dTiles, u8* dValidBytes,
+                     const TmbDecodeBuffers& b, hipStream_t st)
+{
+  switch (g.dt)
+  {
+    case DT_Short:  tmbDecodeT<short>(g, dArena, dOffsets, dSizes, dTiles, dValidBytes, b, st); break;
+    case DT_UShort: tmbDecodeT<unsigned short>(g, dArena, dOffsets, dSizes, dTiles, dValidBytes, b, st); break;
+    case DT_Int:    tmbDecodeT<int>(g, dArena, dOffsets, dSizes, dTiles, dValidBytes, b, st); break;
+    case DT_UInt:   tmbDecodeT<unsigned int>(g, dArena, dOffsets, dSizes, dTiles, dValidBytes, b, st); break;
+    case DT_Float:  tmbDecodeT<float>(g, dArena, dOffsets, dSizes, dTiles, dValidBytes, b, st); break;
+    case DT_Double: tmbDecodeT<double>(g, dArena, dOffsets, dSizes, dTiles, dValidBytes, b, st); break;
+    default: break;
+  }
+}
+
+}    // namespace lerc

@@ -8,7 +8,10 @@ generates inputs directly in HBM).  No sin/cos/exp: a triangle wave stands in fo
   c3_uint16(rows, cols)               16384^2 u16 DEM-like                 (seed 1235)
   c4_rgb_u8(rows, cols)               4096^2 x 3 u8 smooth + sigma~4 noise  (seed 1236)
   C5 tiles are windows of the C2 generator on a 65536^2 virtual raster.
+  island(kind, size, tile)            a mosaic of tiles cut from the C2 / C3 raster, with a validity mask per tile: a disc of valid
+                                      pixels minus salt holes (numpy; tests and tools/time_tiles_masked.py)
 """
+import numpy as np
 import torch
 
 _M32 = 0xFFFFFFFF
@@ -74,3 +77,30 @@ def c4_rgb_u8(rows=4096, cols=4096, device="cpu", seed=1236):
 
 def c5_tile(tile_row, tile_col, tile=256, virt=65536, device="cpu"):
     return c2_float32(tile, tile, tile_row * tile, tile_col * tile, virt_cols=virt, device=device)
+
+
+def island_mask(size=4096):
+    """valid where (i - c)^2 + (j - c)^2 < (0.44 size)^2, c = (size - 1) / 2, minus the pixels with
+    (i * 2654435761 + j * 40503) mod 1009 == 0 (int64) on rows size / 4 ... size / 4 + size / 8 - 1 (4096: rows 1024 ... 1535)"""
+    i = np.arange(size, dtype=np.int64).reshape(-1, 1)
+    j = np.arange(size, dtype=np.int64).reshape(1, -1)
+    half = (size - 1) / 2.0
+    m = ((i - half) ** 2 + (j - half) ** 2) < (0.44 * size) ** 2
+    hole = ((i * 2654435761 + j * 40503) % 1009 == 0) & (i >= size // 4) & (i < size // 4 + size // 8)
+    return (m & ~hole).astype(np.uint8)
+
+
+def cut_tiles(raster, tile):
+    """[rows, cols] -> [n, tile, tile], tiles in row-major order"""
+    r, c = raster.shape
+    return np.ascontiguousarray(raster.reshape(r // tile, tile, c // tile, tile).transpose(0, 2, 1, 3).reshape(-1, tile, tile))
+
+
+def island(kind, size=4096, tile=256):
+    """-> (tiles [n, tile, tile], masks uint8 [n, tile, tile], MaxZError): "float32" is c2_float32 at 0.01, "uint16" c3_uint16 lossless;
+    size 4096 / tile 256: 98 tiles all valid, 76 without a valid pixel, 82 partial"""
+    if kind == "float32":
+        a, e = c2_float32(size, size).numpy(), 0.01
+    else:
+        a, e = c3_uint16(size, size).to(torch.int32).numpy().astype(np.uint16), 0.0
+    return cut_tiles(a, tile), cut_tiles(island_mask(size), tile), e
