@@ -57,7 +57,14 @@ LERC_AMD_API lerc_status lerc_amd_finish(lerc_amd_context* ctx, unsigned int tic
  * Tile t becomes exactly the blob lerc_encode() would make of it, at dArena + offsets[t] (16-byte aligned), sizes[t]
  * bytes long; offsets / sizes / arenaUsed are HOST arrays the caller provides.  BufferTooSmall(3) if the arena is
  * too small (lerc_computeCompressedSize bounds a tile; nRows * nCols * sizeof(T) + 128 per tile always suffices).
- * Decoding takes the same description back.  Blobs that need the general kernels are handled inside, one by one. */
+ * Decoding takes the same description back.  Blobs that need the general kernels are handled inside, one by one.
+ * 8-bit tiles (int8 / uint8, maxZErr < 1, up to 131 072 pixels and 4 096 blocks: 256 x 256, 257 x 257) are a batch as well, one set of
+ * launches and one host wait per sub-batch: statistics, both Huffman code books, the choice between Huffman, delta Huffman and 8 x 8
+ * tiling, table, pixel stream and checksum are made on the device, a workgroup per tile.  Handed back and encoded one by one inside the
+ * call, with the same bytes: a constant tile, one sweep, the 16 x 16 retry of the low-bit-rate rule (lerc_amd_last_note names the reason).
+ * Decoding takes codec 6 blobs of those types in any of the three modes; every other blob (16 x 16 blocks, one sweep, constant, older
+ * codecs, a mask section, damaged ...) is decoded by itself inside the call: a blob that fails leaves its tile zeroed, the other tiles
+ * are decoded all the same, and the call returns the first such status.  Larger 8-bit tiles and maxZErr >= 1 go one by one as before. */
 LERC_AMD_API lerc_status lerc_amd_encode_tiles_device(lerc_amd_context* ctx, const void* dTiles, unsigned int dataType, int nCols,
     int nRows, int nTiles, double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity, unsigned long long* offsets,
     unsigned int* sizes, unsigned long long* arenaUsed);
@@ -80,8 +87,8 @@ LERC_AMD_API lerc_status lerc_amd_decode_tiles_device_slots(lerc_amd_context* ct
  * mask t) makes; a tile without an invalid pixel gets no mask section.  The batch's own launches (one set per sub-batch, one host wait)
  * take float32, float64 and the 16- and 32-bit integer types, tiles of up to 131 072 pixels and 4 096 blocks (256 x 256, 257 x 257), and
  * write header, mask section (run-length coded on the device), ranges, block stream and checksum.  Tiles whose outcome is decided
- * elsewhere -- no valid pixel, a constant tile, NaN, the 16 x 16 retry of the low-bit-rate rule, one sweep -- and 8-bit types, larger tiles, maxZErr == 777 or 0 on float values are encoded inside the call, one by
- * one, with the same result.  Status codes as for the unmasked calls. */
+ * elsewhere -- no valid pixel, a constant tile, NaN, the 16 x 16 retry of the low-bit-rate rule, one sweep -- and 8-bit types WITH a mask pointer, larger tiles, maxZErr == 777 or 0 on float values are encoded inside the call, one by
+ * one, with the same result (8-bit tiles with dValidBytes == NULL are the 8-bit batch described above).  Status codes as for the unmasked calls. */
 LERC_AMD_API lerc_status lerc_amd_encode_tiles_device_masked(lerc_amd_context* ctx, const void* dTiles, unsigned int dataType, int nCols, int nRows,
     int nTiles, const unsigned char* dValidBytes, double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity,
     unsigned long long slotBytes, unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed);

@@ -222,6 +222,12 @@ u32 decodeTilesDevice(Context& ctx, const TilesDecodeRequest& rq);
 u32 encodeTilesDeviceMasked(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed);
 u32 decodeTilesDeviceMasked(Context& ctx, const TilesDecodeRequest& rq);
 
+// 8-bit tiles, every pixel valid, lossless (codec_tiles_bytes.cpp, tile_byte_batch.hip): encodeTilesDevice / decodeTilesDevice hand such requests on
+bool tilesBytesEncodeEligible(const TilesEncodeRequest& rq);
+bool tilesBytesDecodeEligible(const TilesDecodeRequest& rq);
+u32 encodeTilesBytes(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed);
+u32 decodeTilesBytes(Context& ctx, const TilesDecodeRequest& rq);
+
 // header-only queries (host)
 struct BlobInfo
 {

@@ -985,6 +985,7 @@ u32 decodeTilesDevice(Context& ctx, const TilesDecodeRequest& rq)
 {
   if (!rq.dArena || !rq.hOffsets || !rq.hSizes || !rq.dOut || rq.nTiles <= 0 || rq.nRows <= 0 || rq.nCols <= 0 || rq.dt < 0 || rq.dt > DT_Double)
     return kWrongParam;
+  if (tilesBytesDecodeEligible(rq)) return decodeTilesBytes(ctx, rq);
   const int tbytes = dtSize(rq.dt);
   const u64 tileElems = (u64)rq.nRows * (u64)rq.nCols;
   int batchForm = 0;

@@ -1247,6 +1247,7 @@ u32 encodeTilesDevice(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed
   if (!rq.dData || !rq.dArena || !rq.hOffsets || !rq.hSizes || rq.nTiles <= 0 || rq.nRows <= 0 || rq.nCols <= 0 || rq.dt < 0 || rq.dt > DT_Double
     || rq.maxZErr < 0 || (rq.slotBytes & 15u) != 0)
     return kWrongParam;
+  if (tilesBytesEncodeEligible(rq)) return encodeTilesBytes(ctx, rq, arenaUsed);    // (8-bit: the Huffman decision, a tile per workgroup)
   const bool slotted = rq.slotBytes != 0;    // every tile has its place: no arena to fill front to back
   const int tb = dtSize(rq.dt);
   const u64 tileElems = (u64)rq.nRows * (u64)rq.nCols;

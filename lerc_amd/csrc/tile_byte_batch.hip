@@ -1,0 +1,1019 @@
+// tile_byte_batch.hip -- batches of 8-BIT tiles (DT_Char / DT_Byte, every pixel valid, lossless): nTiles rasters of one shape encoded into
+// (decoded from) nTiles independent Lerc2 blobs by ONE set of launches, a tile per workgroup -- no launch, no copy and no host wait per
+// tile, and the Huffman code book of every tile built on the device.
+//
+// Encode (launchTbbEncode):
+//   1. k_tbb_stats     a workgroup per tile: the plain and the delta histogram of Lerc2::ComputeHistoForHuffman (Lerc2.cpp:2311-2380, all
+//                      valid: the predecessor is the left neighbour, the pixel above in column 0, 0 at the origin) in LDS; the range
+//                      follows from the plain one
+//   2. k_tbb_blocks<false>   a wave per 8 x 8 block: the block's size (the general encoder's decisions, tile_encode.hip)
+//   3. k_tbb_decide    a workgroup per tile: the sizes' exclusive scan; two threads build the two code books (Huffman::ComputeCodes,
+//                      Huffman.cpp:35-81, with std::priority_queue's heap discipline restated: tbbBuildBook), their canonical codes, index
+//                      range, serialised table and compressed size; then the mode (Lerc2.cpp:2289-2306, :285-360), the blob's size, the
+//                      slot check.   k_tbb_arena: one workgroup places the blobs in a packed arena (16-byte aligned)
+//   4. k_tbb_blocks<true>    tiling mode tiles: the blocks' bytes
+//   5. k_tbb_write     a workgroup per tile: header, mask section, ranges, "not one sweep", mode byte; Huffman modes: the table and the
+//                      pixel stream -- 4096 pixels a step, 16 a thread: code lengths summed, scanned over the workgroup, the code words
+//                      put together in LDS and stored as whole words -- and its padding words
+//   6. k_tbb_checksum  a workgroup per tile: Fletcher32 over blob[14 ..), stored into the header
+// Tiles whose outcome is decided elsewhere (TbbTile::flags) are left alone; the host encodes them one by one behind the batch.
+//
+// Decode (launchTbbDecode):
+//   1. k_tbbd_parse    a workgroup per tile: header, Fletcher32, mode byte; tiling mode: the walk over the block headers; Huffman modes:
+//                      the code table with parseTable's checks (huffman_host.cpp)
+//   2. k_tbbd_blocks   tiling mode tiles, a wave per block: the general decoder's block (tile_decode.hip)
+//   3. k_tbbd_huff     Huffman mode tiles, a workgroup per tile: the look-up table in LDS, the stream staged in LDS where it fits, 256
+//                      self-synchronising sub-sequences (huffman_kernels.hip: k_huff_sync) whose starts are corrected inside the workgroup
+//                      until every one begins where the one in front ended, the symbols stored, the predictor undone (column 0 by a
+//                      scan over the rows, then every row by a wave)
+// Every loop over a blob is bounded by the blob's size and the pixel count; whatever does not fit raises a flag and the host repeats
+// that tile with the single-blob decoder, which also yields the exact status of a damaged blob.
+// No workgroup waits for another one inside a launch, so the emulator build runs the same path.
+#include <cstdio>
+#include <cstdlib>
+#include "kernels.h"
+#include "wave_utils.h"
+#include "block_plan.h"
+#include "tile_encode_dev.h"
+#include "tile_decode_dev.h"
+#include "huffman_dev.h"
+#include "tile_byte_batch.h"
+#include "tile_batch_dev.h"
+
+namespace lerc {
+
+static const u32 kHdr6 = 90;    // bytes of a codec 6 header (headerBytes(6), codec_common.cpp)
+
+// histogram bin of a raw byte: value + 128 for DT_Char (Lerc2.cpp:2320), the value itself for DT_Byte
+template<class T> __device__ __forceinline__ u32 tbbBin(u32 raw) { return (DtOf<T>::v == DT_Char) ? (raw ^ 0x80u) & 255u : raw & 255u; }
+
+// the predictor's difference at pixel k, as a raw byte
+__device__ __forceinline__ u32 tbbDelta(const u8* __restrict__ px, u32 k, u32 nCols)
+{
+  const u32 i = k / nCols, j = k - i * nCols;
+  const u32 pred = j > 0u ? px[k - 1u] : (i > 0u ? px[k - nCols] : 0u);
+  return ((u32)px[k] - pred) & 255u;
+}
+
+// ================================================================================================
+// encode
+// ================================================================================================
+template<class T>
+__global__ void __launch_bounds__(256) k_tbb_stats(TbbGeom g, const u8* __restrict__ data, TbbEncodeBuffers b)
+{
+  __shared__ u32 s_h[512];
+  __shared__ u32 s_mn[4], s_mx[4];
+  const u32 t = blockIdx.x;
+  const u32 nPix = (u32)g.tileElems, nCols = (u32)g.nCols;
+  const u8* __restrict__ px = data + (u64)t * g.tileElems;
+  s_h[threadIdx.x] = 0; s_h[threadIdx.x + 256u] = 0;
+  __syncthreads();
+  for (u32 k = threadIdx.x; k < nPix; k += 256u)
+  {
+    atomicAdd(&s_h[tbbBin<T>(px[k])], 1u);
+    atomicAdd(&s_h[256u + tbbBin<T>(tbbDelta(px, k, nCols))], 1u);
+  }
+  __syncthreads();
+  u32* __restrict__ out = b.histo + (u64)t * 512u;
+  out[threadIdx.x] = s_h[threadIdx.x]; out[threadIdx.x + 256u] = s_h[threadIdx.x + 256u];
+  const bool used = s_h[threadIdx.x] != 0u;
+  const u32 mn = waveMin(used ? threadIdx.x : 255u), mx = waveMax(used ? threadIdx.x : 0u);
+  if (laneId() == 0) { s_mn[waveId()] = mn; s_mx[waveId()] = mx; }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  TbbTile ti;
+  memset(&ti, 0, sizeof(ti));
+  ti.symMin = min(min(s_mn[0], s_mn[1]), min(s_mn[2], s_mn[3]));
+  ti.symMax = max(max(s_mx[0], s_mx[1]), max(s_mx[2], s_mx[3]));
+  ti.flags = (ti.symMin == ti.symMax) ? kTbbConst : 0u;
+  b.tiles[t] = ti;
+}
+
+// A wave per 8 x 8 block of a tile (blockIdx.y): k_encode_tiles (tile_encode.hip) for one value a pixel, every pixel valid, with the
+// tile's own place in the arena.  WRITE: tiling mode tiles only.
+template<class T, bool WRITE>
+__global__ void __launch_bounds__(256)
+k_tbb_blocks(TbbGeom g, BandParams p, const T* __restrict__ data, u8* __restrict__ arena, TbbEncodeBuffers b)
+{
+  constexpr int NMAX = 64;
+  constexpr int OBW = (1 + NMAX * (int)sizeof(T) + 3) / 4 + 4;
+  __shared__ T s_val[4][NMAX];
+  __shared__ u32 s_obuf[4][WRITE ? OBW : 1];
+  __shared__ u32 s_lut[4][WRITE ? NMAX : 1];
+  const u32 t = blockIdx.y;
+  const TbbTile ti = b.tiles[t];
+  if (ti.flags || (WRITE && ti.mode != (u32)IEM_Tiling)) return;
+  const int nPos = g.nTV * g.nTH;
+  u8* __restrict__ blob = WRITE ? arena + ti.offset : nullptr;
+  const int w = waveId(), lane = laneId();
+  const int pos = (int)blockIdx.x * 4 + w;
+  if (pos >= nPos) return;    // whole wave leaves together
+  const T* __restrict__ px = data + (u64)t * g.tileElems;
+  u32* __restrict__ table = b.blockOff + (u64)t * g.posStride;
+  const int it = pos / g.nTH, jt = pos - it * g.nTH;
+  const int i0 = it * 8, j0 = jt * 8;
+  const int tileH = min(8, g.nRows - i0), tileW = min(8, g.nCols - j0);
+  const int n = tileH * tileW;
+
+  int rank[1];
+  T v[1];
+  u32 q[1];
+  const bool valid = lane < n;
+  const int r = valid ? lane / tileW : 0, c = valid ? lane - r * tileW : 0;
+  const i64 pix = (i64)(i0 + r) * g.nCols + (j0 + c);
+  rank[0] = valid ? lane : -1;
+  T* valBuf = s_val[w];
+  v[0] = T(0);
+  if (valid) { v[0] = px[pix]; valBuf[lane] = v[0]; }
+  waveSync();
+
+  // --- statistics (GetValidDataAndStats)
+  T mn = valBuf[0], mx = valBuf[0];
+  if (valid) { mn = v[0]; mx = v[0]; }
+  mn = waveMinT(mn);
+  mx = waveMaxT(mx);
+  bool s = false;
+  if (rank[0] > 0) s = (v[0] == valBuf[rank[0] - 1]);
+  else if (rank[0] == 0) s = (v[0] == T(0));    // prevVal starts at 0
+  const int same = __popcll(__ballot(s));
+  const bool tryLut = (n > 4) && ((double)mx > (double)mn + 3 * p.maxZErr) && (2 * same > n);
+
+  const double mv = ((double)mx - (double)mn) * p.scale;
+  const bool quantOk = !(mv > (double)p.maxQ || (u32)(mv + 0.5) == 0);
+  u32 qMax = 0;
+  q[0] = 0;
+  if (quantOk)
+  {
+    if (valid) q[0] = quantLossless<T>(v[0], mn);
+    qMax = waveMax(q[0]);
+  }
+  u32 nDistinct = 0;
+  if (tryLut && quantOk)
+  {
+    u32 idxTmp[1];
+    nDistinct = extractDistinct<1>(q, rank, nullptr, idxTmp);
+  }
+  const Plan plan = planBlock<T>(p, n, mn, mx, p.dt, tryLut, mv, qMax, nDistinct);
+  if (!WRITE) { if (lane == 0) table[pos] = (u32)plan.nBytes; return; }
+
+  u32* obuf = s_obuf[w];
+  composeBlock<T, 1>(obuf, s_lut[w], p, plan, n, j0, false, mn, v, q, rank, qMax);
+  const u8* ob8 = reinterpret_cast<const u8*>(obuf);
+  u8* __restrict__ dst = blob + kTbbDataBegin + table[pos];
+  for (int i = lane; i < plan.nBytes; i += 64) dst[i] = ob8[i];
+}
+
+// ---- a code book, built by ONE thread in LDS
+struct TbbBook
+{
+  u32 heapW[256];         // the heap: symbol counts ...
+  u16 heapNode[256];      // ... and the tree node each stands for
+  u16 c0[512], c1[512];   // children of the inner nodes (nodes [0, nLeaves) are leaves, in symbol order)
+  u8 depth[512];
+  u8 leafSym[256];
+  u8 len[256];
+  u32 code[256];
+  u32 start[33];
+  u8 table[kTbbTableCap];
+  u32 tableBytes, nBytes, ok;
+  u64 nBits;
+};
+
+// std::priority_queue<HeapItem> with operator< on minus the count (huffman_host.cpp:22-27): comp(a, b) = a's count > b's count.
+// std::push_heap: the new element sifts up from the end while comp(parent, value).
+__device__ __forceinline__ void tbbHeapPush(TbbBook& k, int& n, u32 w, u32 node)
+{
+  int hole = n++;
+  int parent = (hole - 1) / 2;
+  while (hole > 0 && k.heapW[parent] > w)
+  {
+    k.heapW[hole] = k.heapW[parent]; k.heapNode[hole] = k.heapNode[parent];
+    hole = parent;
+    parent = (hole - 1) / 2;
+  }
+  k.heapW[hole] = w; k.heapNode[hole] = (u16)node;
+}
+
+// std::pop_heap + pop_back: the last element is taken out, the hole at the top sifts down to a leaf along the children that
+// do NOT compare less (std::__adjust_heap), and the element then sifts up from there (std::__push_heap).
+__device__ __forceinline__ void tbbHeapPop(TbbBook& k, int& n, u32& w, u32& node)
+{
+  w = k.heapW[0]; node = k.heapNode[0];
+  n--;
+  if (n < 1) return;
+  const u32 vw = k.heapW[n];
+  const u16 vn = k.heapNode[n];
+  const int len = n;
+  int hole = 0, child = 0;
+  while (child < (len - 1) / 2)
+  {
+    child = 2 * (child + 1);
+    if (k.heapW[child] > k.heapW[child - 1]) child--;    // comp(first[child], first[child - 1])
+    k.heapW[hole] = k.heapW[child]; k.heapNode[hole] = k.heapNode[child];
+    hole = child;
+  }
+  if ((len & 1) == 0 && child == (len - 2) / 2)
+  {
+    child = 2 * (child + 1);
+    k.heapW[hole] = k.heapW[child - 1]; k.heapNode[hole] = k.heapNode[child - 1];
+    hole = child - 1;
+  }
+  int parent = (hole - 1) / 2;
+  while (hole > 0 && k.heapW[parent] > vw)
+  {
+    k.heapW[hole] = k.heapW[parent]; k.heapNode[hole] = k.heapNode[parent];
+    hole = parent;
+    parent = (hole - 1) / 2;
+  }
+  k.heapW[hole] = vw; k.heapNode[hole] = vn;
+}
+
+// buildCodes + codeRange + serialiseTable + compressedBytes of huffman_host.cpp for a 256-bin histogram
+__device__ void tbbBuildBook(const u32* __restrict__ histo, TbbBook& k)
+{
+  k.ok = 0; k.tableBytes = 0; k.nBytes = 0; k.nBits = 0;
+  int n = 0, nNodes = 0;
+  for (int i = 0; i < 256; i++)
+  {
+    k.len[i] = 0; k.code[i] = 0;
+    if (histo[i] > 0u) { k.leafSym[nNodes] = (u8)i; tbbHeapPush(k, n, histo[i], (u32)nNodes); nNodes++; }
+  }
+  const int nLeaves = nNodes;
+  if (nLeaves < 2) return;
+  while (n > 1)
+  {
+    u32 wa, na, wb, nb;
+    tbbHeapPop(k, n, wa, na);
+    tbbHeapPop(k, n, wb, nb);
+    k.c0[nNodes] = (u16)na; k.c1[nNodes] = (u16)nb;
+    tbbHeapPush(k, n, wa + wb, (u32)nNodes);
+    nNodes++;
+  }
+  // depths: a node's children were made before it
+  int maxLen = 0;
+  k.depth[nNodes - 1] = 0;
+  for (int m = nNodes - 1; m >= nLeaves; m--)
+  {
+    const int d = k.depth[m] + 1;
+    if (d > 32) return;    // a code longer than 32 bits: no code book (Huffman.h:84-99)
+    k.depth[k.c0[m]] = (u8)d; k.depth[k.c1[m]] = (u8)d;
+  }
+  for (int m = 0; m < nLeaves; m++) { k.len[k.leafSym[m]] = k.depth[m]; maxLen = max(maxLen, (int)k.depth[m]); }
+  // canonical codes: longest first, ties by ascending symbol (Huffman.cpp:541-572)
+  for (int l = 0; l <= 32; l++) k.start[l] = 0;
+  for (int i = 0; i < 256; i++) if (k.len[i]) k.start[k.len[i]]++;
+  {
+    u32 code = 0;
+    int cur = maxLen;
+    for (int l = maxLen; l >= 1; l--)
+    {
+      const u32 cnt = k.start[l];
+      if (!cnt) continue;
+      code >>= (cur - l);
+      cur = l;
+      k.start[l] = code;
+      code += cnt;
+    }
+  }
+  for (int i = 0; i < 256; i++) if (k.len[i]) k.code[i] = k.start[k.len[i]]++;
+
+  // the smallest (possibly wrapping) index range that covers the used symbols (Huffman.cpp:383-438)
+  int i0 = 0, i1 = 0;
+  {
+    int i = 0;
+    while (i < 256 && k.len[i] == 0) i++;
+    i0 = i;
+    i = 255;
+    while (i >= 0 && k.len[i] == 0) i--;
+    i1 = i + 1;
+    int gapAt = 0, gapLen = 0;
+    for (int j = 0; j < 256;)
+    {
+      while (j < 256 && k.len[j] > 0) j++;
+      const int k0 = j;
+      while (j < 256 && k.len[j] == 0) j++;
+      if (j - k0 > gapLen) { gapAt = k0; gapLen = j - k0; }
+    }
+    if (256 - gapLen < i1 - i0) { i0 = gapAt + gapLen; i1 = gapAt + 256; }
+    if (i1 <= i0) return;
+  }
+  // the table (Huffman.cpp:126-166): version, size, range; the lengths as a BitStuffer2 "simple" stream; the codes MSB first in words
+  u8* out = k.table;
+  const int hdr[4] = { 4, 256, i0, i1 };
+  for (int i = 0; i < 4; i++) putBytes(out + 4 * i, (u64)(u32)hdr[i], 4);
+  const u32 cnt = (u32)(i1 - i0);
+  const int nb = bitLen((u32)maxLen), cb = countFieldBytes(cnt);
+  u32 at = 16;
+  out[at++] = (u8)(nb | (((cb == 4) ? 0 : 3 - cb) << 6));
+  for (int i = 0; i < cb; i++) out[at++] = (u8)(cnt >> (8 * i));
+  const u32 lenBytes = (cnt * (u32)nb + 7u) >> 3;
+  for (u32 i = 0; i < lenBytes; i++) out[at + i] = 0;
+  for (u32 i = 0; i < cnt; i++)
+  {
+    const int sym = i0 + (int)i - ((i0 + (int)i) < 256 ? 0 : 256);
+    const u32 bit = i * (u32)nb;
+    const u32 v = (u32)k.len[sym] << (bit & 7u);    // (six bits at most, shifted by seven at most)
+    out[at + (bit >> 3)] |= (u8)v;
+    if (v >> 8) out[at + (bit >> 3) + 1u] |= (u8)(v >> 8);
+  }
+  at += lenBytes;
+  u32 cur = 0;
+  int used = 0;
+  for (int i = i0; i < i1; i++)
+  {
+    const int sym = i - (i < 256 ? 0 : 256);
+    const int len = k.len[sym];
+    if (!len) continue;
+    const u32 v = k.code[sym];
+    if (32 - used >= len)
+    {
+      cur |= (len == 32) ? v : (v << (32 - used - len));
+      used += len;
+      if (used == 32) { putBytes(out + at, (u64)cur, 4); at += 4; cur = 0; used = 0; }
+    }
+    else
+    {
+      const int rest = len - (32 - used);
+      cur |= v >> rest;
+      putBytes(out + at, (u64)cur, 4); at += 4;
+      cur = v << (32 - rest);
+      used = rest;
+    }
+  }
+  if (used > 0) { putBytes(out + at, (u64)cur, 4); at += 4; }
+  k.tableBytes = at;
+  // Huffman::ComputeCompressedSize (Huffman.cpp:85-111)
+  u64 bits = 0;
+  for (int i = 0; i < 256; i++) bits += (u64)histo[i] * k.len[i];
+  if (bits == 0 || bits > (u64)INT_MAX) return;    // the reference sums the bits in an int
+  k.nBits = bits;
+  k.nBytes = at + 4u * (u32)(((((bits + 7u) >> 3) + 3u) >> 2) + 1u);
+  k.ok = 1;
+}
+
+__global__ void __launch_bounds__(256) k_tbb_decide(TbbGeom g, u64 slotBytes, u64 firstTile, TbbEncodeBuffers b)
+{
+  __shared__ u32 s_scan[257];
+  __shared__ u32 s_h[512];
+  __shared__ TbbBook s_book[2];
+  __shared__ u32 s_pick;
+  const u32 t = blockIdx.x;
+  if (b.tiles[t].flags) return;
+  const u32 nPos = (u32)(g.nTV * g.nTH);
+  const u32* __restrict__ histo = b.histo + (u64)t * 512u;
+  s_h[threadIdx.x] = histo[threadIdx.x]; s_h[threadIdx.x + 256u] = histo[threadIdx.x + 256u];
+  const u32 nBytesTiling = blockScanInPlace(b.blockOff + (u64)t * g.posStride, nPos, s_scan);    // (its barriers cover s_h)
+  if (threadIdx.x == 0) tbbBuildBook(s_h, s_book[0]);
+  if (threadIdx.x == 64) tbbBuildBook(s_h + 256, s_book[1]);
+  __syncthreads();
+  if (threadIdx.x == 0)
+  {
+    TbbTile& ti = b.tiles[t];
+    const u64 nPix = g.tileElems;
+    // Lerc2.cpp:2289-2306: the better of the two books; the plain one where they tie
+    const u32 n0 = s_book[0].ok ? s_book[0].nBytes : 0u, n1 = s_book[1].ok ? s_book[1].nBytes : 0u;
+    u32 pick = 2u, nBytesHuffman = 0;
+    if (n0 > 0u && n1 > 0u) { pick = (n0 <= n1) ? 0u : 1u; nBytesHuffman = min(n0, n1); }
+    else if (n0 > 0u || n1 > 0u) { pick = (n0 > n1) ? 0u : 1u; nBytesHuffman = max(n0, n1); }
+    // Lerc2.cpp:285-304
+    u32 mode = (u32)IEM_Tiling, nBytesData = nBytesTiling;
+    if (pick < 2u && nBytesHuffman < nBytesTiling) { mode = pick == 0u ? (u32)IEM_Huffman : (u32)IEM_DeltaHuffman; nBytesData = nBytesHuffman; }
+    else pick = 2u;
+    u32 fl = 0;
+    // 16 x 16 blocks at low bit rates (Lerc2.cpp:333-357)
+    if ((double)((u64)nBytesTiling * 8u) < (double)nPix * 1.5 && (u64)nBytesTiling < 4u * nPix
+      && (nBytesHuffman == 0u || (u64)nBytesTiling < 2ull * nBytesHuffman) && (g.nRows > 8 || g.nCols > 8))
+      fl |= kTbbRetry16;
+    nBytesData += 1u;    // the mode byte
+    if (nPix <= (u64)nBytesData) fl |= kTbbOneSweep;
+    ti.mode = mode;
+    ti.nBytesTiling = nBytesTiling;
+    ti.nBytesHuffman = nBytesHuffman;
+    ti.tableBytes = pick < 2u ? s_book[pick].tableBytes : 0u;
+    ti.nBits = pick < 2u ? s_book[pick].nBits : 0ull;
+    ti.blobSize = kTbbDataBegin - 1u + nBytesData;
+    if (slotBytes)
+    {
+      ti.offset = (firstTile + t) * slotBytes;
+      if ((u64)ti.blobSize > slotBytes) fl |= kTbbCapacity;
+    }
+    ti.flags = fl;
+    s_pick = fl ? 2u : pick;
+  }
+  __syncthreads();
+  const u32 pick = s_pick;
+  if (pick >= 2u) return;
+  const TbbBook& k = s_book[pick];
+  b.codes[(u64)t * 256u + threadIdx.x] = ((u64)k.len[threadIdx.x] << 32) | k.code[threadIdx.x];
+  u8* __restrict__ tab = b.table + (u64)t * kTbbTableCap;
+  for (u32 i = threadIdx.x; i < k.tableBytes; i += 256u) tab[i] = k.table[i];
+}
+
+// packed arena: the batch's blobs back to back at 16-byte aligned offsets from arenaBase on, in tile order
+__global__ void __launch_bounds__(256) k_tbb_arena(u32 nTiles, u64 arenaBase, u64 arenaCapacity, TbbEncodeBuffers b)
+{
+  __shared__ u64 s_part[257];
+  const u32 per = (nTiles + 255u) / 256u, from = min(nTiles, threadIdx.x * per), to = min(nTiles, from + per);
+  u64 sum = 0;
+  for (u32 i = from; i < to; i++) if (!b.tiles[i].flags) sum += ((u64)b.tiles[i].blobSize + 15ull) & ~15ull;
+  s_part[threadIdx.x] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) { u64 run = 0; for (u32 i = 0; i < 256u; i++) { const u64 y = s_part[i]; s_part[i] = run; run += y; } s_part[256] = run; }
+  __syncthreads();
+  u64 run = arenaBase + s_part[threadIdx.x];
+  for (u32 i = from; i < to; i++)
+  {
+    TbbTile& ti = b.tiles[i];
+    if (ti.flags) continue;
+    ti.offset = run;
+    if (run + ti.blobSize > arenaCapacity) ti.flags |= kTbbArenaFull;
+    run += ((u64)ti.blobSize + 15ull) & ~15ull;
+  }
+}
+
+static const u32 kTbbRun = 16;                      // pixels a thread packs in one step
+static const u32 kTbbStep = 256u * kTbbRun;         // ... and the workgroup
+static const u32 kTbbStageWords = kTbbStep + 4u;    // 32 bits a code word at most, the word carried over, one to spill into
+
+template<class T>
+__global__ void __launch_bounds__(256) k_tbb_write(TbbGeom g, const u8* __restrict__ data, u8* __restrict__ arena, TbbEncodeBuffers b)
+{
+  __shared__ u8 s_hdr[kTbbDataBegin + 2];
+  __shared__ u64 s_code[256];
+  __shared__ u32 s_stage[kTbbStageWords];
+  __shared__ u32 s_wave[4];
+  const u32 t = blockIdx.x;
+  const TbbTile ti = b.tiles[t];
+  if (ti.flags) return;
+  const u32 nPix = (u32)g.tileElems, nCols = (u32)g.nCols;
+  u8* __restrict__ blob = arena + ti.offset;
+  // ---- header (Lerc2.cpp:724-786; checksum patched by k_tbb_checksum), an empty mask section, ranges, "not one sweep", mode
+  if (threadIdx.x == 0)
+  {
+    u8* h = s_hdr;
+    const char magic[6] = { 'L', 'e', 'r', 'c', '2', ' ' };
+    for (int i = 0; i < 6; i++) h[i] = (u8)magic[i];
+    const int ints[10] = { kCodecVersion, 0, g.nRows, g.nCols, 1, (int)nPix, 8, (int)ti.blobSize, g.dt, 0 };
+    for (int i = 0; i < 10; i++) putBytes(h + 6 + 4 * i, (u64)(u32)ints[i], 4);
+    putBytes(h + 46, 0ull, 4);    // passNoData, isInt, two reserved bytes
+    const int off = (g.dt == DT_Char) ? 128 : 0;
+    const double dbl[5] = { 0.5, (double)((int)ti.symMin - off), (double)((int)ti.symMax - off), 0.0, 0.0 };
+    for (int i = 0; i < 5; i++) { u64 bits; memcpy(&bits, &dbl[i], 8); putBytes(h + 50 + 8 * i, bits, 8); }
+    putBytes(h + kHdr6, 0ull, 4);
+    h[kHdr6 + 4u] = (u8)((int)ti.symMin - off);
+    h[kHdr6 + 5u] = (u8)((int)ti.symMax - off);
+    h[kHdr6 + 6u] = 0;
+    h[kHdr6 + 7u] = (u8)ti.mode;
+  }
+  s_code[threadIdx.x] = b.codes[(u64)t * 256u + threadIdx.x];
+  __syncthreads();
+  for (u32 i = threadIdx.x; i < kTbbDataBegin; i += 256u) blob[i] = s_hdr[i];
+  if (ti.mode == (u32)IEM_Tiling) return;
+  const u8* __restrict__ tab = b.table + (u64)t * kTbbTableCap;
+  for (u32 i = threadIdx.x; i < ti.tableBytes; i += 256u) blob[kTbbDataBegin + i] = tab[i];
+
+  // ---- the pixel stream: code words MSB first in little-endian 32-bit words (Huffman::PushValue)
+  const u8* __restrict__ px = data + (u64)t * g.tileElems;
+  u8* __restrict__ stream = blob + kTbbDataBegin + ti.tableBytes;
+  const bool aligned = ((uintptr_t)stream & 3u) == 0u;
+  const bool delta = ti.mode == (u32)IEM_DeltaHuffman;
+  u32 carryBits = 0, carryWord = 0, wordBase = 0;
+  for (u32 k0 = 0; k0 < nPix; k0 += kTbbStep)
+  {
+    for (u32 i = threadIdx.x; i < kTbbStageWords; i += 256u) s_stage[i] = (i == 0u) ? carryWord : 0u;
+    u32 len[kTbbRun], code[kTbbRun];
+    u32 sum = 0;
+    const u32 first = k0 + threadIdx.x * kTbbRun;
+#pragma unroll
+    for (u32 j = 0; j < kTbbRun; j++)
+    {
+      const u32 k = first + j;
+      u64 c = 0;
+      if (k < nPix) c = s_code[tbbBin<T>(delta ? tbbDelta(px, k, nCols) : (u32)px[k])];
+      len[j] = (u32)(c >> 32); code[j] = (u32)c;
+      sum += len[j];
+    }
+    const u32 incl = waveInclusiveScan(sum);
+    if (laneId() == 63) s_wave[waveId()] = incl;
+    __syncthreads();    // (s_stage cleared, the waves' sums there)
+    u32 before = 0, total = 0;
+    for (int w = 0; w < 4; w++) { if (w < waveId()) before += s_wave[w]; total += s_wave[w]; }
+    u32 p = carryBits + before + incl - sum;
+    u32 w = p >> 5, fill = p & 31u, cur = 0;
+#pragma unroll
+    for (u32 j = 0; j < kTbbRun; j++)
+    {
+      if (!len[j]) continue;
+      const u64 x = (((u64)code[j]) << (64u - len[j])) >> fill;
+      cur |= (u32)(x >> 32);
+      fill += len[j];
+      if (fill >= 32u) { atomicOr(&s_stage[w], cur); w++; cur = (u32)x; fill -= 32u; }
+    }
+    if (cur) atomicOr(&s_stage[w], cur);
+    __syncthreads();
+    const u32 segBits = carryBits + total, nFull = segBits >> 5;
+    for (u32 i = threadIdx.x; i < nFull; i += 256u)
+    {
+      const u32 v = s_stage[i];
+      u8* dst = stream + 4ull * (wordBase + i);
+      if (aligned) *reinterpret_cast<u32*>(dst) = v;
+      else { dst[0] = (u8)v; dst[1] = (u8)(v >> 8); dst[2] = (u8)(v >> 16); dst[3] = (u8)(v >> 24); }
+    }
+    carryBits = segBits & 31u;
+    carryWord = carryBits ? s_stage[nFull] : 0u;
+    wordBase += nFull;
+    __syncthreads();    // (everybody has read s_stage and s_wave)
+  }
+  // the last, partly filled word and one more (Lerc2.cpp:2464: the decoder's look-up may read ahead)
+  if (threadIdx.x < 8u)
+  {
+    const u32 nTail = carryBits ? 2u : 1u;
+    const u32 wordIdx = threadIdx.x >> 2, byteIdx = threadIdx.x & 3u;
+    if (wordIdx < nTail)
+    {
+      const u32 v = (carryBits && wordIdx == 0u) ? carryWord : 0u;
+      stream[4ull * (wordBase + wordIdx) + byteIdx] = (u8)(v >> (8u * byteIdx));
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) k_tbb_checksum(u8* __restrict__ arena, TbbEncodeBuffers b)
+{
+  __shared__ u64 s_red[4];
+  const TbbTile ti = b.tiles[blockIdx.x];
+  if (ti.flags) return;
+  u8* __restrict__ blob = arena + ti.offset;
+  u64 A, B;
+  blockFletcher(blob + 14, ti.blobSize - 14u, s_red, A, B);
+  if (threadIdx.x == 0) putBytes(blob + 10, (u64)fletcherFold(A, B, ti.blobSize - 14u), 4);
+}
+
+template<class T>
+static void tbbEncodeT(const TbbGeom& g, const BandParams& bp, const void* dTiles, u8* dArena, u64 arenaBase, u64 arenaCapacity, u64 slotBytes,
+                       u64 firstTile, const TbbEncodeBuffers& b, hipStream_t st)
+{
+  const int nPos = g.nTV * g.nTH;
+  const dim3 perTile(g.nTiles), blk(256), perBlock((nPos + 3) / 4, g.nTiles);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_stats<T>), perTile, blk, 0, st, g, (const u8*)dTiles, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_blocks<T, false>), perBlock, blk, 0, st, g, bp, (const T*)dTiles, (u8*)nullptr, b);
+  hipLaunchKernelGGL(k_tbb_decide, perTile, blk, 0, st, g, slotBytes, firstTile, b);
+  if (!slotBytes) hipLaunchKernelGGL(k_tbb_arena, dim3(1), blk, 0, st, g.nTiles, arenaBase, arenaCapacity, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_blocks<T, true>), perBlock, blk, 0, st, g, bp, (const T*)dTiles, dArena, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_write<T>), perTile, blk, 0, st, g, (const u8*)dTiles, dArena, b);
+  hipLaunchKernelGGL(k_tbb_checksum, perTile, blk, 0, st, dArena, b);
+}
+
+void launchTbbEncode(const TbbGeom& g, const BandParams& bp, const void* dTiles, u8* dArena, u64 arenaBase, u64 arenaCapacity, u64 slotBytes,
+                     u64 firstTile, const TbbEncodeBuffers& b, hipStream_t st)
+{
+  if (g.dt == DT_Char) tbbEncodeT<signed char>(g, bp, dTiles, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st);
+  else if (g.dt == DT_Byte) tbbEncodeT<unsigned char>(g, bp, dTiles, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st);
+}
+
+// ================================================================================================
+// decode
+// ================================================================================================
+// parseTable (huffman_host.cpp) for codec 6, by one thread; the batch takes tables of 256 symbols whose range does not lap itself and
+// whose lengths are stored in at most 6 bits -- every table an encoder writes -- and leaves any other to the single-blob decoder
+__device__ bool tbbParseTable(const u8* __restrict__ p, u32 n, u8* __restrict__ lens, u32* __restrict__ codes, u32& used)
+{
+  if (n < 16u) return false;
+  int hdr[4];
+  for (int i = 0; i < 4; i++) hdr[i] = (int)(u32)getBytes(p + 4 * i, 4);
+  if (hdr[0] < 2) return false;
+  const int size = hdr[1], i0 = hdr[2], i1 = hdr[3];
+  if (size != 256 || i0 >= i1 || i0 < 0 || i0 >= size || i1 - 1 >= 2 * size || i1 - i0 > size) return false;
+  u32 at = 16;
+  if (n < at + 1u) return false;
+  const u8 b0 = p[at++];
+  const int code = b0 >> 6, cb = (code == 0) ? 4 : 3 - code;
+  const int nb = b0 & 31;
+  if (cb == 0 || (b0 & 32) || n < at + (u32)cb || nb > 6) return false;
+  u32 cnt = 0;
+  for (int i = 0; i < cb; i++) cnt |= (u32)p[at + i] << (8 * i);
+  at += (u32)cb;
+  if (cnt != (u32)(i1 - i0)) return false;
+  for (int i = 0; i < 256; i++) { lens[i] = 0; codes[i] = 0; }
+  if (nb > 0)
+  {
+    const u32 nBytes = (cnt * (u32)nb + 7u) >> 3;
+    if (n < at + nBytes) return false;
+    for (u32 i = 0; i < cnt; i++)
+    {
+      const u32 bit = i * (u32)nb, q = bit >> 3;
+      const u32 v = (u32)p[at + q] | (q + 1u < nBytes ? (u32)p[at + q + 1u] << 8 : 0u);
+      const int sym = i0 + (int)i - ((i0 + (int)i) < 256 ? 0 : 256);
+      lens[sym] = (u8)((v >> (bit & 7u)) & ((1u << nb) - 1u));
+    }
+    at += nBytes;
+  }
+  // the codes themselves, MSB first in little-endian words (Huffman.cpp:471-537)
+  u32 word = 0;
+  int bitPos = 0;
+  for (int i = i0; i < i1; i++)
+  {
+    const int sym = i - (i < 256 ? 0 : 256);
+    const int len = lens[sym];
+    if (len == 0) continue;
+    if (len > 32) return false;
+    if (n < at + 4u * (word + 1u)) return false;
+    const u32 w0 = (u32)getBytes(p + at + 4u * word, 4);
+    u32 c = (w0 << bitPos) >> (32 - len);
+    if (32 - bitPos >= len) { bitPos += len; if (bitPos == 32) { bitPos = 0; word++; } }
+    else
+    {
+      bitPos += len - 32;
+      word++;
+      if (n < at + 4u * (word + 1u)) return false;
+      const u32 w1 = (u32)getBytes(p + at + 4u * word, 4);
+      c |= w1 >> (32 - bitPos);
+    }
+    codes[sym] = c;
+  }
+  used = at + 4u * (word + (bitPos > 0 ? 1u : 0u));
+  return used <= n;
+}
+
+template<class T>
+__global__ void __launch_bounds__(256)
+k_tbbd_parse(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ offsets, const u32* __restrict__ sizes, TbbDecodeBuffers b)
+{
+  __shared__ u64 s_red[4];
+  __shared__ TbbTile s_ti;
+  const u32 t = blockIdx.x;
+  const u8* __restrict__ blob = arena + offsets[t];
+  const u32 sizeGiven = sizes[t];
+  const u32 nPix = (u32)g.tileElems;
+  const u32 nPos = (u32)(g.nTV * g.nTH);
+
+  if (threadIdx.x == 0)
+  {
+    TbbTile ti;
+    memset(&ti, 0, sizeof(ti));
+    u32 fl = 0;
+    if (sizeGiven < kTbbDataBegin + 1u) fl = kTbbHeader;
+    else
+    {
+      const char magic[6] = { 'L', 'e', 'r', 'c', '2', ' ' };
+      for (int i = 0; i < 6; i++) if (blob[i] != (u8)magic[i]) fl = kTbbHeader;
+      int ints[10];
+      for (int i = 0; i < 10; i++) ints[i] = (int)(u32)getBytes(blob + 6 + 4 * i, 4);
+      double dbl[3];
+      for (int i = 0; i < 3; i++) { const u64 bits = getBytes(blob + 50 + 8 * i, 8); memcpy(&dbl[i], &bits, 8); }
+      const u32 flagBytes = (u32)getBytes(blob + 46, 4);    // passNoData, isInt, reserved
+      ti.checksum = (u32)ints[1];
+      ti.blobSize = (u32)ints[7];
+      if (ints[0] != kCodecVersion || ints[2] != g.nRows || ints[3] != g.nCols || ints[4] != 1 || (u32)ints[5] != nPix || ints[6] != 8
+        || ints[7] < (int)(kTbbDataBegin + 1u) || (u32)ints[7] > sizeGiven || ints[8] != g.dt || ints[9] != 0 || (flagBytes & 0xFFu) != 0u)
+        fl = kTbbHeader;
+      // (the mode byte is there for an error bound of 0.5 only: Lerc2::HeaderInfo::TryHuffmanInt)
+      if (!(dbl[0] == 0.5) || !(dbl[1] < dbl[2])) fl = kTbbHeader;
+      if (!fl)
+      {
+        const u8* r = blob + kHdr6;
+        if (getBytes(r, 4) != 0ull || r[4] == r[5] || r[6] != 0 || r[7] > 2) fl = kTbbHeader;    // a mask, constant, one sweep, a later mode
+        ti.mode = r[7];
+      }
+    }
+    ti.flags = fl;
+    s_ti = ti;
+  }
+  __syncthreads();
+  if (s_ti.flags) { if (threadIdx.x == 0) b.tiles[t] = s_ti; return; }
+  const u32 blobEnd = s_ti.blobSize;
+
+  // ---- Fletcher32 over blob[14 .. blobSize)
+  {
+    u64 A, B;
+    blockFletcher(blob + 14, blobEnd - 14u, s_red, A, B);
+    if (fletcherFold(A, B, blobEnd - 14u) != s_ti.checksum)
+    {
+      if (threadIdx.x == 0) { s_ti.flags = kTbbChecksum; b.tiles[t] = s_ti; }
+      return;
+    }
+  }
+  if (threadIdx.x != 0) return;
+
+  if (s_ti.mode == (u32)IEM_Tiling)
+  {
+    // ---- the walk: block k + 1 starts where block k ends
+    BandParams p;
+    memset(&p, 0, sizeof(p));
+    p.nRows = g.nRows; p.nCols = g.nCols; p.nDepth = 1; p.mb = 8; p.nTV = g.nTV; p.nTH = g.nTH; p.dt = g.dt; p.version = kCodecVersion;
+    u32* __restrict__ table = b.blockOff + (u64)t * g.posStride;
+    const u32 pattern = 14u;    // codec >= 5: bit 2 of the flag is the difference flag
+    u32 pos = kTbbDataBegin, fl = 0;
+    for (u32 k = 0; k < nPos; k++)
+    {
+      table[k] = pos;
+      const u32 it = k / (u32)g.nTH, jt = k - it * (u32)g.nTH;
+      const u32 nElem = min(8u, (u32)g.nRows - it * 8u) * min(8u, (u32)g.nCols - jt * 8u);
+      BlkInfo bi;
+      const int rc = parseBlock<1>(blob, pos, blobEnd, p, (int)nElem, nElem, bi);
+      if (rc != 0 || bi.len == 0 || (((u32)bi.flag >> 2) & pattern) != (jt & pattern) || bi.diff) { fl = kTbbBlocks; break; }
+      pos += bi.len;
+    }
+    if (!fl && pos != blobEnd) fl = kTbbBlocks;
+    table[nPos] = pos;
+    s_ti.flags = fl;
+  }
+  else
+  {
+    u32 used = 0;
+    if (!tbbParseTable(blob + kTbbDataBegin, blobEnd - kTbbDataBegin, b.lens + (u64)t * 256u, b.codes + (u64)t * 256u, used)) s_ti.flags = kTbbTable;
+    else if (kTbbDataBegin + used + 4u > blobEnd) s_ti.flags = kTbbStream;
+    s_ti.tableBytes = kTbbDataBegin + used;
+  }
+  b.tiles[t] = s_ti;
+}
+
+// a wave per block: k_decode_tiles (tile_decode.hip) for one value a pixel, every pixel valid, with the tile's own blob
+template<class T>
+__global__ void __launch_bounds__(256)
+k_tbbd_blocks(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ offsets, T* __restrict__ outAll, TbbDecodeBuffers b)
+{
+  __shared__ u32 s_lut[4][256];
+  __shared__ __align__(16) u8 s_head[4][64];
+  const u32 t = blockIdx.y;
+  if ((b.tiles[t].flags & ~kTbbSibling) || b.tiles[t].mode != (u32)IEM_Tiling) return;
+  const int w = waveId(), lane = laneId();
+  const int pos = (int)blockIdx.x * 4 + w;
+  if (pos >= g.nTV * g.nTH) return;
+  const u32 blobEnd = b.tiles[t].blobSize;
+  BandParams p;
+  memset(&p, 0, sizeof(p));
+  p.nRows = g.nRows; p.nCols = g.nCols; p.nDepth = 1; p.mb = 8; p.nTV = g.nTV; p.nTH = g.nTH; p.dt = g.dt; p.version = kCodecVersion;
+  p.allValid = 1;
+  p.invScale = 1.0;    // 2 * maxZErr
+  const u8* __restrict__ blob = arena + offsets[t];
+  double zMax;
+  { const u64 bits = getBytes(blob + 66, 8); memcpy(&zMax, &bits, 8); }
+  T* __restrict__ out = outAll + (u64)t * g.tileElems;
+  const int it = pos / g.nTH, jt = pos - it * g.nTH;
+  const int i0 = it * 8, j0 = jt * 8;
+  const int tileH = min(8, g.nRows - i0), tileW = min(8, g.nCols - j0);
+  const int nElem = tileH * tileW;
+  const bool valid = lane < nElem;
+  const int r = valid ? lane / tileW : 0, c = valid ? lane - r * tileW : 0;
+  const i64 px = (i64)(i0 + r) * g.nCols + (j0 + c);
+  const int rank = lane;
+
+  const u32 off = b.blockOff[(u64)t * g.posStride + pos];
+  s_head[w][lane] = ((u64)off + (u64)lane < (u64)blobEnd) ? blob[(u64)off + lane] : (u8)0;
+  waveSync();
+  BlkInfo bi;
+  const int rc = (off < blobEnd) ? parseBlockWords<1>(reinterpret_cast<const u32*>(s_head[w]), 0u, blobEnd - off, p, nElem, (u32)nElem, bi) : 1;
+  bool failed = rc != 0 || (((u32)bi.flag >> 2) & 14u) != (((u32)j0 >> 3) & 14u) || bi.diff;
+  if (!failed)
+  {
+    double offset = 0;
+    if (bi.mode == 1 || bi.mode == 3) offset = typedFromBits(getBytes(s_head[w] + 1, bi.offBytes), bi.dtUsed);
+    const u64 payloadBit = 8ull * ((u64)off + bi.payload);
+    const int nbIdx = bi.lut ? bitLen(bi.nLut) : 0;
+    u64 idxBit = 0;
+    if (bi.mode == 1 && bi.lut)
+    {
+      s_lut[w][0] = 0;
+      for (u32 i = (u32)lane; i < bi.nLut; i += 64) s_lut[w][i + 1] = unstuffElement(blob, payloadBit, i, bi.nb, bi.nLut, blobEnd, p.version);
+      idxBit = payloadBit + 8ull * (((u64)bi.nLut * bi.nb + 7) >> 3);
+      waveSync();
+    }
+    bool badIdx = false;
+    T val = T(0);
+    if (valid)
+    {
+      if (bi.mode == 2) val = T(0);
+      else if (bi.mode == 0) { const u64 bits = getBytes(blob + off + 1 + (u64)rank, 1); memcpy(&val, &bits, 1); }
+      else if (bi.mode == 3) val = (T)offset;
+      else
+      {
+        u32 q;
+        if (!bi.lut) q = unstuffElement(blob, payloadBit, (u32)rank, bi.nb, bi.cnt, blobEnd, p.version);
+        else
+        {
+          const u32 ix = unstuffElement(blob, idxBit, (u32)rank, nbIdx, bi.cnt, blobEnd, p.version);
+          if (ix > bi.nLut) { badIdx = true; q = 0; } else q = s_lut[w][ix];
+        }
+        const double z = offset + (double)q * p.invScale;
+        val = (T)(z < zMax ? z : zMax);    // std::min(z, zMax)
+      }
+    }
+    if (valid) out[px] = val;
+    failed = __any(badIdx);
+  }
+  if (failed && lane == 0) atomicOr(&b.tiles[t].flags, kTbbSibling);
+}
+
+static const u32 kTbbdStageWords = 10240;    // 40 KB of stream in LDS: 4.9 bits a pixel at 256 x 256; a longer stream is read where it lies
+
+struct TbbdBits
+{
+  const u32* s_str;       // the staged words, or nullptr
+  const u8* bytes;        // the stream where it lies
+  u32 nWords;
+  __device__ __forceinline__ u32 word(u32 w) const
+  {
+    if (w >= nWords) return 0u;    // (words beyond the stream read as zero: peek32, huffman_kernels.hip)
+    if (s_str) return s_str[w];
+    const u8* q = bytes + 4ull * w;
+    return (u32)q[0] | ((u32)q[1] << 8) | ((u32)q[2] << 16) | ((u32)q[3] << 24);
+  }
+  __device__ __forceinline__ u32 top(u32 pos) const
+  {
+    const u32 w = pos >> 5;
+    const u64 x = ((u64)word(w) << 32) | word(w + 1u);
+    return (u32)((x << (pos & 31u)) >> 32);
+  }
+};
+
+struct TbbdTable
+{
+  u32 lut[1 << kHuffLutBits];    // (symbol << 8) | length for codes of <= 12 bits, 0: none
+  u32 longCode[256];
+  u16 longLenSym[256];           // sorted by length, then symbol
+  u32 nLong;
+};
+
+// returns the code length (0 = no code matches): decodeOne (huffman_kernels.hip)
+__device__ __forceinline__ int tbbdDecodeOne(const TbbdTable& s, u32 top, u32& sym)
+{
+  const u32 e = s.lut[top >> (32 - kHuffLutBits)];
+  if (e) { sym = e >> 8; return (int)(e & 255u); }
+  const u32 nLong = s.nLong;
+  for (u32 i = 0; i < nLong; i++)
+  {
+    const u32 ls = s.longLenSym[i];
+    const int len = (int)(ls >> 8);
+    if ((top >> (32 - len)) == s.longCode[i]) { sym = ls & 0xFFu; return len; }
+  }
+  return 0;
+}
+
+template<class T>
+__global__ void __launch_bounds__(256)
+k_tbbd_huff(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ offsets, u8* __restrict__ outAll, TbbDecodeBuffers b)
+{
+  __shared__ TbbdTable s_tab;
+  __shared__ u32 s_str[kTbbdStageWords];
+  __shared__ u8 s_len[256];
+  __shared__ u32 s_code[256];
+  __shared__ u32 s_exit[256];
+  __shared__ u32 s_scan[257];
+  __shared__ u32 s_any, s_bad;
+  const u32 t = blockIdx.x;
+  const TbbTile ti = b.tiles[t];
+  if (ti.flags || ti.mode == (u32)IEM_Tiling) return;
+  const u32 nPix = (u32)g.tileElems, nCols = (u32)g.nCols, nRows = (u32)g.nRows;
+  const u8* __restrict__ blob = arena + offsets[t];
+  u8* __restrict__ out = outAll + (u64)t * g.tileElems;
+  const u32 streamBegin = ti.tableBytes, blobEnd = ti.blobSize;
+
+  // ---- the look-up table (buildDecodeTable, huffman_host.cpp): the host fills it symbol by symbol, so where two codes claim an entry
+  // the larger symbol has it
+  const u32 sym = threadIdx.x;
+  const u32 myLen = b.lens[(u64)t * 256u + sym], myCode = b.codes[(u64)t * 256u + sym];
+  s_len[sym] = (u8)myLen; s_code[sym] = myCode;
+  for (u32 i = threadIdx.x; i < (1u << kHuffLutBits); i += 256u) s_tab.lut[i] = 0;
+  if (threadIdx.x == 0) { s_any = 0; s_bad = 0; s_tab.nLong = 0; }
+  __syncthreads();
+  if (myLen > 0u && myLen <= (u32)kHuffLutBits)
+  {
+    const u32 span = 1u << (kHuffLutBits - myLen), base = myCode << (kHuffLutBits - myLen);
+    if (myCode >= (1u << myLen)) s_bad = 1;    // (base + span > the table: the host refuses the blob)
+    else for (u32 j = 0; j < span; j++) atomicMax(&s_tab.lut[base + j], (sym << 8) | myLen);
+  }
+  else if (myLen > (u32)kHuffLutBits)
+  {
+    u32 rank = 0;
+    for (u32 j = 0; j < 256u; j++)
+    {
+      const u32 l = s_len[j];
+      if (l > (u32)kHuffLutBits && (l < myLen || (l == myLen && j < sym))) rank++;
+    }
+    s_tab.longCode[rank] = myCode;
+    s_tab.longLenSym[rank] = (u16)((myLen << 8) | sym);
+    atomicAdd(&s_tab.nLong, 1u);
+  }
+  if (myLen) s_any = 1;
+  // ---- the stream, as whole words; staged where it fits
+  const u32 nWords = (blobEnd - streamBegin) >> 2, streamBits = nWords * 32u;
+  TbbdBits in;
+  in.bytes = blob + streamBegin; in.nWords = nWords;
+  in.s_str = (nWords <= kTbbdStageWords) ? s_str : nullptr;
+  if (in.s_str)
+    for (u32 i = threadIdx.x; i < nWords; i += 256u)
+    {
+      const u8* q = in.bytes + 4ull * i;
+      s_str[i] = (u32)q[0] | ((u32)q[1] << 8) | ((u32)q[2] << 16) | ((u32)q[3] << 24);
+    }
+  __syncthreads();
+  if (s_bad || !s_any)    // (no code at all: codeRange fails on the host)
+  {
+    if (threadIdx.x == 0) b.tiles[t].flags = kTbbTable;
+    return;
+  }
+
+  // ---- 256 sub-sequences: decode from the own start to the own end; then every thread whose predecessor ended somewhere else starts
+  // over from there, until the chain fits (at most one pass a thread: a pass settles at least the first unsettled one)
+  const u32 subBits = ((nWords + 255u) / 256u) * 32u;
+  const u32 end = min((threadIdx.x + 1u) * subBits, streamBits);
+  u32 start = min(threadIdx.x * subBits, streamBits), count = 0, exitPos = start;
+  bool todo = true;
+  for (u32 pass = 0; pass < 258u; pass++)
+  {
+    if (todo)
+    {
+      u32 pos = start, n = 0;
+      while (pos < end)
+      {
+        u32 sy;
+        const int len = tbbdDecodeOne(s_tab, in.top(pos), sy);
+        if (len == 0) break;    // (no code word matches: nothing behind it counts)
+        pos += (u32)len;
+        n++;
+      }
+      exitPos = pos; count = n;
+    }
+    __syncthreads();
+    s_exit[threadIdx.x] = exitPos;
+    if (threadIdx.x == 0) s_any = 0;
+    __syncthreads();
+    todo = false;
+    if (threadIdx.x > 0u)
+    {
+      const u32 before = s_exit[threadIdx.x - 1u];
+      if (before != start) { start = before; todo = true; s_any = 1; }
+    }
+    __syncthreads();
+    if (!s_any) break;
+  }
+  // ---- where each sub-sequence's symbols go
+  __syncthreads();
+  s_scan[threadIdx.x] = count;
+  __syncthreads();
+  if (threadIdx.x == 0) { u32 run = 0; for (u32 i = 0; i < 256u; i++) { const u32 y = s_scan[i]; s_scan[i] = run; run += y; } s_scan[256] = run; }
+  __syncthreads();
+  if (s_any || s_scan[256] < nPix)    // (the chain did not settle -- it cannot be --, or fewer code words than pixels)
+  {
+    if (threadIdx.x == 0) b.tiles[t].flags = kTbbStream;
+    return;
+  }
+  {
+    u32 pos = start, k = s_scan[threadIdx.x];
+    for (u32 i = 0; i < count && k < nPix; i++, k++)
+    {
+      u32 sy = 0;
+      const int len = tbbdDecodeOne(s_tab, in.top(pos), sy);
+      pos += (u32)len;
+      out[k] = (u8)tbbBin<T>(sy);    // (T)(symbol - offset): the same flip of the top bit
+    }
+  }
+  if (ti.mode != (u32)IEM_DeltaHuffman) return;
+
+  // ---- the predictor undone (Lerc2.cpp:2499-2523): column 0 sums down the rows, then every row sums along itself; bytes wrap
+  __syncthreads();
+  u32 carry = 0;
+  for (u32 r0 = 0; r0 < nRows; r0 += 256u)
+  {
+    const u32 r = r0 + threadIdx.x;
+    const u32 v = r < nRows ? out[(u64)r * nCols] : 0u;
+    const u32 incl = waveInclusiveScan(v);
+    if (laneId() == 63) s_scan[waveId()] = incl;
+    __syncthreads();
+    u32 before = carry, total = 0;
+    for (int w = 0; w < 4; w++) { if (w < waveId()) before += s_scan[w]; total += s_scan[w]; }
+    if (r < nRows) out[(u64)r * nCols] = (u8)(before + incl);
+    carry += total;
+    __syncthreads();
+  }
+  for (u32 r = (u32)waveId(); r < nRows; r += 4u)
+  {
+    u8* __restrict__ row = out + (u64)r * nCols;
+    u32 run = 0;
+    for (u32 j0 = 0; j0 < nCols; j0 += 64u)
+    {
+      const u32 j = j0 + (u32)laneId();
+      const u32 v = j < nCols ? row[j] : 0u;
+      const u32 incl = waveInclusiveScan(v) + run;
+      if (j < nCols) row[j] = (u8)incl;
+      run = __shfl(incl, 63);
+    }
+  }
+}
+
+template<class T>
+static void tbbDecodeT(const TbbGeom& g, const u8* dArena, const u64* dOffsets, const u32* dSizes, void* dTiles, const TbbDecodeBuffers& b, hipStream_t st)
+{
+  const int nPos = g.nTV * g.nTH;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_parse<T>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, dSizes, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_blocks<T>), dim3((nPos + 3) / 4, g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, (T*)dTiles, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_huff<T>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, (u8*)dTiles, b);
+}
+
+void launchTbbDecode(const TbbGeom& g, const u8* dArena, const u64* dOffsets, const u32* dSizes, void* dTiles, const TbbDecodeBuffers& b, hipStream_t st)
+{
+  if (g.dt == DT_Char) tbbDecodeT<signed char>(g, dArena, dOffsets, dSizes, dTiles, b, st);
+  else if (g.dt == DT_Byte) tbbDecodeT<unsigned char>(g, dArena, dOffsets, dSizes, dTiles, b, st);
+}
+
+}    // namespace lerc

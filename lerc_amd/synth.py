@@ -104,3 +104,8 @@ def island(kind, size=4096, tile=256):
     else:
         a, e = c3_uint16(size, size).to(torch.int32).numpy().astype(np.uint16), 0.0
     return cut_tiles(a, tile), cut_tiles(island_mask(size), tile), e
+
+
+def byte_mosaic(size=4096, tile=256, channel=0):
+    """-> uint8 tiles [n, tile, tile]: channel `channel` of c4_rgb_u8(size, size), cut by cut_tiles"""
+    return cut_tiles(np.ascontiguousarray(c4_rgb_u8(size, size).numpy()[:, :, channel]), tile)
