@@ -86,17 +86,19 @@ LERC_AMD_API lerc_status lerc_amd_decode_tiles_device_slots(lerc_amd_context* ct
  * offsets[t] is set to that (arenaCapacity >= nTiles * slotBytes).  Tile t's blob is byte for byte what lerc_encode(tile t, nMasks = 1,
  * mask t) makes; a tile without an invalid pixel gets no mask section.  The batch's own launches (one set per sub-batch, one host wait)
  * take float32, float64 and the 16- and 32-bit integer types, tiles of up to 131 072 pixels and 4 096 blocks (256 x 256, 257 x 257), and
- * write header, mask section (run-length coded on the device), ranges, block stream and checksum.  Tiles whose outcome is decided
- * elsewhere -- no valid pixel, a constant tile, NaN, the 16 x 16 retry of the low-bit-rate rule, one sweep -- and 8-bit types WITH a mask pointer, larger tiles, maxZErr == 777 or 0 on float values are encoded inside the call, one by
- * one, with the same result (8-bit tiles with dValidBytes == NULL are the 8-bit batch described above).  Status codes as for the unmasked calls. */
+ * write header, mask section (run-length coded on the device), ranges, block stream and checksum -- of tiles without a valid pixel
+ * (header only), constant tiles (header and mask section), one-sweep tiles (the valid pixels raw) and tiles whose low-bit-rate retry
+ * ends in 16 x 16 blocks as well.  A tile with a NaN at a valid pixel (its mask changes), and 8-bit types WITH a mask pointer, larger
+ * tiles, maxZErr == 777 or 0 on float values are encoded inside the call, one by one, with the same result (8-bit tiles with dValidBytes == NULL are the 8-bit batch described above).  Status codes as for the unmasked calls. */
 LERC_AMD_API lerc_status lerc_amd_encode_tiles_device_masked(lerc_amd_context* ctx, const void* dTiles, unsigned int dataType, int nCols, int nRows,
     int nTiles, const unsigned char* dValidBytes, double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity,
     unsigned long long slotBytes, unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed);
 /* The way back.  dValidBytes: device, [nTiles][nRows][nCols], written 1 / 0 for EVERY tile (all ones for a blob without a mask section,
  * all zeros for a blob without valid pixels); NULL: the call is lerc_amd_decode_tiles_device (WrongParam(2) as soon as a blob carries a
  * mask).  Pixels: exactly what lerc_amd_decode_device writes for that blob (0 at invalid pixels).  The batch's launches take codec 6
- * blobs in 8 x 8 tiling mode of the types and sizes above, with or without a mask section; every other blob (16 x 16 blocks, one sweep,
- * constant, empty, older codecs, damaged ...) is decoded by itself inside the call.  A blob that fails leaves its tile zeroed, mask
+ * blobs of the types and sizes above, with or without a mask section: blocks of 8 x 8 or 16 x 16, one sweep, constant and empty blobs;
+ * every other blob (older codecs, damaged, or one the batch's parse is not certain of: bytes behind the last section, a mask whose count
+ * of valid pixels is not the header's ...) is decoded by itself inside the call.  A blob that fails leaves its tile zeroed, mask
  * too; the other tiles are decoded all the same, and the call returns the first such status. */
 LERC_AMD_API lerc_status lerc_amd_decode_tiles_device_masked(lerc_amd_context* ctx, const unsigned char* dArena, const unsigned long long* offsets,
     const unsigned int* sizes, int nTiles, int nCols, int nRows, unsigned int dataType, void* dTiles, unsigned char* dValidBytes);

@@ -29,6 +29,7 @@ static TmbGeom tmbGeom(int dt, int nRows, int nCols, u32 nTiles)
   g.bitStride = (nBytes + 16u + 15u) & ~15u;
   g.rleStride = (2u * nBytes + 64u + 15u) & ~15u;    // (no stream is longer: a literal byte costs 1 + 2 / 32767, a run of five 3)
   g.posStride = ((u32)(g.nTV * g.nTH) + 1u + 3u) & ~3u;
+  g.pos16Stride = ((u32)(((nRows + 15) / 16) * ((nCols + 15) / 16)) + 1u + 3u) & ~3u;
   return g;
 }
 
@@ -76,7 +77,7 @@ u32 encodeTilesDeviceMasked(Context& ctx, const TilesEncodeRequest& rq, u64& are
 
   hipStream_t st = ctx.activeStream();
   const TmbGeom g1 = tmbGeom(rq.dt, rq.nRows, rq.nCols, 1);
-  const size_t perTile = sizeof(TmbTile) + g1.bitStride + g1.rleStride + (size_t)g1.posStride * 4;
+  const size_t perTile = sizeof(TmbTile) + g1.bitStride + g1.rleStride + ((size_t)g1.posStride + g1.pos16Stride) * 4;
   // (a tile is a blockIdx.y: at most 65535 of them per launch)
   const int maxBatch = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)rq.nTiles, 65535), ((size_t)256 << 20) / perTile));
   u32 cand = 0;
@@ -109,8 +110,9 @@ u32 encodeTilesDeviceMasked(Context& ctx, const TilesEncodeRequest& rq, u64& are
     b.bits = ctx.allocT<u8>((size_t)n * g.bitStride);
     b.rle = ctx.allocT<u8>((size_t)n * g.rleStride);
     b.blockOff = ctx.allocT<u32>((size_t)n * g.posStride);
+    b.blockOff16 = ctx.allocT<u32>((size_t)n * g.pos16Stride);
     u8* pin = (u8*)ctx.pinned(recBytes);
-    if (!rec || !b.bits || !b.rle || !b.blockOff || !pin) return kFailed;
+    if (!rec || !b.bits || !b.rle || !b.blockOff || !b.blockOff16 || !pin) return kFailed;
     end = (end + 15) & ~15ull;
     (void)hipGetLastError();
     {

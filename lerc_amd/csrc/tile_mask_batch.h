@@ -7,20 +7,27 @@ namespace lerc {
 // why a tile left the batch (it is then encoded / decoded by itself behind the batch, with its mask)
 enum : u32
 {
-  kTmbEmpty = 1u,         // no valid pixel: a header-only blob
-  kTmbConst = 2u,         // every valid pixel has the same value
   kTmbNaN = 4u,           // a NaN at a valid pixel (the mask changes)
-  kTmbRetry16 = 32u,      // the low-bit-rate rule asks for 16 x 16 blocks
   kTmbCapacity = 64u,     // the blob does not fit its slot (encoded by itself, that tile says BufferTooSmall)
   kTmbArenaFull = 128u,   // the blob does not fit what is left of the arena
-  kTmbOneSweep = 256u,    // the raw form is no longer than the blocks
   kTmbRle = 512u,         // the mask's run-length stream outgrew its scratch
   // decode
-  kTmbHeader = 1024u,     // not a header the batch takes (codec < 6, another shape or type, 16 x 16 blocks, a mode byte, ...)
+  kTmbHeader = 1024u,     // not a header the batch takes (codec < 6, another shape or type, blocks other than 8 x 8 or 16 x 16, a mode byte,
+                          // bytes behind the last section, a count of valid pixels the mask does not share, ...)
   kTmbChecksum = 2048u,   // Fletcher32 differs
   kTmbMaskStream = 4096u, // the mask's run-length stream is damaged
   kTmbBlocks = 8192u,     // the walk met a block header that cannot be, or the blocks do not end where the blob does
   kTmbSibling = 16384u    // a block's decode failed (raised by the block kernel's waves)
+};
+
+// what a tile's blob holds behind header and mask section (TmbTile::kind)
+enum : u32
+{
+  kTmbKindBlocks8 = 0u,   // ranges, a 0 byte, the stream of 8 x 8 blocks
+  kTmbKindBlocks16 = 1u,  // the same with 16 x 16 blocks: the low-bit-rate retry won (Lerc2.cpp:333-357)
+  kTmbKindEmpty = 2u,     // no valid pixel: nothing
+  kTmbKindConst = 3u,     // every valid pixel has the header's zMin: nothing
+  kTmbKindOneSweep = 4u   // ranges, a 1 byte, the valid pixels raw in row order
 };
 
 struct TmbTile    // one per tile, device; copied home after the batch
@@ -37,6 +44,10 @@ struct TmbTile    // one per tile, device; copied home after the batch
   double maxZErr;         // the tile's own error bound (encode: k_tmb_prelude decides it; decode: the header's)
   u32 checksum;           // decode: the header's
   u32 isInt;              // encode: float values that are all integers (header byte)
+  u32 kind;               // kTmbKind...
+  u32 retry;              // encode: the low-bit-rate rule asks for the sizes of 16 x 16 blocks (k_tmb_decide)
+  u32 mbSize;             // encode: the header's microBlockSize -- 16 once the retry has won, even if one sweep then beats the blocks
+  u32 rsv;
 };
 
 struct TmbGeom
@@ -46,6 +57,7 @@ struct TmbGeom
   u32 bitStride;          // bytes between the tiles' bit masks (a multiple of 16)
   u32 rleStride;          // bytes between the tiles' run-length scratch
   u32 posStride;          // words between the tiles' block tables (>= nTV * nTH + 1)
+  u32 pos16Stride;        // encode: words between the tiles' tables of 16 x 16 blocks (>= their number + 1)
   u64 tileElems;
 };
 
@@ -58,6 +70,7 @@ struct TmbEncodeBuffers
   u8* bits;               // [nTiles][bitStride]
   u8* rle;                // [nTiles][rleStride]
   u32* blockOff;          // [nTiles][posStride]: sizes, then their exclusive scan
+  u32* blockOff16;        // [nTiles][pos16Stride]: the same for 16 x 16 blocks, tiles with TmbTile::retry only
 };
 // maxZErr: the header's for a tile whose statistics decide nothing else; cand: TryRaiseMaxZError candidates whose error bound beats it (bit c: factor c)
 void launchTmbEncode(const TmbGeom& g, const BandParams& bp, double maxZErr, u32 cand, const void* dTiles, const u8* dValidBytes, u8* dArena,

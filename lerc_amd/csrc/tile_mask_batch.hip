@@ -5,25 +5,33 @@
 // Encode (launchTmbEncode), every section of a masked band's blob made on the device:
 //   1. k_tmb_prelude   a workgroup per tile: byte mask -> bit mask (BitMask's layout: most significant bit first) in LDS and in
 //                      global memory, the count of valid pixels, the range over them, NaN findings, the tile's own error bound (all-integer
-//                      float values, TryRaiseMaxZError), and the mask's run-length stream (RLE.cpp:123-254, the same bytes as rleEncode, codec_common.cpp)
-//   2. k_tmb_blocks<false>   a wave per 8 x 8 block: the block's size (the general encoder's decisions, tile_encode.hip)
-//   3. k_tmb_decide    a workgroup per tile: the sizes' exclusive scan, the 16 x 16 retry rule (Lerc2.cpp:333-357), one sweep, the
-//                      blob's size, the slot check;  k_tmb_arena: one workgroup places the blobs in a packed arena (16-byte aligned)
-//   4. k_tmb_blocks<true>    the blocks' bytes, and one more workgroup per tile that writes header, mask section, ranges and the
-//                      "not one sweep" byte
+//                      float values, TryRaiseMaxZError; 0 for a float tile without a valid pixel), the tile's kind where the statistics
+//                      settle it (empty, constant), and the mask's run-length stream (RLE.cpp:123-254, the same bytes as rleEncode,
+//                      codec_common.cpp)
+//   2. k_tmb_blocks<8, false>    a wave per 8 x 8 block: the block's size (the general encoder's decisions, tile_encode.hip)
+//   3. k_tmb_decide    a workgroup per tile: the sizes' exclusive scan; marks the tiles the low-bit-rate rule (Lerc2.cpp:333-357) sends
+//                      to the retry;  k_tmb_blocks<16, false>: the sizes of 16 x 16 blocks of the marked tiles (launched over the whole
+//                      batch: the host does not wait to learn which tiles are marked);  k_tmb_decide2: 16 x 16 if no longer (:346),
+//                      then one sweep against what is left, the blob's size, the slot check;  k_tmb_arena: one workgroup places the blobs
+//                      of every kind in a packed arena (16-byte aligned)
+//   4. k_tmb_blocks<8, true>, <16, true>    the blocks' bytes of the tiles of that block size; in the 8 x 8 launch one more workgroup
+//                      per tile writes header and mask section, and where the valid pixels differ ranges and the "one sweep" byte --
+//                      behind a 1 the valid pixels raw in row order, by their rank among the valid pixels (a workgroup scan over the
+//                      popcounts of the bit mask)
 //   5. k_tmb_checksum  a workgroup per tile: Fletcher32 over blob[14 ..) (Lerc2.cpp:1037-1064), stored into the header.  It reads
 //                      the finished blob, whatever the parity of the mask section's length.
-// Tiles whose outcome is decided elsewhere (TmbTile::flags) are left alone; the host encodes them one by one behind the batch.
+// Tiles that leave the batch (TmbTile::flags: NaN at a valid pixel, no room) are left alone; the host encodes them one by one behind it.
 // No workgroup waits for another one inside a launch, so the emulator build runs the same path.
 //
 // Decode (launchTmbDecode):
-//   1. k_tmbd_parse    a workgroup per tile: header, Fletcher32, the mask's run-length stream expanded into LDS (bounded by the
-//                      section's length and the mask's size), valid counts per block by popcount, the caller's valid bytes, and the
-//                      walk over the block headers -- a block's length follows from its header and its valid count, which is known
-//                      here -- into a table of block offsets
-//   2. k_tmbd_blocks   a wave per block: the general decoder's block (tile_decode.hip), checked against the table
-// Every walk is bounded by the blob's size; whatever does not fit raises a flag and the host repeats that tile with the
-// single-blob decoder, which also yields the exact status of a damaged blob.
+//   1. k_tmbd_parse    a workgroup per tile: header (which names the blob's kind: no valid pixel, zMin == zMax, the one-sweep byte,
+//                      blocks of 8 x 8 or 16 x 16), Fletcher32, the mask's run-length stream expanded into LDS (bounded by the section's
+//                      length and the mask's size), the caller's valid bytes; the pixels of empty, constant and one-sweep blobs; for
+//                      blocks the valid counts per block by popcount and the walk over the block headers -- a block's length follows
+//                      from its header and its valid count, which is known here -- into a table of block offsets
+//   2. k_tmbd_blocks<8>, <16>   a wave per block: the general decoder's block (tile_decode.hip), checked against the table
+// Every walk is bounded by the blob's size; whatever does not fit, or is not certain, raises a flag and the host repeats that tile with
+// the single-blob decoder, which also yields the exact status of a damaged blob.
 #include <cstdio>
 #include <cstdlib>
 #include "kernels.h"
@@ -125,8 +133,7 @@ k_tmb_prelude(TmbGeom g, double maxZErr, u32 cand, const T* __restrict__ data, c
   memset(&ti, 0, sizeof(ti));
   ti.numValid = numValid;
   u32 fl = anyFlags;
-  if (numValid == 0) fl |= kTmbEmpty;
-  else if (!(mn < mx)) fl |= kTmbConst;
+  ti.kind = (numValid == 0) ? kTmbKindEmpty : (!(mn < mx) ? kTmbKindConst : kTmbKindBlocks8);
   if (numValid)
   {
     ti.zMin = (double)mn; ti.zMax = (double)mx;
@@ -136,6 +143,7 @@ k_tmb_prelude(TmbGeom g, double maxZErr, u32 cand, const T* __restrict__ data, c
   // (encodeBand, codec_encode.cpp, restated per tile): float values that are all integers inside the type's exact range make the
   // tile an integer one (isInt in the header, bound max(0.5, floor)); else the first candidate bound every valid value agrees with
   ti.maxZErr = maxZErr;
+  if (isFlt && !numValid) ti.maxZErr = 0;    // "tile has no valid data" (Lerc.cpp:1479-1484)
   if (isFlt && numValid)
   {
     const double lim = (g.dt == DT_Float) ? (double)(1 << 23) : (double)(1ll << 53);
@@ -162,7 +170,7 @@ k_tmb_prelude(TmbGeom g, double maxZErr, u32 cand, const T* __restrict__ data, c
   // ---- the mask's run-length stream: [int16 n][payload] ..., n > 0 literal bytes, n < 0 one byte -n times, -32768 ends it; a run
   // is opened only where at least 5 equal bytes start and one more byte follows; segments are cut at 32767
   u32 rleLen = 0;
-  if (fl == 0 && numValid < nPix)
+  if (fl == 0 && numValid > 0 && numValid < nPix)
   {
     u8* __restrict__ out = b.rle + (u64)t * g.rleStride;
     const u32 cap = g.rleStride, n = nBytes;
@@ -203,82 +211,146 @@ k_tmb_prelude(TmbGeom g, double maxZErr, u32 cand, const T* __restrict__ data, c
   }
   ti.flags = fl;
   ti.rleLen = rleLen;
-  ti.dataBegin = kHdr6 + 4u + rleLen + 2u * (u32)sizeof(T) + 1u;    // header, mask section, ranges, "not one sweep"
+  // header and mask section; where pixels differ: ranges and the "one sweep" byte
+  ti.dataBegin = kHdr6 + 4u + rleLen + (ti.kind == kTmbKindBlocks8 ? 2u * (u32)sizeof(T) + 1u : 0u);
+  ti.mbSize = 8u;
+  ti.blobSize = ti.dataBegin;    // (all there is of an empty or a constant tile; the others: k_tmb_decide2)
   b.tiles[t] = ti;
 }
 
-// A wave per 8 x 8 block of a tile (blockIdx.y): k_encode_tiles (tile_encode.hip) for one value a pixel, with the tile's own mask,
-// "all valid" and place in the arena.  WRITE: the workgroup behind the last block writes what lies in front of the block stream.
-template<class T, bool WRITE>
+// The pixels of a tile in row order, the valid ones with their rank among the valid ones, by one workgroup of 256 threads: a thread
+// takes a byte of the bit mask (8 pixels) a round, a round's popcounts are scanned over the workgroup.  f(pixel, valid, rank) is
+// called once for every pixel below nPix (the tail bits of an encoder's mask are set: they do not count).  s: 4 words of LDS.
+template<class F>
+__device__ __forceinline__ u32 tmbRankedSweep(const u8* bits, u32 nPix, u32* s, F f)
+{
+  const u32 nBytes = (nPix + 7u) >> 3;
+  u32 run = 0;
+  for (u32 base = 0; base < nBytes; base += 256u)
+  {
+    const u32 by = base + threadIdx.x;
+    u32 m = by < nBytes ? (u32)bits[by] : 0u;
+    if (8u * by + 8u > nPix) m &= (8u * by < nPix) ? (0xFF00u >> (nPix - 8u * by)) & 0xFFu : 0u;
+    const u32 c = (u32)__popc(m), inc = waveInclusiveScan(c);
+    if (laneId() == 63) s[waveId()] = inc;
+    __syncthreads();
+    u32 r = run + inc - c;
+    for (int w = 0; w < waveId(); w++) r += s[w];
+    run += s[0] + s[1] + s[2] + s[3];
+    for (u32 j = 0; j < 8u && 8u * by + j < nPix; j++)
+    {
+      const bool valid = (m & (0x80u >> j)) != 0u;
+      f(8u * by + j, valid, r);
+      r += valid ? 1u : 0u;
+    }
+    __syncthreads();
+  }
+  return run;
+}
+
+// What lies in front of a tile's block stream, by one workgroup: header (Lerc2.cpp:724-786; checksum patched by k_tmb_checksum),
+// mask section; where the valid pixels differ: ranges and the "one sweep" byte, and behind a 1 the valid pixels raw in row
+// order (Lerc2::WriteDataOneSweep)
+template<class T>
+__device__ __forceinline__ void tmbWriteFront(const TmbGeom& g, u32 t, const TmbTile& ti, const T* __restrict__ px, u8* __restrict__ blob, const TmbEncodeBuffers& b)
+{
+  __shared__ u8 s_hdr[96];
+  __shared__ u32 s_w[4];
+  if (threadIdx.x == 0)
+  {
+    u8* h = s_hdr;
+    const char magic[6] = { 'L', 'e', 'r', 'c', '2', ' ' };
+    for (int i = 0; i < 6; i++) h[i] = (u8)magic[i];
+    const int ints[10] = { kCodecVersion, 0, g.nRows, g.nCols, 1, (int)ti.numValid, (int)ti.mbSize, (int)ti.blobSize, g.dt, 0 };
+    for (int i = 0; i < 10; i++) putBytes(h + 6 + 4 * i, (u64)(u32)ints[i], 4);
+    putBytes(h + 46, ti.isInt ? 0x100ull : 0ull, 4);    // passNoData, isInt, two reserved bytes
+    const double dbl[5] = { ti.maxZErr, ti.zMin, ti.zMax, 0.0, 0.0 };
+    for (int i = 0; i < 5; i++) { u64 bits; memcpy(&bits, &dbl[i], 8); putBytes(h + 50 + 8 * i, bits, 8); }
+    putBytes(h + kHdr6, (u64)ti.rleLen, 4);
+  }
+  __syncthreads();
+  for (u32 i = threadIdx.x; i < kHdr6 + 4u; i += 256u) blob[i] = s_hdr[i];
+  const u8* __restrict__ rle = b.rle + (u64)t * g.rleStride;
+  for (u32 i = threadIdx.x; i < ti.rleLen; i += 256u) blob[kHdr6 + 4u + i] = rle[i];
+  if (ti.kind == kTmbKindEmpty || ti.kind == kTmbKindConst) return;    // (Lerc2.cpp:235-241, :255: nothing behind the mask)
+  if (threadIdx.x == 0)
+  {
+    u8* r = blob + kHdr6 + 4u + ti.rleLen;
+    putBytes(r, ti.minBits, (int)sizeof(T));
+    putBytes(r + sizeof(T), ti.maxBits, (int)sizeof(T));
+    r[2 * sizeof(T)] = ti.kind == kTmbKindOneSweep ? 1 : 0;
+  }
+  if (ti.kind != kTmbKindOneSweep) return;
+  u8* __restrict__ dst = blob + ti.dataBegin;    // (any alignment: bytes)
+  auto put = [&](u32 k, bool valid, u32 rank)
+  {
+    if (!valid) return;
+    u64 bits = 0;
+    const T v = px[k];
+    memcpy(&bits, &v, sizeof(T));
+    putBytes(dst + (u64)rank * sizeof(T), bits, (int)sizeof(T));
+  };
+  const u32 nPix = (u32)g.tileElems;
+  if (ti.numValid == nPix) { for (u32 k = threadIdx.x; k < nPix; k += 256u) put(k, true, k); }
+  else tmbRankedSweep(b.bits + (u64)t * g.bitStride, nPix, s_w, put);
+}
+
+// A wave per MB x MB block of a tile (blockIdx.y): k_encode_tiles (tile_encode.hip) for one value a pixel, with the tile's own mask,
+// "all valid" and place in the arena; lane l holds elements l, l + 64, ... of the block.  Sizes: 8 x 8 for every tile with blocks,
+// 16 x 16 for the tiles k_tmb_decide marked.  WRITE: the tiles of that block size, and in the 8 x 8 launch one more workgroup behind
+// a tile's last block that writes what lies in front of the block stream -- for a tile of any kind.
+template<class T, int MB, bool WRITE>
 __global__ void __launch_bounds__(256)
 k_tmb_blocks(TmbGeom g, BandParams p, const T* __restrict__ data, u8* __restrict__ arena, TmbEncodeBuffers b)
 {
-  constexpr int NMAX = 64;
+  constexpr int E = MB * MB / 64, NMAX = MB * MB;
   constexpr int OBW = (1 + NMAX * (int)sizeof(T) + 3) / 4 + 4;
   __shared__ T s_val[4][NMAX];
   __shared__ u32 s_obuf[4][WRITE ? OBW : 1];
   __shared__ u32 s_lut[4][WRITE ? NMAX : 1];
-  __shared__ u8 s_hdr[WRITE ? 96 : 1];
   const u32 t = blockIdx.y;
   const TmbTile ti = b.tiles[t];
   if (ti.flags) return;
-  const int nPos = g.nTV * g.nTH;
+  const int nTV = (g.nRows + MB - 1) / MB, nTH = (g.nCols + MB - 1) / MB;
+  const int nPos = nTV * nTH;
   const u32 nPix = (u32)g.tileElems;
   u8* __restrict__ blob = WRITE ? arena + ti.offset : nullptr;
+  const T* __restrict__ px = data + (u64)t * g.tileElems;
 
-  if (WRITE && blockIdx.x == gridDim.x - 1)
-  {
-    // ---- header (Lerc2.cpp:724-786; checksum patched by k_tmb_checksum), mask section, ranges, "not one sweep"
-    if (threadIdx.x == 0)
-    {
-      u8* h = s_hdr;
-      const char magic[6] = { 'L', 'e', 'r', 'c', '2', ' ' };
-      for (int i = 0; i < 6; i++) h[i] = (u8)magic[i];
-      const int ints[10] = { kCodecVersion, 0, g.nRows, g.nCols, 1, (int)ti.numValid, 8, (int)ti.blobSize, g.dt, 0 };
-      for (int i = 0; i < 10; i++) putBytes(h + 6 + 4 * i, (u64)(u32)ints[i], 4);
-      putBytes(h + 46, ti.isInt ? 0x100ull : 0ull, 4);    // passNoData, isInt, two reserved bytes
-      const double dbl[5] = { ti.maxZErr, ti.zMin, ti.zMax, 0.0, 0.0 };
-      for (int i = 0; i < 5; i++) { u64 bits; memcpy(&bits, &dbl[i], 8); putBytes(h + 50 + 8 * i, bits, 8); }
-      putBytes(h + kHdr6, (u64)ti.rleLen, 4);
-    }
-    __syncthreads();
-    for (u32 i = threadIdx.x; i < kHdr6 + 4u; i += 256u) blob[i] = s_hdr[i];
-    const u8* __restrict__ rle = b.rle + (u64)t * g.rleStride;
-    for (u32 i = threadIdx.x; i < ti.rleLen; i += 256u) blob[kHdr6 + 4u + i] = rle[i];
-    if (threadIdx.x == 0)
-    {
-      u8* r = blob + kHdr6 + 4u + ti.rleLen;
-      putBytes(r, ti.minBits, (int)sizeof(T));
-      putBytes(r + sizeof(T), ti.maxBits, (int)sizeof(T));
-      r[2 * sizeof(T)] = 0;
-    }
-    return;
-  }
+  if (WRITE && MB == 8 && blockIdx.x == gridDim.x - 1) { tmbWriteFront<T>(g, t, ti, px, blob, b); return; }
+  if (WRITE ? ti.kind != (MB == 8 ? kTmbKindBlocks8 : kTmbKindBlocks16) : (ti.kind != kTmbKindBlocks8 || (MB == 16 && !ti.retry))) return;
 
   const int w = waveId(), lane = laneId();
   const int pos = (int)blockIdx.x * 4 + w;
   if (pos >= nPos) return;    // whole wave leaves together
+  p.mb = MB; p.nTV = nTV; p.nTH = nTH;
   p.allValid = (ti.numValid == nPix) ? 1 : 0;
   p.maxZErr = ti.maxZErr; p.scale = 1 / (2 * ti.maxZErr); p.invScale = 2 * ti.maxZErr;    // (the tile's own bound: k_tmb_prelude)
-  const T* __restrict__ px = data + (u64)t * g.tileElems;
   const u8* __restrict__ maskBits = b.bits + (u64)t * g.bitStride;
-  u32* __restrict__ table = b.blockOff + (u64)t * g.posStride;
-  const int it = pos / g.nTH, jt = pos - it * g.nTH;
-  const int i0 = it * 8, j0 = jt * 8;
-  const int tileH = min(8, g.nRows - i0), tileW = min(8, g.nCols - j0);
+  u32* __restrict__ table = MB == 8 ? b.blockOff + (u64)t * g.posStride : b.blockOff16 + (u64)t * g.pos16Stride;
+  const int it = pos / nTH, jt = pos - it * nTH;
+  const int i0 = it * MB, j0 = jt * MB;
+  const int tileH = min(MB, g.nRows - i0), tileW = min(MB, g.nCols - j0);
   const int nElem = tileH * tileW;
   const u64 lt = laneMaskLt();
 
-  int rank[1];
-  T v[1];
-  u32 q[1];
-  const bool inb = lane < nElem;
-  const int r = inb ? lane / tileW : 0, c = inb ? lane - r * tileW : 0;
-  const i64 pix = (i64)(i0 + r) * g.nCols + (j0 + c);
-  const bool valid = inb && (p.allValid || maskBit(maskBits, pix));
-  const u64 bal = __ballot(valid);
-  rank[0] = valid ? __popcll(bal & lt) : -1;
-  const int n = __popcll(bal);
+  int rank[E];
+  i64 pix[E];
+  T v[E];
+  u32 q[E];
+  int n = 0;
+#pragma unroll
+  for (int k = 0; k < E; k++)
+  {
+    const int e = k * 64 + lane;
+    const bool inb = e < nElem;
+    const int r = inb ? e / tileW : 0, c = inb ? e - r * tileW : 0;
+    pix[k] = (i64)(i0 + r) * g.nCols + (j0 + c);
+    const bool valid = inb && (p.allValid || maskBit(maskBits, pix[k]));
+    const u64 bal = __ballot(valid);
+    rank[k] = valid ? n + __popcll(bal & lt) : -1;
+    n += __popcll(bal);
+  }
 
   if (n == 0)    // empty position: one "all zero" byte (Lerc2.cpp:1534-1538, :1960-1966)
   {
@@ -287,19 +359,30 @@ k_tmb_blocks(TmbGeom g, BandParams p, const T* __restrict__ data, u8* __restrict
     return;
   }
   T* valBuf = s_val[w];
-  v[0] = T(0);
-  if (valid) { v[0] = px[pix]; valBuf[rank[0]] = v[0]; }
+#pragma unroll
+  for (int k = 0; k < E; k++)
+  {
+    v[k] = T(0);
+    if (rank[k] >= 0) { v[k] = px[pix[k]]; valBuf[rank[k]] = v[k]; }
+  }
   waveSync();
 
   // --- statistics (GetValidDataAndStats)
   T mn = valBuf[0], mx = valBuf[0];
-  if (valid) { mn = v[0]; mx = v[0]; }
+#pragma unroll
+  for (int k = 0; k < E; k++)
+    if (rank[k] >= 0) { mn = (v[k] < mn) ? v[k] : mn; mx = (v[k] > mx) ? v[k] : mx; }
   mn = waveMinT(mn);
   mx = waveMaxT(mx);
-  bool s = false;
-  if (rank[0] > 0) s = (v[0] == valBuf[rank[0] - 1]);
-  else if (rank[0] == 0) s = p.allValid ? (v[0] == T(0)) : false;    // prevVal starts at 0 (all-valid branch only)
-  const int same = __popcll(__ballot(s));
+  int same = 0;
+#pragma unroll
+  for (int k = 0; k < E; k++)
+  {
+    bool s = false;
+    if (rank[k] > 0) s = (v[k] == valBuf[rank[k] - 1]);
+    else if (rank[k] == 0) s = p.allValid ? (v[k] == T(0)) : false;    // prevVal starts at 0 (all-valid branch only)
+    same += __popcll(__ballot(s));
+  }
   const bool tryLut = (n > 4) && ((double)mx > (double)mn + 3 * p.maxZErr) && (2 * same > n);
 
   double mv = 0;
@@ -310,50 +393,79 @@ k_tmb_blocks(TmbGeom g, BandParams p, const T* __restrict__ data, u8* __restrict
     quantOk = !(mv > (double)p.maxQ || (u32)(mv + 0.5) == 0);
   }
   u32 qMax = 0;
-  q[0] = 0;
+#pragma unroll
+  for (int k = 0; k < E; k++) q[k] = 0;
   if (quantOk)
   {
-    if (valid) q[0] = p.intLossless ? quantLossless<T>(v[0], mn) : (u32)(((double)v[0] - (double)mn) * p.scale + 0.5);
-    qMax = waveMax(q[0]);
+#pragma unroll
+    for (int k = 0; k < E; k++)
+      if (rank[k] >= 0)
+      {
+        q[k] = p.intLossless ? quantLossless<T>(v[k], mn) : (u32)(((double)v[k] - (double)mn) * p.scale + 0.5);
+        qMax = q[k] > qMax ? q[k] : qMax;
+      }
+    qMax = waveMax(qMax);
   }
   u32 nDistinct = 0;
   if (tryLut && quantOk)
   {
-    u32 idxTmp[1];
-    nDistinct = extractDistinct<1>(q, rank, nullptr, idxTmp);
+    u32 idxTmp[E];
+    nDistinct = extractDistinct<E>(q, rank, nullptr, idxTmp);
   }
   const Plan plan = planBlock<T>(p, n, mn, mx, p.dt, tryLut, mv, qMax, nDistinct);
   if (!WRITE) { if (lane == 0) table[pos] = (u32)plan.nBytes; return; }
 
   u32* obuf = s_obuf[w];
-  composeBlock<T, 1>(obuf, s_lut[w], p, plan, n, j0, false, mn, v, q, rank, qMax);
+  composeBlock<T, E>(obuf, s_lut[w], p, plan, n, j0, false, mn, v, q, rank, qMax);
   const u8* ob8 = reinterpret_cast<const u8*>(obuf);
   u8* __restrict__ dst = blob + ti.dataBegin + table[pos];
   for (int i = lane; i < plan.nBytes; i += 64) dst[i] = ob8[i];
 }
 
-__global__ void __launch_bounds__(256) k_tmb_decide(TmbGeom g, u32 tb, u64 slotBytes, u64 firstTile, TmbEncodeBuffers b)
+// the 8 x 8 blocks' sizes scanned, and whether the low-bit-rate rule asks for the sizes of 16 x 16 blocks too
+__global__ void __launch_bounds__(256) k_tmb_decide(TmbGeom g, u32 tb, TmbEncodeBuffers b)
 {
   __shared__ u32 s_scan[257];
   const u32 t = blockIdx.x;
-  if (b.tiles[t].flags) return;
+  if (b.tiles[t].flags || b.tiles[t].kind != kTmbKindBlocks8) return;    // (neither is written in this kernel)
   const u32 nPos = (u32)(g.nTV * g.nTH);
   const u32 nBytesTiling = blockScanInPlace(b.blockOff + (u64)t * g.posStride, nPos, s_scan);
   if (threadIdx.x != 0) return;
   TmbTile& ti = b.tiles[t];
   const u64 nPix = g.tileElems, oneSweep = (u64)tb * ti.numValid;
-  u32 fl = 0;
   // 16 x 16 blocks at low bit rates (Lerc2.cpp:333-357; nPix counts invalid pixels too)
-  if ((double)((u64)nBytesTiling * 8u) < (double)nPix * 1.5 && (u64)nBytesTiling < 4u * oneSweep && (g.nRows > 8 || g.nCols > 8)) fl |= kTmbRetry16;
-  if (oneSweep <= (u64)nBytesTiling) fl |= kTmbOneSweep;
+  ti.retry = ((double)((u64)nBytesTiling * 8u) < (double)nPix * 1.5 && (u64)nBytesTiling < 4u * oneSweep && (g.nRows > 8 || g.nCols > 8)) ? 1u : 0u;
   ti.nBytesTiling = nBytesTiling;
-  ti.blobSize = ti.dataBegin + nBytesTiling;
+}
+
+// Lerc2.cpp:330-381 from the retry on: 16 x 16 blocks if they are no longer than the 8 x 8 ones (:346), one sweep if it is no
+// longer than the blocks that are left, the blob's size, the slot check
+__global__ void __launch_bounds__(256) k_tmb_decide2(TmbGeom g, u32 tb, u64 slotBytes, u64 firstTile, TmbEncodeBuffers b)
+{
+  __shared__ u32 s_scan[257];
+  __shared__ u32 s_rec[3];
+  const u32 t = blockIdx.x;
+  // (the record is read once, in front of a barrier: thread 0 rewrites it further down)
+  if (threadIdx.x == 0) { s_rec[0] = b.tiles[t].flags; s_rec[1] = b.tiles[t].kind; s_rec[2] = b.tiles[t].retry; }
+  __syncthreads();
+  if (s_rec[0]) return;
+  const bool blocks = s_rec[1] == kTmbKindBlocks8, retry = blocks && s_rec[2];
+  u32 nBytes16 = 0;
+  if (retry) nBytes16 = blockScanInPlace(b.blockOff16 + (u64)t * g.pos16Stride, (u32)(((g.nRows + 15) / 16) * ((g.nCols + 15) / 16)), s_scan);
+  if (threadIdx.x != 0) return;
+  TmbTile& ti = b.tiles[t];
+  if (blocks)
+  {
+    if (retry && nBytes16 <= ti.nBytesTiling) { ti.kind = kTmbKindBlocks16; ti.mbSize = 16u; ti.nBytesTiling = nBytes16; }
+    const u64 oneSweep = (u64)tb * ti.numValid;
+    if (oneSweep <= (u64)ti.nBytesTiling) { ti.kind = kTmbKindOneSweep; ti.blobSize = ti.dataBegin + (u32)oneSweep; }
+    else ti.blobSize = ti.dataBegin + ti.nBytesTiling;
+  }
   if (slotBytes)
   {
     ti.offset = (firstTile + t) * slotBytes;
-    if ((u64)ti.blobSize > slotBytes) fl |= kTmbCapacity;
+    if ((u64)ti.blobSize > slotBytes) ti.flags = kTmbCapacity;
   }
-  ti.flags = fl;
 }
 
 // packed arena: the batch's blobs back to back at 16-byte aligned offsets from arenaBase on, in tile order
@@ -393,13 +505,17 @@ template<class T>
 static void tmbEncodeT(const TmbGeom& g, const BandParams& bp, double maxZErr, u32 cand, const void* dTiles, const u8* dValidBytes, u8* dArena,
                        u64 arenaBase, u64 arenaCapacity, u64 slotBytes, u64 firstTile, const TmbEncodeBuffers& b, hipStream_t st)
 {
-  const int nPos = g.nTV * g.nTH;
+  const int nPos = g.nTV * g.nTH, nPos16 = ((g.nRows + 15) / 16) * ((g.nCols + 15) / 16);
   const dim3 perTile(g.nTiles), blk(256);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_prelude<T>), perTile, blk, 0, st, g, maxZErr, cand, (const T*)dTiles, dValidBytes, b);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_blocks<T, false>), dim3((nPos + 3) / 4, g.nTiles), blk, 0, st, g, bp, (const T*)dTiles, (u8*)nullptr, b);
-  hipLaunchKernelGGL(k_tmb_decide, perTile, blk, 0, st, g, (u32)sizeof(T), slotBytes, firstTile, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_blocks<T, 8, false>), dim3((nPos + 3) / 4, g.nTiles), blk, 0, st, g, bp, (const T*)dTiles, (u8*)nullptr, b);
+  hipLaunchKernelGGL(k_tmb_decide, perTile, blk, 0, st, g, (u32)sizeof(T), b);
+  // (over the whole batch, whether a tile is marked or not: the host knows nothing yet, and does not wait to learn it)
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_blocks<T, 16, false>), dim3((nPos16 + 3) / 4, g.nTiles), blk, 0, st, g, bp, (const T*)dTiles, (u8*)nullptr, b);
+  hipLaunchKernelGGL(k_tmb_decide2, perTile, blk, 0, st, g, (u32)sizeof(T), slotBytes, firstTile, b);
   if (!slotBytes) hipLaunchKernelGGL(k_tmb_arena, dim3(1), blk, 0, st, g.nTiles, arenaBase, arenaCapacity, b);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_blocks<T, true>), dim3((nPos + 3) / 4 + 1, g.nTiles), blk, 0, st, g, bp, (const T*)dTiles, dArena, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_blocks<T, 8, true>), dim3((nPos + 3) / 4 + 1, g.nTiles), blk, 0, st, g, bp, (const T*)dTiles, dArena, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_blocks<T, 16, true>), dim3((nPos16 + 3) / 4, g.nTiles), blk, 0, st, g, bp, (const T*)dTiles, dArena, b);
   hipLaunchKernelGGL(k_tmb_checksum, perTile, blk, 0, st, dArena, b);
 }
 
@@ -421,29 +537,39 @@ void launchTmbEncode(const TmbGeom& g, const BandParams& bp, double maxZErr, u32
 // ================================================================================================
 // decode
 // ================================================================================================
+// is z a value of type T (so that (T)z means the same everywhere)?
+template<class T> __device__ __forceinline__ bool tmbIsValueOf(double z)
+{
+  if (DtOf<T>::v == DT_Double) return z == z;
+  if (DtOf<T>::v == DT_Float) return (double)(float)z == z;
+  const double lo = (DtOf<T>::v == DT_Short) ? -32768.0 : (DtOf<T>::v == DT_Int) ? -2147483648.0 : 0.0;
+  const double hi = (DtOf<T>::v == DT_Short) ? 32767.0 : (DtOf<T>::v == DT_UShort) ? 65535.0 : (DtOf<T>::v == DT_Int) ? 2147483647.0 : 4294967295.0;
+  return z >= lo && z <= hi && z == floor(z);
+}
+
 template<class T>
 __global__ void __launch_bounds__(256)
-k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ offsets, const u32* __restrict__ sizes, u8* __restrict__ validOut,
-             TmbDecodeBuffers b)
+k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ offsets, const u32* __restrict__ sizes, T* __restrict__ outAll,
+             u8* __restrict__ validOut, TmbDecodeBuffers b)
 {
   constexpr u32 TB = (u32)sizeof(T);
   __shared__ __align__(16) u8 s_bits[kTmbMaxMaskBytes + 16];
   __shared__ u16 s_nv[kTmbMaxBlocks];
   __shared__ u64 s_red[4];
+  __shared__ u32 s_w[4];
   __shared__ TmbTile s_ti;
   __shared__ u32 s_flags, s_nm;
   const u32 t = blockIdx.x;
   const u8* __restrict__ blob = arena + offsets[t];
   const u32 sizeGiven = sizes[t];
   const u32 nPix = (u32)g.tileElems, nBytes = (nPix + 7u) >> 3;
-  const u32 nPos = (u32)(g.nTV * g.nTH);
 
   if (threadIdx.x == 0)
   {
     TmbTile ti;
     memset(&ti, 0, sizeof(ti));
     u32 fl = 0, nm = 0;
-    if (sizeGiven < kHdr6 + 4u + 2u * TB + 2u) fl = kTmbHeader;
+    if (sizeGiven < kHdr6 + 4u) fl = kTmbHeader;
     else
     {
       const char magic[6] = { 'L', 'e', 'r', 'c', '2', ' ' };
@@ -457,25 +583,49 @@ k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
       ti.numValid = (u32)ints[5];
       ti.blobSize = (u32)ints[7];
       ti.maxZErr = dbl[0]; ti.zMin = dbl[1]; ti.zMax = dbl[2];
-      if (ints[0] != kCodecVersion || ints[2] != g.nRows || ints[3] != g.nCols || ints[4] != 1 || ints[5] <= 0 || (u32)ints[5] > nPix || ints[6] != 8
-        || ints[7] < (int)(kHdr6 + 4u + 2u * TB + 2u) || (u32)ints[7] > sizeGiven || ints[8] != g.dt || ints[9] != 0 || (flagBytes & 0xFFu) != 0u)
+      if (ints[0] != kCodecVersion || ints[2] != g.nRows || ints[3] != g.nCols || ints[4] != 1 || ints[5] < 0 || (u32)ints[5] > nPix
+        || (ints[6] != 8 && ints[6] != 16) || ints[7] < (int)(kHdr6 + 4u) || (u32)ints[7] > sizeGiven || ints[8] != g.dt || ints[9] != 0 || (flagBytes & 0xFFu) != 0u)
         fl = kTmbHeader;
-      // (an error bound of 0 is the lossless float mode or a stream this decoder has not been pinned on; NaN fails every comparison)
-      if (!(ti.maxZErr > 0) || !(ti.maxZErr < 1e300) || !(ti.zMin < ti.zMax)) fl = kTmbHeader;
       if (!fl)
       {
         nm = (u32)getBytes(blob + kHdr6, 4);
-        const bool allValid = ti.numValid == nPix;
-        if (allValid ? nm != 0u : (nm < 2u || nm > ti.blobSize)) fl = kTmbHeader;
-        else if ((u64)kHdr6 + 4u + nm + 2u * TB + 1u >= (u64)ti.blobSize) fl = kTmbHeader;
+        const bool noStream = ti.numValid == nPix || ti.numValid == 0u;
+        if (noStream ? nm != 0u : (nm < 2u || nm > ti.blobSize)) fl = kTmbHeader;
+        else if (ti.numValid == 0u)
+        {
+          // no valid pixel: nothing may follow the mask section's length (Lerc2.cpp:235-241); range and error bound are not asked
+          ti.kind = kTmbKindEmpty;
+          if (ti.blobSize != kHdr6 + 4u) fl = kTmbHeader;
+        }
+        else if (ti.zMin == ti.zMax)
+        {
+          // every valid pixel is (T)zMin (Lerc2.cpp:255, FillConstImage): nothing may follow the mask section
+          ti.kind = kTmbKindConst;
+          if ((u64)ti.blobSize != (u64)kHdr6 + 4u + nm || !tmbIsValueOf<T>(ti.zMin)) fl = kTmbHeader;
+          ti.minBits = typedBits(ti.zMin, g.dt);
+        }
+        else if (!(ti.zMin < ti.zMax) || (u64)kHdr6 + 4u + nm + 2u * TB + 1u >= (u64)ti.blobSize) fl = kTmbHeader;    // (NaN fails every comparison)
         else
         {
           const u8* r = blob + kHdr6 + 4u + nm;
           ti.minBits = getBytes(r, (int)TB); ti.maxBits = getBytes(r + TB, (int)TB);
-          if (ti.minBits == ti.maxBits || r[2 * TB] != 0) fl = kTmbHeader;    // constant, one sweep
           ti.dataBegin = kHdr6 + 4u + nm + 2u * TB + 1u;
-          ti.rleLen = nm;
+          if (ti.minBits == ti.maxBits) fl = kTmbHeader;    // (constant by its ranges)
+          else if (r[2 * TB] == 1)
+          {
+            // one sweep: the blob ends behind numValid raw values (Lerc2::ReadDataOneSweep); the mask's own count is compared below
+            ti.kind = kTmbKindOneSweep;
+            if ((u64)ti.dataBegin + (u64)ti.numValid * TB != (u64)ti.blobSize) fl = kTmbHeader;
+          }
+          else if (r[2 * TB] != 0) fl = kTmbHeader;
+          else
+          {
+            ti.kind = ints[6] == 16 ? kTmbKindBlocks16 : kTmbKindBlocks8;
+            // (an error bound of 0 is the lossless float mode or a stream this decoder has not been pinned on)
+            if (!(ti.maxZErr > 0) || !(ti.maxZErr < 1e300)) fl = kTmbHeader;
+          }
         }
+        ti.rleLen = nm;
       }
     }
     ti.flags = fl;
@@ -483,7 +633,7 @@ k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
   }
   __syncthreads();
   if (s_flags) { if (threadIdx.x == 0) b.tiles[t] = s_ti; return; }
-  const u32 blobEnd = s_ti.blobSize, nm = s_nm;
+  const u32 blobEnd = s_ti.blobSize, nm = s_nm, kind = s_ti.kind;
 
   // ---- Fletcher32 over blob[14 .. blobSize)
   {
@@ -496,11 +646,11 @@ k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
     }
   }
 
-  // ---- the mask: all ones, or the run-length stream expanded (rleDecode, codec_common.cpp: what it does not fill stays zero)
+  // ---- the mask: all ones, all zeros, or the run-length stream expanded (rleDecode, codec_common.cpp: what it does not fill stays zero)
   const bool allValid = s_ti.numValid == nPix;
   for (u32 i = threadIdx.x; i < nBytes + 16u; i += 256u) s_bits[i] = (allValid && i < nBytes) ? (u8)0xFF : (u8)0;
   __syncthreads();
-  if (!allValid && threadIdx.x == 0)
+  if (!allValid && kind != kTmbKindEmpty && threadIdx.x == 0)
   {
     const u8* src = blob + kHdr6 + 4u;
     u32 left = nm, at = 0, sp = 0;
@@ -522,20 +672,59 @@ k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
   __syncthreads();
   if (s_flags) { if (threadIdx.x == 0) { s_ti.flags = s_flags; b.tiles[t] = s_ti; } return; }
 
-  // ---- valid pixels per block, the bit mask for the block kernel, the caller's valid bytes
-  for (u32 pos = threadIdx.x; pos < nPos; pos += 256u)
+  T* __restrict__ out = outAll + (u64)t * g.tileElems;
+  if (kind == kTmbKindConst || kind == kTmbKindOneSweep)
   {
-    const u32 it = pos / (u32)g.nTH, jt = pos - it * (u32)g.nTH;
-    const u32 i1 = min((u32)g.nRows, it * 8u + 8u), j1 = min((u32)g.nCols, jt * 8u + 8u);
-    u32 n = 0;
-    for (u32 i = it * 8u; i < i1; i++)
-      for (u32 j = jt * 8u; j < j1; j++) { const u32 k = i * (u32)g.nCols + j; n += (s_bits[k >> 3] >> (7u - (k & 7u))) & 1u; }
-    s_nv[pos] = (u16)n;
+    // ---- pixels by the mask alone.  A mask that names another number of valid pixels than the header does is the single-blob
+    // decoder's business (it asks the mask, codec_decode.cpp): nothing has been written yet.
+    const u8* __restrict__ raw = blob + s_ti.dataBegin;
+    const u64 constBits = s_ti.minBits;
+    const bool sweep = kind == kTmbKindOneSweep;
+    u32 cnt = 0;
+    for (u32 by = threadIdx.x; by < nBytes; by += 256u)
+    {
+      u32 m = s_bits[by];
+      if (8u * by + 8u > nPix) m &= (0xFF00u >> (nPix - 8u * by)) & 0xFFu;
+      cnt += (u32)__popc(m);
+    }
+    if ((u32)blockSum((u64)cnt, s_red) != s_ti.numValid)
+    {
+      if (threadIdx.x == 0) { s_ti.flags = kTmbHeader; b.tiles[t] = s_ti; }
+      return;
+    }
+    tmbRankedSweep(s_bits, nPix, s_w, [&](u32 k, bool valid, u32 rank)
+    {
+      const u64 bits = !valid ? 0ull : sweep ? getBytes(raw + (u64)rank * TB, (int)TB) : constBits;    // (0 where nothing is valid, like FillConstImage)
+      T v; memcpy(&v, &bits, sizeof(T));
+      out[k] = v;
+    });
   }
+  else if (kind == kTmbKindEmpty)
+    for (u32 k = threadIdx.x; k < nPix; k += 256u) out[k] = T(0);
+
+  // ---- the bit mask for the block kernel, the caller's valid bytes
   u8* __restrict__ bitsOut = b.bits + (u64)t * g.bitStride;
   for (u32 i = threadIdx.x; i < nBytes; i += 256u) bitsOut[i] = s_bits[i];
   u8* __restrict__ vOut = validOut + (u64)t * g.tileElems;
   for (u32 k = threadIdx.x; k < nPix; k += 256u) vOut[k] = (u8)((s_bits[k >> 3] >> (7u - (k & 7u))) & 1u);
+  if (kind != kTmbKindBlocks8 && kind != kTmbKindBlocks16)
+  {
+    if (threadIdx.x == 0) b.tiles[t] = s_ti;
+    return;
+  }
+
+  // ---- valid pixels per block
+  const u32 MB = kind == kTmbKindBlocks16 ? 16u : 8u;
+  const u32 nTV = ((u32)g.nRows + MB - 1u) / MB, nTH = ((u32)g.nCols + MB - 1u) / MB, nPos = nTV * nTH;
+  for (u32 pos = threadIdx.x; pos < nPos; pos += 256u)
+  {
+    const u32 it = pos / nTH, jt = pos - it * nTH;
+    const u32 i1 = min((u32)g.nRows, it * MB + MB), j1 = min((u32)g.nCols, jt * MB + MB);
+    u32 n = 0;
+    for (u32 i = it * MB; i < i1; i++)
+      for (u32 j = jt * MB; j < j1; j++) { const u32 k = i * (u32)g.nCols + j; n += (s_bits[k >> 3] >> (7u - (k & 7u))) & 1u; }
+    s_nv[pos] = (u16)n;    // (at most 256)
+  }
   __syncthreads();
 
   // ---- the walk: block k + 1 starts where block k ends; a block's length follows from its header and its valid count
@@ -543,19 +732,19 @@ k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
   {
     BandParams p;
     memset(&p, 0, sizeof(p));
-    p.nRows = g.nRows; p.nCols = g.nCols; p.nDepth = 1; p.mb = 8; p.nTV = g.nTV; p.nTH = g.nTH; p.dt = g.dt; p.version = kCodecVersion;
+    p.nRows = g.nRows; p.nCols = g.nCols; p.nDepth = 1; p.mb = (int)MB; p.nTV = (int)nTV; p.nTH = (int)nTH; p.dt = g.dt; p.version = kCodecVersion;
     u32* __restrict__ table = b.blockOff + (u64)t * g.posStride;
     const u32 pattern = 14u;    // codec >= 5: bit 2 of the flag is the difference flag
     u32 pos = s_ti.dataBegin, fl = 0;
     for (u32 k = 0; k < nPos; k++)
     {
       table[k] = pos;
-      const u32 it = k / (u32)g.nTH, jt = k - it * (u32)g.nTH;
-      const u32 nElem = min(8u, (u32)g.nRows - it * 8u) * min(8u, (u32)g.nCols - jt * 8u);
+      const u32 it = k / nTH, jt = k - it * nTH;
+      const u32 nElem = min(MB, (u32)g.nRows - it * MB) * min(MB, (u32)g.nCols - jt * MB);
       BlkInfo bi;
       const int rc = parseBlock<(int)TB>(blob, pos, blobEnd, p, (int)s_nv[k], nElem, bi);
       // (a block of a position without valid pixels is the one "all zero" byte)
-      if (rc != 0 || bi.len == 0 || (((u32)bi.flag >> 2) & pattern) != (jt & pattern) || bi.diff || (s_nv[k] == 0 && bi.mode != 2)) { fl = kTmbBlocks; break; }
+      if (rc != 0 || bi.len == 0 || (((u32)bi.flag >> 2) & pattern) != (((jt * MB) >> 3) & pattern) || bi.diff || (s_nv[k] == 0 && bi.mode != 2)) { fl = kTmbBlocks; break; }
       pos += bi.len;
     }
     if (!fl && pos != blobEnd) fl = kTmbBlocks;
@@ -565,41 +754,54 @@ k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
   }
 }
 
-// a wave per block: k_decode_tiles (tile_decode.hip) for one value a pixel, with the tile's own blob, mask and header values
-template<class T>
+// a wave per block: k_decode_tiles (tile_decode.hip) for one value a pixel, with the tile's own blob, mask and header values; lane l
+// holds elements l, l + 64, ... of the block.  One launch per block size over the whole batch; a tile of another kind is left alone.
+template<class T, int MB>
 __global__ void __launch_bounds__(256)
 k_tmbd_blocks(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ offsets, T* __restrict__ outAll, TmbDecodeBuffers b)
 {
+  constexpr int E = MB * MB / 64;
   __shared__ u32 s_lut[4][256];
   __shared__ __align__(16) u8 s_head[4][64];
   const u32 t = blockIdx.y;
   if (b.tiles[t].flags & ~kTmbSibling) return;    // (whatever the parse kernel raised; a sibling wave's kTmbSibling: nothing to gain from leaving)
+  if (b.tiles[t].kind != (MB == 8 ? kTmbKindBlocks8 : kTmbKindBlocks16)) return;
   const int w = waveId(), lane = laneId();
   const int pos = (int)blockIdx.x * 4 + w;
-  if (pos >= g.nTV * g.nTH) return;
+  const int nTV = (g.nRows + MB - 1) / MB, nTH = (g.nCols + MB - 1) / MB;
+  if (pos >= nTV * nTH) return;
   const u32 blobEnd = b.tiles[t].blobSize;
   const u32 nPix = (u32)g.tileElems;
   BandParams p;
   memset(&p, 0, sizeof(p));
-  p.nRows = g.nRows; p.nCols = g.nCols; p.nDepth = 1; p.mb = 8; p.nTV = g.nTV; p.nTH = g.nTH; p.dt = g.dt; p.version = kCodecVersion;
+  p.nRows = g.nRows; p.nCols = g.nCols; p.nDepth = 1; p.mb = MB; p.nTV = nTV; p.nTH = nTH; p.dt = g.dt; p.version = kCodecVersion;
   p.allValid = (b.tiles[t].numValid == nPix) ? 1 : 0;
   p.invScale = 2 * b.tiles[t].maxZErr;
   const double zMax = b.tiles[t].zMax;
   const u8* __restrict__ blob = arena + offsets[t];
   const u8* __restrict__ maskBits = b.bits + (u64)t * g.bitStride;
   T* __restrict__ out = outAll + (u64)t * g.tileElems;
-  const int it = pos / g.nTH, jt = pos - it * g.nTH;
-  const int i0 = it * 8, j0 = jt * 8;
-  const int tileH = min(8, g.nRows - i0), tileW = min(8, g.nCols - j0);
+  const int it = pos / nTH, jt = pos - it * nTH;
+  const int i0 = it * MB, j0 = jt * MB;
+  const int tileH = min(MB, g.nRows - i0), tileW = min(MB, g.nCols - j0);
   const int nElem = tileH * tileW;
   const u64 lt = laneMaskLt();
 
-  const bool inb = lane < nElem;
-  const int r = inb ? lane / tileW : 0, c = inb ? lane - r * tileW : 0;
-  const i64 px = (i64)(i0 + r) * g.nCols + (j0 + c);
-  const bool valid = inb && (p.allValid || maskBit(maskBits, px));
-  const u64 bal = __ballot(valid);
-  const int rank = __popcll(bal & lt), nValid = __popcll(bal);
+  int rank[E];
+  i64 px[E];
+  int nValid = 0;
+#pragma unroll
+  for (int k = 0; k < E; k++)
+  {
+    const int e = k * 64 + lane;
+    const bool inb = e < nElem;
+    const int r = inb ? e / tileW : 0, c = inb ? e - r * tileW : 0;
+    px[k] = inb ? (i64)(i0 + r) * g.nCols + (j0 + c) : -1;
+    const bool valid = inb && (p.allValid || maskBit(maskBits, px[k]));
+    const u64 bal = __ballot(valid);
+    rank[k] = valid ? nValid + __popcll(bal & lt) : -1;
+    nValid += __popcll(bal);
+  }
 
   const u32 off = b.blockOff[(u64)t * g.posStride + pos];
   s_head[w][lane] = ((u64)off + (u64)lane < (u64)blobEnd) ? blob[(u64)off + lane] : (u8)0;
@@ -622,30 +824,34 @@ k_tmbd_blocks(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ o
       waveSync();
     }
     bool badIdx = false;
-    T val = T(0);
-    if (valid)
+#pragma unroll
+    for (int k = 0; k < E; k++)
     {
-      if (bi.mode == 2) val = T(0);
-      else if (bi.mode == 0)
+      T val = T(0);
+      if (rank[k] >= 0)
       {
-        const u64 bits = getBytes(blob + off + 1 + (u64)rank * sizeof(T), (int)sizeof(T));
-        memcpy(&val, &bits, sizeof(T));
-      }
-      else if (bi.mode == 3) val = (T)offset;
-      else
-      {
-        u32 q;
-        if (!bi.lut) q = unstuffElement(blob, payloadBit, (u32)rank, bi.nb, bi.cnt, blobEnd, p.version);
+        if (bi.mode == 2) val = T(0);
+        else if (bi.mode == 0)
+        {
+          const u64 bits = getBytes(blob + off + 1 + (u64)rank[k] * sizeof(T), (int)sizeof(T));
+          memcpy(&val, &bits, sizeof(T));
+        }
+        else if (bi.mode == 3) val = (T)offset;
         else
         {
-          const u32 ix = unstuffElement(blob, idxBit, (u32)rank, nbIdx, bi.cnt, blobEnd, p.version);
-          if (ix > bi.nLut) { badIdx = true; q = 0; } else q = s_lut[w][ix];
+          u32 q;
+          if (!bi.lut) q = unstuffElement(blob, payloadBit, (u32)rank[k], bi.nb, bi.cnt, blobEnd, p.version);
+          else
+          {
+            const u32 ix = unstuffElement(blob, idxBit, (u32)rank[k], nbIdx, bi.cnt, blobEnd, p.version);
+            if (ix > bi.nLut) { badIdx = true; q = 0; } else q = s_lut[w][ix];
+          }
+          const double z = offset + (double)q * p.invScale;
+          val = (T)(z < zMax ? z : zMax);    // std::min(z, zMax)
         }
-        const double z = offset + (double)q * p.invScale;
-        val = (T)(z < zMax ? z : zMax);    // std::min(z, zMax)
       }
+      if (px[k] >= 0) out[px[k]] = val;
     }
-    if (inb) out[px] = val;
     failed = __any(badIdx);
   }
   if (failed && lane == 0) atomicOr(&b.tiles[t].flags, kTmbSibling);
@@ -655,9 +861,10 @@ template<class T>
 static void tmbDecodeT(const TmbGeom& g, const u8* dArena, const u64* dOffsets, const u32* dSizes, void* dTiles, u8* dValidBytes,
                        const TmbDecodeBuffers& b, hipStream_t st)
 {
-  const int nPos = g.nTV * g.nTH;
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_parse<T>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, dSizes, dValidBytes, b);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_blocks<T>), dim3((nPos + 3) / 4, g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, (T*)dTiles, b);
+  const int nPos = g.nTV * g.nTH, nPos16 = ((g.nRows + 15) / 16) * ((g.nCols + 15) / 16);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_parse<T>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, dSizes, (T*)dTiles, dValidBytes, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_blocks<T, 8>), dim3((nPos + 3) / 4, g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, (T*)dTiles, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_blocks<T, 16>), dim3((nPos16 + 3) / 4, g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, (T*)dTiles, b);
 }
 
 void launchTmbDecode(const TmbGeom& g, const u8* dArena, const u64* dOffsets, const u32* dSizes, void* dTiles, u8* dValidBytes,

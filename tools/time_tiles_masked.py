@@ -7,26 +7,30 @@ minus salt holes; float32 at MaxZError 0.01 and uint16 lossless), all device res
       on the same context
   (c) for scale: the unmasked batch calls on the same pixels, masks dropped
 
-Median of REPS repetitions after a warm-up, HIP events around the calls, plus a wall-clock figure for the whole run.  Writes
-profiles/tiles_masked_time.txt.  Run it under a time limit of its own:  timeout -k 10 600 python tools/time_tiles_masked.py
+Median of REPS repetitions after a warm-up with the interquartile range beside it, HIP events around the calls, plus a wall-clock
+figure for the whole run.  Writes profiles/tiles_masked_time.txt (or into TILES_MASKED_OUT).  Run it under a time limit of its own:
+    timeout -k 10 600 python tools/time_tiles_masked.py [--parent-lib lerc_amd/csrc/_var/parent.so]
+--parent-lib: a library built from the parent commit (REV=HEAD~1 tools/build_variant.sh parent).  The script then measures that
+library and this build in a fresh child process each (itself with --measure; the parent through LERC_AMD_LIBRARY), writes both sets
+of lines, the ratios parent / this build of (a) and the hand-back counts.  The pass line of that comparison: for both kinds and both
+directions the ratio exceeds 1 by more than three times the larger relative interquartile range of the two runs.
 """
 import ctypes as ct
+import json
 import os
 import statistics
+import subprocess
 import sys
 import time
 
-import numpy as np
-import torch
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from lerc_amd import api, synth    # noqa: E402
 
 REPS = int(os.environ.get("REPS", "21"))
 
 
 def timed(fn, reps=REPS, warm=2):
+    import torch
     for _ in range(warm):
         fn()
     ms = []
@@ -38,10 +42,14 @@ def timed(fn, reps=REPS, warm=2):
         b.record()
         torch.cuda.synchronize()
         ms.append(a.elapsed_time(b))
-    return statistics.median(ms)
+    q = statistics.quantiles(ms, n=4)
+    return statistics.median(ms), q[2] - q[0]
 
 
-def run(kind, lines):
+def run(kind, lines, figures):
+    import numpy as np
+    import torch
+    from lerc_amd import api, synth
     tiles_np, masks_np, e = synth.island(kind)
     n, r, c = tiles_np.shape
     item = tiles_np.itemsize
@@ -100,12 +108,15 @@ def run(kind, lines):
     lines.append("%s, %d tiles of %d x %d, MaxZError %g (%.1f Mpixel); median of %d, ms" % (kind, n, r, c, e, mp, REPS))
     lines.append("  one batch: %d tiles encoded by the batch's launches, %d one by one; %d / %d decoded" %
                  (c1[0] - c0[0], c1[1] - c0[1], c1[2] - c0[2], c1[3] - c0[3]))
-    lines.append("  (a) masked batch calls            encode %8.3f   decode %8.3f" % res["a"])
-    lines.append("  (b) one call per tile, nMasks = 1 encode %8.3f   decode %8.3f" % res["b"])
-    lines.append("  (c) unmasked batch, masks dropped encode %8.3f   decode %8.3f" % res["c"])
+    iqr = {k: (v[0][1], v[1][1]) for k, v in res.items()}
+    res = {k: (v[0][0], v[1][0]) for k, v in res.items()}
+    for name, text in (("a", "(a) masked batch calls           "), ("b", "(b) one call per tile, nMasks = 1"), ("c", "(c) unmasked batch, masks dropped")):
+        lines.append("  %s encode %8.3f (iqr %.3f)   decode %8.3f (iqr %.3f)" % (text, res[name][0], iqr[name][0], res[name][1], iqr[name][1]))
     lines.append("  (b)/(a): encode %.2f, decode %.2f   (pass line: >= 1.1 each)" % (res["b"][0] / res["a"][0], res["b"][1] / res["a"][1]))
     lines.append("  (a)/(c): encode %.2f, decode %.2f" % (res["a"][0] / res["c"][0], res["a"][1] / res["c"][1]))
     ok = res["b"][0] / res["a"][0] >= 1.1 and res["b"][1] / res["a"][1] >= 1.1
+    figures[kind] = {"encode": {"median": res["a"][0], "iqr": iqr["a"][0]}, "decode": {"median": res["a"][1], "iqr": iqr["a"][1]},
+                     "single": [c1[1] - c0[1], c1[3] - c0[3]]}
     # where the time of (a) goes, by profile group
     codec.lib.lerc_amd_profile_enable.argtypes = [ct.c_void_p, ct.c_int]
     codec.lib.lerc_amd_profile_read.argtypes = [ct.c_void_p, ct.c_char_p, ct.c_int, ct.c_int]
@@ -122,15 +133,54 @@ def run(kind, lines):
     return ok
 
 
-def main():
+def measure(label):
+    """one build, this process -> (lines, figures of (a), (b)/(a) line met)"""
+    import torch
     assert torch.cuda.is_available(), "needs a GPU"
     t0 = time.time()
-    lines = ["masked tile batches on the island mosaic -- %s" % torch.cuda.get_device_name(0)]
+    lines = ["masked tile batches on the island mosaic -- %s -- %s" % (torch.cuda.get_device_name(0), label)]
+    figures = {}
     ok = True
     for kind in ("float32", "uint16"):
-        ok = run(kind, lines) and ok
+        ok = run(kind, lines, figures) and ok
     lines.append("wall clock of the whole run: %.1f s" % (time.time() - t0))
-    lines.append("pass line met: %s" % ("yes" if ok else "NO"))
+    lines.append("(b)/(a) line met: %s" % ("yes" if ok else "NO"))
+    return lines, figures, ok
+
+
+def child(label, library):
+    env = dict(os.environ)
+    if library:
+        env["LERC_AMD_LIBRARY"] = os.path.abspath(library)
+    else:
+        env.pop("LERC_AMD_LIBRARY", None)
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--measure", label], env=env, stdout=subprocess.PIPE, timeout=280, check=True)
+    return json.loads(out.stdout.decode().strip().splitlines()[-1])
+
+
+def main():
+    if "--measure" in sys.argv:
+        lines, figures, ok = measure(sys.argv[sys.argv.index("--measure") + 1])
+        print(json.dumps({"lines": lines, "figures": figures, "ok": ok}))
+        return 0
+    parent_lib = sys.argv[sys.argv.index("--parent-lib") + 1] if "--parent-lib" in sys.argv else os.environ.get("PARENT_LIB")
+    if parent_lib:
+        before, after = child("parent commit", parent_lib), child("this build", None)
+        lines = before["lines"] + [""] + after["lines"] + ["", "parent / this build, (a) masked batch calls (pass line: ratio > 1 + 3 x the larger relative iqr):"]
+        ok = True
+        for kind in ("float32", "uint16"):
+            for way in ("encode", "decode"):
+                p, t = before["figures"][kind][way], after["figures"][kind][way]
+                ratio = p["median"] / t["median"]
+                rel = max(p["iqr"] / p["median"], t["iqr"] / t["median"])
+                met = ratio > 1 + 3 * rel
+                ok = ok and met
+                lines.append("  %-8s %s: %8.3f / %8.3f = %6.2f   larger relative iqr %.4f   line 1 + 3 x = %.3f   %s"
+                             % (kind, way, p["median"], t["median"], ratio, rel, 1 + 3 * rel, "met" if met else "NOT MET"))
+            lines.append("  %-8s tiles one by one (encode, decode): parent %s, this build %s" % (kind, before["figures"][kind]["single"], after["figures"][kind]["single"]))
+        lines.append("pass line met: %s" % ("yes" if ok else "NO"))
+    else:
+        lines, _, ok = measure("this build")
     text = "\n".join(lines) + "\n"
     print(text)
     out_dir = os.environ.get("TILES_MASKED_OUT", os.path.join(ROOT, "profiles"))
