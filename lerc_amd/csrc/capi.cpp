@@ -24,8 +24,7 @@ struct AsyncOp
   EncodeRequest er;
   DecodeRequest dr;
   bool streamed = false;    // its streaming kernels and the copy of their verdict are on the stream
-  int form = 0;             // a decode: which streaming form (DecodeRequest::maxForm)
-  u32 epoch = 0;
+  StreamTicket launch;      // a decode: what was enqueued (its verdict is judged against this)
   bool done = false;
   u32 status = kOk, bytes = 0;
 };
@@ -208,7 +207,7 @@ lerc_status decodeHost(const unsigned char* blob, unsigned blobSize, int nMasks,
   rq.hBlob = blob; rq.blobSize = blobSize; rq.dt = (int)dataType; rq.nDepth = nDepth; rq.nCols = nCols; rq.nRows = nRows;
   rq.nBands = nBands; rq.nMasks = nMasks; rq.dOut = dOut; rq.dValidBytes = dMask;
   rq.hUsesNoData = pUsesNoData; rq.hNoDataValues = noDataValues;
-  bool triedOne = false;
+  StreamTicket tried;    // (form kFormGeneral: nothing enqueued -- no form has refused the blob, nothing was written)
   // What the streaming kernels can take -- the header says so: one band, every pixel valid, 8 x 8 blocks, nDepth 1 -- goes
   // up, through the kernels and back in one go: upload, kernels, verdict and the pixels' way back are enqueued together
   // and this thread waits once (two waits and the gap between them are a quarter of a small raster's call).
@@ -225,16 +224,15 @@ lerc_status decodeHost(const unsigned char* blob, unsigned blobSize, int nMasks,
       {
         DecodeRequest rs = rq;
         rs.hBlob = nullptr; rs.dBlob = dBlob;
-        bool handled = false, tried = false;
+        bool handled = false;
         const u32 src = decodeSpeculativeToHost(ctx, rs, pData, outBytes, nMasks ? pValidBytes : nullptr, maskBytes, handled, tried);
         if (src != kOk) return src;
         if (handled) return kOk;
-        triedOne = tried;    // (nothing enqueued: no form has refused the blob, nothing was written)
       }
     }
   }
-  if (triedOne) rq.maxForm = ctx.lastStreamForm - 1;    // (that streaming form has just refused this blob)
-  if (rq.maxForm <= 0) rq.noStreaming = true;
+  const bool triedOne = tried.form > kFormGeneral;
+  if (triedOne) rq.startAt(ctx.tiers.below(tried.form, tried.shape));    // (that streaming form has just refused this blob)
   const u32 rc = decodeDevice(ctx, rq);
   if (rc != kOk)
   {
@@ -514,7 +512,7 @@ void completeAll(lerc_amd_context* h)
         op.bytes = op.er.dOut ? written : needed;
         rerun = redo;
       }
-      else rerun = !decodeStreamingVerdict(ctx, slot, op.epoch, nullptr, op.form, op.dr.dt);
+      else rerun = !decodeStreamingVerdict(ctx, slot, op.launch);
       if (!rerun) { if (!op.isEncode) ctx.pathCount[2]++; op.done = true; continue; }
     }
     rerun = true;
@@ -537,7 +535,7 @@ void completeAll(lerc_amd_context* h)
           if (getBlobInfo(head, sizeof(head), info) == kOk && info.blobSize >= 70 && info.blobSize <= op.dr.blobSize) op.dr.blobSize = info.blobSize;
         }
       }
-      if (op.streamed) { op.dr.maxForm = op.form - 1; op.dr.noStreaming = op.dr.maxForm <= 0; }    // (that streaming form has just refused this blob)
+      if (op.streamed) op.dr.startAt(ctx.tiers.below(op.launch.form, op.launch.shape));    // (that streaming form has just refused this blob)
       op.status = decodeDevice(ctx, op.dr);
       if (op.status == kFailed) wipeDecodeOutputs(ctx, op.dr);
     }
@@ -594,8 +592,7 @@ lerc_status lerc_amd_decode_device_async(lerc_amd_context* h, const unsigned cha
   rq.nBands = nBands; rq.nMasks = nMasks; rq.dOut = dData; rq.dValidBytes = dValidBytes;
   const unsigned t = pushOp(h, op);
   AsyncOp& q = h->ops.back();
-  q.streamed = decodeEnqueueStreaming(h->ctx, q.dr, h->ctx.asyncSlot(t), q.epoch);
-  q.form = h->ctx.lastStreamForm;
+  q.streamed = decodeEnqueueStreaming(h->ctx, q.dr, h->ctx.asyncSlot(t), q.launch);
   if (!q.streamed) completeAll(h);
   *ticket = t;
   return kOk;
@@ -736,7 +733,7 @@ void lerc_amd_path_counters(lerc_amd_context* h, unsigned long long out[4])
 void lerc_amd_decode_forms(lerc_amd_context* h, unsigned long long out[4])
 {
   if (!h) h = threadHandle();
-  for (int i = 0; i < 4; i++) out[i] = h ? h->ctx.formCount[i] : 0;
+  for (int i = 0; i < 4; i++) out[i] = h ? h->ctx.tiers.formCount[i] : 0;
 }
 
 unsigned int lerc_amd_gather_blobs(lerc_amd_context* h, void* ncclComm, int root, const void* dMessage, unsigned long long nBytes,
@@ -753,7 +750,7 @@ unsigned int lerc_amd_gather_blobs(lerc_amd_context* h, void* ncclComm, int root
 void lerc_amd_decode_refusals(lerc_amd_context* h, unsigned long long out[4])
 {
   if (!h) h = threadHandle();
-  for (int i = 0; i < 4; i++) out[i] = h ? h->ctx.refusalCount[i] : 0;
+  for (int i = 0; i < 4; i++) out[i] = h ? h->ctx.tiers.refusalCount[i] : 0;
 }
 
 unsigned int lerc_amd_mask_rle_device(lerc_amd_context* h, const unsigned char* dBits, unsigned int nBytes, unsigned char* dOut,

@@ -33,6 +33,66 @@ void rleEncode(const u8* src, size_t n, std::vector<u8>& out);
 bool rleEncodeWhenReady(const u8* b, size_t n, const std::function<bool()>& ready, std::vector<u8>& out);    // (pieces by several threads, started before the bytes are there)
 bool rleDecode(const u8* src, size_t n, u8* dst, size_t dstSize, size_t* written = nullptr);    // (what the stream does not fill stays as it was)
 
+// ---- which decoder takes a band (codec_decode.cpp holds the rules; DESIGN.md 4.2c states them in one place)
+// The streaming forms, fastest first; each follows streams the one above it cannot, and every one checks what it decodes, so a
+// wrong choice costs launches, never pixels.  (DecodeRequest::maxForm and lerc_amd_decode_forms speak in these numbers.)
+enum DecodeForm : int
+{
+  kFormGeneral = 0,      // no streaming kernels: header read on the host, general discovery
+  kFormTwoLaunch = 1,    // discovery + decode as two launches over chunks of 2 KiB (tile_fast_decode.hip)
+  kFormWalk = 2,         // the walking one-launch decoder (tile_fast_decode_one.hip)
+  kFormScan = 3,         // the scanning decoder, counts late (tile_fast_decode_scan.hip)
+  kFormScanEarly = 4     // the scanning decoder with early counts
+};
+
+struct RasterShape
+{
+  int dt = -1, nRows = 0, nCols = 0;    // dt < 0: of any type
+  bool covers(const RasterShape& o) const { return nRows == o.nRows && nCols == o.nCols && (dt < 0 || dt == o.dt); }
+};
+
+// "The next n decodes of shape S do X": the bands of one job are alike, another job's are not.
+struct ShapeWindow
+{
+  RasterShape shape;
+  u32 n = 0;    // calls left (the size guess: the bytes; 0: nothing is remembered)
+  void open(const RasterShape& s, u32 count) { shape = s; n = count; }
+  bool holds(const RasterShape& s) const { return n > 0 && shape.covers(s); }
+  bool take(const RasterShape& s) { if (!holds(s)) return false; n--; return true; }    // one call of the window used up
+};
+
+// What one launch of the streaming decoders was, kept by whoever waits for its verdict (several may be in flight on a stream):
+// a verdict is judged against this, never against what the context enqueued last.
+struct StreamTicket
+{
+  int form = kFormGeneral;
+  u32 epoch = 0;            // the value the launch's flags are raised with (tile_fast.h)
+  RasterShape shape;
+  u32 gridBytes = 0;        // blob bytes the scanning decoder's launch held pieces for (0: not that decoder)
+};
+
+// The tier memory of a context.  pick / below choose, judge is the only place that turns a verdict into memory and counters.
+struct DecodeTiers
+{
+  ShapeWindow offScan;      // keep off the scanning decoder: it has just handed a band of that shape on (kScanSkip calls, any type)
+  ShapeWindow countLate;    // the scanning decoder counts late: an early count was wrong (lateSpan calls, any type)
+  ShapeWindow notBlind;     // go to the header-reading path at once: the header refused the last blind attempt (8 calls)
+  ShapeWindow sizeGuess;    // n = bytes of the last band of that shape the streaming kernels decoded (launchFastBands sizes a launch by it)
+  static constexpr u32 kScanSkip = 16, kScanLate = 64, kScanLateMax = 4096, kBlindSkip = 8;    // how long the windows are
+  u32 lateSpan = kScanLate; // what the next wrong early count opens countLate with (grows: 64, 256, ... 4096)
+  unsigned long long formCount[4] = { 0, 0, 0, 0 };       // lerc_amd_decode_forms: [0] masked bands whose blocks the scan found, [1 .. 3] bands / tiles decoded by that form (4 counts as 3)
+  unsigned long long refusalCount[4] = { 0, 0, 0, 0 };    // attempts thrown away (lerc_amd_decode_refusals): [0] the decode kernels refused the masked scan's block offsets, [1] the masked scan handed a band on, [2] a streaming decode tier handed a band on, [3] unused
+
+  int pick(int maxForm, const RasterShape& s);    // the form a request starts with: the highest one <= maxForm that is switched on, takes the raster and is not kept off by a window
+  int below(int form, const RasterShape& s) { return form > kFormTwoLaunch ? pick(form - 1, s) : kFormGeneral; }    // ... after `form` has refused
+  // a single band's verdict (fastBandVerdict; blobEnd: the band's size by its header).  true: decoded, checksum good
+  bool judge(const StreamTicket& t, u32 verdict, u32 blobEnd);
+  // a batch's: tiles served, and whether so many went on that the form is not for these tiles (the caller's trigger)
+  void judgeBatch(const StreamTicket& t, u32 nServed, bool manyWentOn);
+private:
+  void handedOn(const StreamTicket& t);
+};
+
 // ---- growable device workspace + stream, one per host thread (C API) or per handle (device API)
 class Context
 {
@@ -86,20 +146,8 @@ public:
   unsigned long long pathCount[4] = { 0, 0, 0, 0 };
   unsigned long long tileBatchCount[4] = { 0, 0, 0, 0 };    // tiles of batch calls (lerc_amd_tile_batch_counters): [0] encoded by the batch's own launches, [1] encoded one by one behind it, [2] / [3] the same for decodes
   bool lastDecodeStreamed = false;
-  unsigned long long formCount[4] = { 0, 0, 0, 0 };    // bands / tiles decoded by streaming form 1, 2, 3 (lerc_amd_decode_forms)
-  unsigned long long refusalCount[4] = { 0, 0, 0, 0 };    // attempts thrown away (lerc_amd_decode_refusals): [0] the decode kernels refused the masked scan's block offsets, [1] the masked scan handed a band on, [2] a streaming decode tier handed a band on, [3] unused
-  int lastStreamForm = 0;              // the form decodeEnqueueStreaming last enqueued (DecodeRequest::maxForm)
-  struct { int dt = -1, nRows = 0, nCols = 0; u32 end = 0; } scanHint;    // size of the last band the streaming kernels decoded, and its shape (see launchFastBands)
-  int lastStreamShape[3] = { -1, 0, 0 };                                 // dt, nRows, nCols of the band decodeEnqueueStreaming / decodeImpl last enqueued
-  u32 blindSkip = 0;                   // decodes of blindShape that go to the header-reading path at once (the last blind attempt was refused by the header)
-  int blindShape[3] = { -1, 0, 0 };
+  DecodeTiers tiers;                   // which streaming decoder a band starts with, and the counters of what became of it
   bool scanOffsetsBan = false;         // this call: a masked band's scan for block offsets has failed, the general discovery takes the bands
-  u32 scanLateSpan = 64;               // how many decodes the next wrong early count keeps the context on late counts (grows: 64, 256, ... 4096)
-  int scanLateRows = 0, scanLateCols = 0;    // ... and the shape of the band whose early count was wrong: the window is for bands of that shape
-  u32 scanLate = 0;                    // decodes whose scanning decoder counts late: an early count has just turned out wrong (a stream with blocks the scan does not see: the mending found them)
-  u32 lastScanGridBytes = 0;           // blob bytes the scanning decoder's last launch held pieces for (launchFastBands)
-  int scanSkipRows = 0, scanSkipCols = 0;    // ... of that shape
-  u32 scanSkip = 0;                    // decodes that keep off the scanning decoder: it has just handed a band on (a stream with blocks it cannot see)
 
   // optional per-kernel timing with HIP events on the active stream (bench.py: roofline of the dominant kernel)
   void profEnable(bool on) { m_prof = on; }
@@ -198,8 +246,8 @@ struct DecodeRequest
   void* dOut = nullptr;               // device: decoded pixels
   u8* dValidBytes = nullptr;          // device: nMasks byte masks, or nullptr
   bool noStreaming = false;            // go straight to the general kernels (a batch has already tried the streaming ones)
-  int maxForm = 4;                     // the first streaming form to try: 4 the scanning decoder with early counts, 3 the scanning decoder, 2 the walking one-launch decoder, 1 discovery + decode in
-                                       // two launches (a form that has just refused this blob hands it on with its own number less one)
+  int maxForm = kFormScanEarly;        // the first streaming form to try (DecodeForm)
+  void startAt(int form) { maxForm = form; noStreaming = form <= kFormGeneral; }    // (DecodeTiers::below of the form that has just refused this blob)
   u8* hUsesNoData = nullptr;           // host [nBands] out (lerc_decode_4D), or nullptr
   double* hNoDataValues = nullptr;
 };
@@ -212,10 +260,10 @@ u32 decodeDevice(Context& ctx, const DecodeRequest& rq);
 bool encodeEnqueueStreaming(Context& ctx, const EncodeRequest& rq, u8* slot);
 // redo: the general path has to repeat the request; else status / sizes are final
 void encodeStreamingVerdict(Context& ctx, const EncodeRequest& rq, const u8* slot, bool& redo, u32& status, u32& numBytesNeeded, u32& numBytesWritten);
-bool decodeEnqueueStreaming(Context& ctx, const DecodeRequest& rq, u8* slot, u32& epoch);
-bool decodeStreamingVerdict(Context& ctx, const u8* slot, u32 epoch, u32* bits = nullptr, int form = -1, int dt = -1);    // true: decoded, checksum good (bits: why not; form: the one that was enqueued, default the last)
+bool decodeEnqueueStreaming(Context& ctx, const DecodeRequest& rq, u8* slot, StreamTicket& ticket);
+bool decodeStreamingVerdict(Context& ctx, const u8* slot, const StreamTicket& ticket, u32* bits = nullptr);    // true: decoded, checksum good (bits: why not)
 // host-pointer calls: streaming kernels + the results' way back to the host enqueued together, one wait (rq holds a device copy of the blob)
-u32 decodeSpeculativeToHost(Context& ctx, const DecodeRequest& rq, void* hOut, size_t outBytes, u8* hMask, size_t maskBytes, bool& handled, bool& tried);    // tried: the streaming kernels were enqueued (and may have written pixels)
+u32 decodeSpeculativeToHost(Context& ctx, const DecodeRequest& rq, void* hOut, size_t outBytes, u8* hMask, size_t maskBytes, bool& handled, StreamTicket& ticket);    // ticket.form > 0: the streaming kernels were enqueued (and may have written pixels)
 u32 encodeTilesDevice(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed);
 u32 decodeTilesDevice(Context& ctx, const TilesDecodeRequest& rq);
 // the same with a validity mask per tile (codec_tiles_masked.cpp, tile_mask_batch.hip); without mask pointers they ARE the two calls above

@@ -76,27 +76,23 @@ bool readBandHeader(const BlobReader& rd, u64 off, BandDesc& b)
 static const size_t kCellParams = 0, kCellFallback = 128, kCellBytes = 192;
 static_assert(sizeof(FastDecodeParams) <= 128, "cell layout");
 
-static bool fastDecodeOneLaunch();    // the one-launch decoders (tile_fast_decode_scan.hip, tile_fast_decode_one.hip); LERC_AMD_DECODE_LAUNCHES=2: discovery + decode as two launches
-static int pickForm(Context& ctx, int maxForm, int nRows, int nCols);
-static int lowerForm(Context& ctx, int form, int nRows, int nCols) { return form > 1 ? pickForm(ctx, form - 1, nRows, nCols) : 0; }
-
 static size_t fastBandWorkspace(int nRows, int nCols, u32 sizeGiven, u32 nTiles = 1)
 {
   const FastWalkPlan wp = makeFastWalkPlan(nRows, nCols, sizeGiven, nTiles);
   const size_t perTile = (size_t)wp.nChunks * (sizeof(FastChunkRec) + (size_t)kDiscWalks * kFastListCap * 2 + 12) + (size_t)wp.nBlocks * 4
-    + (size_t)(wp.nChunks / kOneDiscChunks + 1) * 16 + (size_t)(wp.nChunks / kResolveWG + 2) * 4 + 4096 + kResolveWG * sizeof(FastChunkRec);
+    + (size_t)(wp.nChunks / kResolveWG + 2) * 4 + 4096 + kResolveWG * sizeof(FastChunkRec);
   return perTile * nTiles + (size_t)kDecodeChunks * kDiscWalks * kFastListCap * 2 + (1u << 16);
 }
 
-// Enqueues header check, discovery and decode of nTiles blobs (one band: nTiles == 1, dTileOffset == nullptr);
-// nothing is read back here.  dParams [nTiles] and dFallback [4 * nTiles] receive the verdicts; the flags in dFallback
-// are raised by writing `epoch` (tile_fast.h), so the cells need no clearing.
-// (form 3: the scanning decoder -- one launch, no walks, streams of bit-stuffed blocks; 2: the walking one-launch decoder -- short
-// walks over sub-chunks of 1 KiB; 1: discovery + decode as two launches over chunks of 2 KiB, which follow streams the others
-// cannot: more tiny blocks in a row, longer stretches without a bit-stuffed block)
-static bool launchFastBands(Context& ctx, int form, int dt, int nRows, int nCols, const u8* dBlobs, u32 sizeBound, u32 nTiles, const u64* dTileOffset,
-                            const u32* dTileSize, void* dOut, FastDecodeParams* dParams, u32* dFallback, u32 epoch, u8* hCell = nullptr)
+// Enqueues header check, discovery and decode of nTiles blobs (one band: nTiles == 1, dTileOffset == nullptr) by the form, for the
+// shape and with the epoch of ticket `t`; nothing is read back here.  dParams [nTiles] and dFallback [4 * nTiles] receive the
+// verdicts; the flags in dFallback are raised by writing the epoch (tile_fast.h), so the cells need no clearing.  t.gridBytes: what
+// the scanning decoder's launch was sized for.
+static bool launchFastBands(Context& ctx, StreamTicket& t, const u8* dBlobs, u32 sizeBound, u32 nTiles, const u64* dTileOffset,
+                            const u32* dTileSize, void* dOut, FastDecodeParams* dParams, u32* dFallback, u8* hCell = nullptr)
 {
+  const int form = t.form, dt = t.shape.dt, nRows = t.shape.nRows, nCols = t.shape.nCols;
+  const u32 epoch = t.epoch;
   hipStream_t st = ctx.activeStream();
   const FastWalkPlan fwp = makeFastWalkPlan(nRows, nCols, sizeBound, nTiles);
   const size_t nT = nTiles, sChunk = fastChunkStride(fwp.nChunks);
@@ -111,7 +107,6 @@ static bool launchFastBands(Context& ctx, int form, int dt, int nRows, int nCols
   fbuf.epoch = epoch;
   fbuf.publishEpoch = (fastTestGiveUp() & 2u) ? epoch ^ 0x5A5A5A5Au : epoch;
   fbuf.spinLimit = (fastTestGiveUp() & 2u) ? 8u : (1u << 22);
-  fbuf.discCell = nullptr;
   fbuf.testRewalk = (fastTestGiveUp() & 4u) ? 1u : 0u;
   fbuf.wgCell = fbuf.wgGroupCell = fbuf.wgAcc = nullptr;
   // The scanning decoder asks for a piece's bytes without waiting for the band header where the blob is expected to reach that far:
@@ -125,22 +120,21 @@ static bool launchFastBands(Context& ctx, int form, int dt, int nRows, int nCols
     bool fromHint = false;
     if (!dTileOffset && (u64)sizeBound * 10u >= raw * 9u)    // (as large as the raster itself: a capacity, not a size)
     {
-      const bool alike = ctx.scanHint.dt == dt && ctx.scanHint.nRows == nRows && ctx.scanHint.nCols == nCols && ctx.scanHint.end != 0u;
-      fromHint = alike;
-      const u64 guess = alike ? (u64)ctx.scanHint.end + ctx.scanHint.end / 8u + 65536u : raw / 2u;
+      const u64 last = ctx.tiers.sizeGuess.n;
+      fromHint = ctx.tiers.sizeGuess.holds(t.shape);
+      const u64 guess = fromHint ? last + last / 8u + 65536u : raw / 2u;
       spec = (u32)std::min<u64>(guess, sizeBound);
     }
     fbuf.scanSpecEnd = dTileOffset ? 0xFFFFFFFFu : spec;
     // (... and the launch itself is sized by a guess that comes from a band of this shape: LERC_AMD_SCAN_GRID=0 sizes it by what was given)
     static const bool gridByGuess = []() { const char* e = getenv("LERC_AMD_SCAN_GRID"); return !e || atoi(e) != 0; }();
-    fbuf.scanEarly = form == 4 ? 1u : 0u;
+    fbuf.scanEarly = form == kFormScanEarly ? 1u : 0u;
     fbuf.scanGridBytes = (gridByGuess && fromHint && spec < sizeBound) ? spec : 0u;
-    ctx.lastScanGridBytes = form >= 3 ? (fbuf.scanGridBytes ? fbuf.scanGridBytes : sizeBound) : 0u;
-    ctx.lastStreamShape[0] = dt; ctx.lastStreamShape[1] = nRows; ctx.lastStreamShape[2] = nCols;
+    t.gridBytes = form >= kFormScan ? (fbuf.scanGridBytes ? fbuf.scanGridBytes : sizeBound) : 0u;
   }
   fbuf.wgStride = fbuf.wgGroupStride = 0;
   // (epoch-tagged cells, never cleared: they live as long as the context and share its area with the encoder's)
-  if (form >= 2)
+  if (form >= kFormWalk)
   {
     // everything in one launch: a cell per workgroup and per group of workgroups, and the groups' checksum accumulators
     // (counters: left zero by the launch's last workgroup)
@@ -151,7 +145,7 @@ static bool launchFastBands(Context& ctx, int form, int dt, int nRows, int nCols
     fbuf.wgAcc = (u64*)ctx.persistentState(0, (nT * sGrp + 8) * 8);
     if (!fbuf.wgCell || !fbuf.wgAcc) return false;
     fbuf.recs = nullptr; fbuf.lists = nullptr; fbuf.chunkCell = fbuf.groupCell = fbuf.waveFletcher = nullptr;
-    if (form >= 3)
+    if (form >= kFormScan)
     {
       ProfScope ps(ctx, "fast_decode_scan");
       launchFastDecodeScan(dt, nRows, nCols, tb, dBlobs, sizeBound, fbuf, dOut, st);
@@ -178,50 +172,79 @@ static bool launchFastBands(Context& ctx, int form, int dt, int nRows, int nCols
   return true;
 }
 
-static bool launchFastBand(Context& ctx, int form, int dt, int nRows, int nCols, const u8* dBand, u32 sizeGiven, void* dOutBand, u8* dCell, u32 epoch,
-                           u8* hCell = nullptr)
+static bool launchFastBand(Context& ctx, StreamTicket& t, const u8* dBand, u32 sizeGiven, void* dOutBand, u8* dCell, u8* hCell = nullptr)
 {
-  return launchFastBands(ctx, form, dt, nRows, nCols, dBand, sizeGiven, 1, nullptr, nullptr, dOutBand,
-                         reinterpret_cast<FastDecodeParams*>(dCell + kCellParams), reinterpret_cast<u32*>(dCell + kCellFallback), epoch, hCell);
+  return launchFastBands(ctx, t, dBand, sizeGiven, 1, nullptr, nullptr, dOutBand, reinterpret_cast<FastDecodeParams*>(dCell + kCellParams),
+                         reinterpret_cast<u32*>(dCell + kCellFallback), hCell);
 }
 
-static bool fastDecodeOneLaunch()
+// ------------------------------------------------------------------------------------------------
+// which form takes a band: DecodeTiers (codec.h)
+// ------------------------------------------------------------------------------------------------
+static bool fastDecodeOneLaunch()    // the one-launch decoders; LERC_AMD_DECODE_LAUNCHES=2: discovery + decode as two launches only
 {
   static const bool one = []() { const char* e = getenv("LERC_AMD_DECODE_LAUNCHES"); return !e || atoi(e) != 2; }();
   return one;
 }
-
-// The streaming form a request starts with: the highest one at most maxForm that is switched on (LERC_AMD_DECODE_LAUNCHES=2: the
-// two-launch form only; LERC_AMD_DECODE_SCAN=0: not the scanning decoder), takes the raster (the scanning decoder: whole 8 x 8
-// blocks) and has not just handed a band of this context on: a stream the scanning decoder cannot follow -- many blocks that are not
-// bit-stuffed -- costs a launch before the next tier gets it, and the bands of one job are alike, so the next kScanSkip decodes
-// start one tier down.
-static const u32 kScanSkip = 16;
-// Form 4 is form 3 with EARLY counts (tile_fast_decode_scan.hip): a piece says how many blocks it holds as soon as the survivors are
-// counted.  A piece whose check or mending comes to another count -- a stream with blocks the scan does not see: constant, all zero,
-// raw -- raises a flag, and the band is decoded once more by form 3, which counts late and mends; the bands of one job are alike, so
-// the next kScanLate decodes start there.
-static const u32 kScanLate = 64;    // (the first time; four times as many after every further one, up to 4 096: Context::scanLateSpan)
 static bool scanOffsetsOn()    // (LERC_AMD_SCAN_OFFSETS=0: masked bands keep to the general discovery)
 {
   static const bool on = []() { const char* e = getenv("LERC_AMD_SCAN_OFFSETS"); return !e || atoi(e) != 0; }();
   return on;
 }
-static int pickForm(Context& ctx, int maxForm, int nRows, int nCols)
+
+// The highest form at most maxForm that is switched on (LERC_AMD_DECODE_LAUNCHES=2: the two-launch form only; LERC_AMD_DECODE_SCAN=0:
+// not the scanning decoder; LERC_AMD_SCAN_EARLY=0: no early counts), takes the raster (the scanning decoder: whole 8 x 8 blocks) and
+// is not kept off by a window: a stream the scanning decoder cannot follow -- many blocks that are not bit-stuffed -- costs a launch
+// before the next tier gets it, and the bands of one job are alike.
+int DecodeTiers::pick(int maxForm, const RasterShape& s)
 {
   static const bool scanOn = []() { const char* e = getenv("LERC_AMD_DECODE_SCAN"); return !e || atoi(e) != 0; }();
   static const bool earlyOn = []() { const char* e = getenv("LERC_AMD_SCAN_EARLY"); return !e || atoi(e) != 0; }();
-  int f = maxForm > 4 ? 4 : maxForm;
-  if (f <= 0) return 0;
-  if (!fastDecodeOneLaunch()) return 1;
-  if (f >= 3)
+  int f = std::min(maxForm, (int)kFormScanEarly);
+  if (f <= kFormGeneral) return kFormGeneral;
+  if (!fastDecodeOneLaunch()) return kFormTwoLaunch;
+  if (f >= kFormScan)
   {
-    if (!scanOn || !fastDecodeScanEligible(nRows, nCols)) f = 2;
-    else if (ctx.scanSkip > 0 && ctx.scanSkipRows == nRows && ctx.scanSkipCols == nCols) { ctx.scanSkip--; f = 2; }    // (bands of the shape that was handed on: the bands of one job are alike, another job's are not)
-    else if (f == 4 && (!earlyOn || nRows % 8 != 0 || nCols % 8 != 0)) f = 3;    // (ragged rasters count late: three count values in their filter make false survivors -- which the mending strikes, changing a count -- likelier: one piece in 3 244 of the 8190^2 raster, enough to throw every early launch away)
-    else if (f == 4 && ctx.scanLate > 0 && ctx.scanLateRows == nRows && ctx.scanLateCols == nCols) { ctx.scanLate--; f = 3; }    // (the bands of that shape: another job's rasters have streams of their own)
+    if (!scanOn || !fastDecodeScanEligible(s.nRows, s.nCols)) f = kFormWalk;
+    else if (offScan.take(s)) f = kFormWalk;
+    else if (f == kFormScanEarly && (!earlyOn || s.nRows % 8 != 0 || s.nCols % 8 != 0)) f = kFormScan;    // (ragged rasters count late: three count values in their filter make false survivors -- which the mending strikes, changing a count -- likelier: one piece in 3 244 of the 8190^2 raster, enough to throw every early launch away)
+    else if (f == kFormScanEarly && countLate.take(s)) f = kFormScan;
   }
   return f;
+}
+
+// A form's launch was thrown away for the stream's sake.  The scanning decoder: the next kScanSkip decodes of that shape start one
+// tier down.  Its early counts (a piece says how many blocks it holds as soon as the survivors are counted; one whose check or mending
+// comes to another count -- a stream with blocks the scan does not see: constant, all zero, raw -- raises a flag): the next lateSpan
+// decodes count late, which mends; four times as many after every further one.
+void DecodeTiers::handedOn(const StreamTicket& t)
+{
+  const RasterShape anyType = { -1, t.shape.nRows, t.shape.nCols };
+  if (t.form == kFormScan) offScan.open(anyType, kScanSkip);
+  if (t.form == kFormScanEarly) { countLate.open(anyType, lateSpan); lateSpan = std::min<u32>(lateSpan * 4u, kScanLateMax); }
+}
+
+bool DecodeTiers::judge(const StreamTicket& t, u32 verdict, u32 blobEnd)
+{
+  if (verdict == 0u)
+  {
+    if (t.form >= kFormTwoLaunch && t.form <= kFormScanEarly) formCount[std::min<int>(t.form, kFormScan)]++;
+    sizeGuess.open(t.shape, blobEnd);    // (the guess for the next band of that shape: launchFastBands)
+    return true;
+  }
+  if (verdictLaunchWasted(verdict)) refusalCount[2]++;
+  if (!verdictTierRefused(verdict) || t.form < kFormScan) return false;
+  // The launch was sized by the last band of this shape and this one is larger: not the stream's fault -- the guess is forgotten,
+  // the shape keeps its tier.  (t.gridBytes is what THIS band's launch held pieces for, whatever has been enqueued since.)
+  if ((verdict & kVerdictBlockCount) && t.gridBytes != 0u && fastScanNumWG(blobEnd) > fastScanNumWG(t.gridBytes)) { sizeGuess.n = 0u; return false; }
+  handedOn(t);
+  return false;
+}
+
+void DecodeTiers::judgeBatch(const StreamTicket& t, u32 nServed, bool manyWentOn)
+{
+  formCount[std::min<int>(t.form, kFormScan)] += nServed;
+  if (manyWentOn) handedOn(t);    // (sizes are exact in a batch: no guess to keep or to forget; the tiles that went on are judged one by one)
 }
 
 // reason bits of a tile's / band's four epoch tagged flag cells
@@ -232,35 +255,26 @@ static u32 fastFlagBits(const u32* cells, u32 epoch)
   return bits;
 }
 
-// what the host makes of a band's cell after the sync: 0 = decoded and checksum good, else the reason bits
-static u32 fastBandVerdict(const u8* hCell, u32 epoch)
+// what the host makes of a band's cell after the sync: 0 = decoded and checksum good, else the reason bits (tile_fast.h: kVerdict...)
+static u32 fastBandVerdict(const u8* hCell, u32 epoch, u32* blobEnd = nullptr)
 {
   FastDecodeParams hp;
   memcpy(&hp, hCell + kCellParams, sizeof(hp));
   u32 cells[4];
   memcpy(cells, hCell + kCellFallback, 16);
   u32 fb = fastFlagBits(cells, epoch);
-  if (!hp.ok) fb |= 0x100u;
-  else if (!fb && !hp.checksumOk) fb |= 0x200u;
+  if (!hp.ok) fb |= kVerdictNotOurs;
+  else if (!fb && !hp.checksumOk) fb |= kVerdictBadChecksum;
+  if (blobEnd) *blobEnd = hp.blobEnd;
   return fb;
 }
 
-// a band the streaming kernels decoded: its size is the guess for the next band of that shape (launchFastBands)
-static void noteBandSize(Context& ctx, const u8* hCell, int dt = -1)
-{
-  // (the shape from the band's own cell, the type from the request that is being answered: with several decodes of different shapes in
-  // flight, the shape the context enqueued LAST is another band's)
-  FastDecodeParams hp;
-  memcpy(&hp, hCell + kCellParams, sizeof(hp));
-  ctx.scanHint.dt = dt >= 0 ? dt : ctx.lastStreamShape[0]; ctx.scanHint.nRows = (int)hp.nRows; ctx.scanHint.nCols = (int)hp.nCols;
-  ctx.scanHint.end = hp.blobEnd;
-}
-
 // Device-resident single-band blobs: everything is enqueued before a single byte of the blob has been seen by the
-// host (the header is checked by k_fast_header); one synchronisation.  handled == false: nothing was decided,
+// host (the header is checked by the kernels); one synchronisation.  false: nothing was enqueued (ticket.form == kFormGeneral),
 // the caller goes the long way (header read, general kernels, exact status codes).
-bool decodeEnqueueStreaming(Context& ctx, const DecodeRequest& rq, u8* slot, u32& epoch)
+bool decodeEnqueueStreaming(Context& ctx, const DecodeRequest& rq, u8* slot, StreamTicket& ticket)
 {
+  ticket = StreamTicket();
   const int dt = rq.dt, nRows = rq.nRows, nCols = rq.nCols;
   if (!slot || !rq.dBlob || rq.hBlob || rq.nBands != 1 || rq.nDepth != 1 || rq.blobSize < 70 || !rq.dOut) return false;
   if (!fastDecodeEligible(dt, 6, 8, nRows, nCols, 1, true)) return false;
@@ -272,74 +286,47 @@ bool decodeEnqueueStreaming(Context& ctx, const DecodeRequest& rq, u8* slot, u32
   static_assert(64 + kCellBytes <= Context::kAsyncSlotBytes, "a verdict fits a pinned slot");
   u8* dCells = ctx.allocT<u8>(cellsBytes);
   if (!dCells) return false;
-  epoch = ctx.nextEpoch();
+  StreamTicket t;
+  t.epoch = ctx.nextEpoch();
+  t.shape = { dt, nRows, nCols };
   // (the kernels write the verdict -- header check, checksum, flags -- through to `slot`, pinned host memory, as well as to
   // the device cell they read it back from: a copy kernel behind the decode would cost every call 4 us.  The slot is wiped
   // first: if a launch fails, what the operation that had the slot before left there must not read as this one's "ok")
   memset(slot + 64, 0, kCellBytes);
   (void)hipGetLastError();
-  const int form = pickForm(ctx, rq.maxForm, nRows, nCols);
-  if (form <= 0) return false;
-  ctx.lastStreamForm = form;
-  if (!launchFastBand(ctx, form, dt, nRows, nCols, rq.dBlob, rq.blobSize, rq.dOut, dCells + 64, epoch, slot + 64)) return false;
+  t.form = ctx.tiers.pick(rq.maxForm, t.shape);
+  if (t.form <= kFormGeneral) return false;
+  if (!launchFastBand(ctx, t, rq.dBlob, rq.blobSize, rq.dOut, dCells + 64, slot + 64)) return false;
   if (hipGetLastError() != hipSuccess) { ctx.lastError = "lerc_amd: a streaming decode kernel could not be launched"; return false; }
   if (rq.nMasks > 0 && rq.dValidBytes) hipMemsetAsync(rq.dValidBytes, 1, (size_t)nRows * nCols, st);    // numValid == nPix or no verdict
+  ticket = t;
   return true;
 }
 
-bool decodeStreamingVerdict(Context& ctx, const u8* slot, u32 epoch, u32* bits, int form, int dt)
+bool decodeStreamingVerdict(Context& ctx, const u8* slot, const StreamTicket& ticket, u32* bits)
 {
   if (ctx.profOn()) ctx.profCollect();
-  if (form < 0) form = ctx.lastStreamForm;
-  const u32 verdict = fastBandVerdict(slot + 64, epoch);
+  u32 blobEnd = 0;
+  const u32 verdict = fastBandVerdict(slot + 64, ticket.epoch, &blobEnd);
   if (bits) *bits = verdict;
-  if (verdict & 0x8u) ctx.wipePersistentState();    // (a workgroup gave up waiting: the checksum accumulators may hold residue)
-  bool gridTooSmall = false;
-  if (form >= 3 && (verdict & 0x4u) && !(verdict & 0x300u))
-  {
-    // (the launch was sized by the last band of this shape and this one is larger: not the stream's fault -- the guess is forgotten)
-    FastDecodeParams hp;
-    memcpy(&hp, slot + 64 + kCellParams, sizeof(hp));
-    gridTooSmall = ctx.lastScanGridBytes != 0u && fastScanNumWG(hp.blobEnd) > fastScanNumWG(ctx.lastScanGridBytes);
-    if (gridTooSmall) ctx.scanHint.end = 0u;
-  }
-  if (form == 3 && (verdict & 0x7u) && !(verdict & 0x300u) && !gridTooSmall)    // (a stream the scanning decoder does not follow)
-  {
-    FastDecodeParams hpS;
-    memcpy(&hpS, slot + 64 + kCellParams, sizeof(hpS));
-    ctx.scanSkip = kScanSkip; ctx.scanSkipRows = (int)hpS.nRows; ctx.scanSkipCols = (int)hpS.nCols;
-  }
-  if (form == 4 && (verdict & 0x7u) && !(verdict & 0x300u) && !gridTooSmall) {
-    FastDecodeParams hpL;
-    memcpy(&hpL, slot + 64 + kCellParams, sizeof(hpL));
-    ctx.scanLate = ctx.scanLateSpan; ctx.scanLateSpan = std::min<u32>(ctx.scanLateSpan * 4u, 4096u);
-    ctx.scanLateRows = (int)hpL.nRows; ctx.scanLateCols = (int)hpL.nCols;
-  }    // (an early count was wrong: the late form mends)
-  if (verdict)
-  {
-    char msg[128];
-    snprintf(msg, sizeof(msg), "streaming decode (form %d) handed the blob on (reason bits 0x%x)", form, verdict);
-    ctx.lastNote = msg;
-    if (!(verdict & 0x300u)) ctx.refusalCount[2]++;    // (a tier's launch thrown away; 0x100 / 0x200: the header said "not ours" / the checksum is wrong)
-    return false;
-  }
-  if (form >= 1 && form <= 4) ctx.formCount[std::min(form, 3)]++;
-  noteBandSize(ctx, slot + 64, dt);
-  return true;
+  if (verdict & kVerdictGaveUp) ctx.wipePersistentState();    // (a workgroup gave up waiting: the checksum accumulators may hold residue)
+  if (ctx.tiers.judge(ticket, verdict, blobEnd)) return true;
+  char msg[128];
+  snprintf(msg, sizeof(msg), "streaming decode (form %d) handed the blob on (reason bits 0x%x)", ticket.form, verdict);
+  ctx.lastNote = msg;
+  return false;
 }
 
-// Device-resident single-band blobs: everything is enqueued before a single byte of the blob has been seen by the
-// host (the header is checked on the device); one synchronisation.  handled == false: nothing was decided,
-// the caller goes the long way (header read, general kernels, exact status codes).
-static u32 decodeSpeculative(Context& ctx, const DecodeRequest& rq, bool& handled, bool& tried, u32* bits = nullptr)
+// The same with the wait in the middle.  handled == false: nothing was decided, the caller goes the long way; ticket.form says
+// whether (and which of) the streaming kernels were tried.
+static u32 decodeSpeculative(Context& ctx, const DecodeRequest& rq, bool& handled, StreamTicket& ticket, u32* bits = nullptr)
 {
-  handled = false; tried = false;
+  handled = false;
   u8* pin = (u8*)ctx.pinned(64 + kCellBytes);
-  u32 epoch = 0;
-  if (!pin || !decodeEnqueueStreaming(ctx, rq, pin, epoch)) return kOk;
-  tried = true;
+  ticket = StreamTicket();
+  if (!pin || !decodeEnqueueStreaming(ctx, rq, pin, ticket)) return kOk;
   if (!ctx.sync()) return kFailed;
-  handled = decodeStreamingVerdict(ctx, pin, epoch, bits, -1, rq.dt);
+  handled = decodeStreamingVerdict(ctx, pin, ticket, bits);
   return kOk;
 }
 
@@ -401,8 +388,6 @@ static u32 decodeImpl(Context& ctx, const DecodeRequest& rq, int fastLevel, bool
   }
 
   // ---- workspace
-  const u32 nPosMin = (u32)(((nRows + 31) / 32) * ((nCols + 31) / 32));
-  (void)nPosMin;
   size_t need = (rq.dBlob ? 0 : (size_t)rq.blobSize + 256) + 2 * (maskBytes + 64) + (1u << 16)
     + (size_t)nD * 8 + 4 * ((size_t)(nPix >> 5) + 1024) * 4;
   // block offsets: one per sub-block for the smallest legal block size we may meet (decided per band below)
@@ -469,7 +454,7 @@ static u32 decodeImpl(Context& ctx, const DecodeRequest& rq, int fastLevel, bool
   // bands decoded by the streaming kernels: their checksum comes out of the decode kernel itself
   // (a band of its own epoch each: the bands share the context's epoch-tagged cells, and cells left by the band before must
   // not look like this band's)
-  struct FastBand { bool used = false; bool offsetsOnly = false; u32 epoch = 0; };    // offsetsOnly: a masked band whose block offsets the scanning decoder's first half found (its flags count, nothing else of the cell)
+  struct FastBand { bool used = false; bool offsetsOnly = false; StreamTicket ticket; };    // ticket: of the band's launch (a masked band's scan: its epoch only); offsetsOnly: a masked band whose block offsets the scanning decoder's first half found (its flags count, nothing else of the cell)
   std::vector<FastBand> fast(rq.nBands);
 
   // what a band's kernels take from the workspace (mask tables, chunk tables, block offsets ...) is sized for ONE band: every band
@@ -758,8 +743,8 @@ static u32 decodeImpl(Context& ctx, const DecodeRequest& rq, int fastLevel, bool
     if (fastBand && fastDataBegin == (u32)(at - bd.offset))
     {
       FastBand& f = fast[iBand];
-      f.epoch = ctx.nextEpoch();
-      if (!launchFastBand(ctx, fastLevel, dt, nRows, nCols, dBand, blobEnd, dOutBand, dCells + 64 + (size_t)iBand * kCellBytes, f.epoch)) return kFailed;
+      f.ticket.form = fastLevel; f.ticket.epoch = ctx.nextEpoch(); f.ticket.shape = { dt, nRows, nCols };
+      if (!launchFastBand(ctx, f.ticket, dBand, blobEnd, dOutBand, dCells + 64 + (size_t)iBand * kCellBytes)) return kFailed;
       ctx.lastDecodeStreamed = true;
       f.used = true;
       if (!finishMask()) return kFailed;    // all valid: the caller's mask bytes become 1s (Lerc.cpp:464-488 always writes them)
@@ -813,13 +798,13 @@ static u32 decodeImpl(Context& ctx, const DecodeRequest& rq, int fastLevel, bool
       fbuf.wgAcc = (u64*)ctx.persistentState(0, (sGrp + 8) * 8);
       if (!fbuf.wgCell || !fbuf.wgAcc) return kFailed;
       FastBand& f = fast[iBand];
-      f.epoch = ctx.nextEpoch();
+      f.ticket.epoch = ctx.nextEpoch();
       f.offsetsOnly = true;
       u8* cell = dCells + 64 + (size_t)iBand * kCellBytes;
       fbuf.params = reinterpret_cast<FastDecodeParams*>(cell + kCellParams);
       fbuf.fallback = reinterpret_cast<u32*>(cell + kCellFallback);
-      fbuf.epoch = f.epoch;
-      fbuf.publishEpoch = (fastTestGiveUp() & 2u) ? f.epoch ^ 0x5A5A5A5Au : f.epoch;
+      fbuf.epoch = f.ticket.epoch;
+      fbuf.publishEpoch = (fastTestGiveUp() & 2u) ? fbuf.epoch ^ 0x5A5A5A5Au : fbuf.epoch;
       fbuf.spinLimit = (fastTestGiveUp() & 2u) ? 8u : (1u << 22);
       // (the scan needs no mask: it runs while the host decodes the mask's RLE and sends the bits)
       { ProfScope ps(ctx, "scan_offsets");
@@ -859,15 +844,15 @@ static u32 decodeImpl(Context& ctx, const DecodeRequest& rq, int fastLevel, bool
     {
       u32 cells[4];
       memcpy(cells, pin + 64 + (size_t)iBand * kCellBytes + kCellFallback, 16);
-      const u32 bits = fastFlagBits(cells, fast[iBand].epoch);
-      if (bits & 0x8u) ctx.wipePersistentState();
+      const u32 bits = fastFlagBits(cells, fast[iBand].ticket.epoch);
+      if (bits & kVerdictGaveUp) ctx.wipePersistentState();
       if (bits)    // the caller repeats with the general kernels' own discovery
       {
         char msg[112];
         snprintf(msg, sizeof(msg), "the scan did not find band %d's blocks (reason bits 0x%x): the general discovery takes it", iBand, bits);
         ctx.lastNote = msg;
         ctx.scanOffsetsBan = true;    // (for the rest of this call)
-        ctx.refusalCount[1]++;
+        ctx.tiers.refusalCount[1]++;
         fellBack = true;
         return kOk;
       }
@@ -875,22 +860,21 @@ static u32 decodeImpl(Context& ctx, const DecodeRequest& rq, int fastLevel, bool
       continue;
     }
     if (!fast[iBand].used) continue;
-    const u32 verdict = fastBandVerdict(pin + 64 + (size_t)iBand * kCellBytes, fast[iBand].epoch);
-    if (verdict & 0x8u) ctx.wipePersistentState();    // (a workgroup gave up waiting: the checksum accumulators may hold residue)
-    if (verdict & 0x200u) return kFailed;    // decoded, but the checksum is wrong
-    if (fastLevel == 3 && (verdict & 0x7u) && !(verdict & 0x300u)) { ctx.scanSkip = kScanSkip; ctx.scanSkipRows = nRows; ctx.scanSkipCols = nCols; }
-    if (fastLevel == 4 && (verdict & 0x7u) && !(verdict & 0x300u)) { ctx.scanLate = ctx.scanLateSpan; ctx.scanLateSpan = std::min<u32>(ctx.scanLateSpan * 4u, 4096u); ctx.scanLateRows = nRows; ctx.scanLateCols = nCols; }
-    if (verdict)                             // caller repeats with the general kernels
+    u32 bandEnd = 0;
+    const u32 verdict = fastBandVerdict(pin + 64 + (size_t)iBand * kCellBytes, fast[iBand].ticket.epoch, &bandEnd);
+    if (verdict & kVerdictGaveUp) ctx.wipePersistentState();    // (a workgroup gave up waiting: the checksum accumulators may hold residue)
+    if (verdict & kVerdictBadChecksum) return kFailed;    // decoded, but the checksum is wrong
+    // (these launches are sized by the band's true size, which the host has read: the launch that is too small for its band, which
+    // judge() forgives a queued decode, cannot arise here.  A header the kernels rule out although the host let it through -- a flag
+    // byte of codec 6 -- sends the band on without counting as a launch thrown away, as it does for the blind attempt)
+    if (!ctx.tiers.judge(fast[iBand].ticket, verdict, bandEnd))    // caller repeats with the next tier
     {
       char msg[96];
       snprintf(msg, sizeof(msg), "streaming decode handed band %d to the general kernels (reason bits 0x%x)", iBand, verdict);
       ctx.lastNote = msg;
-      ctx.refusalCount[2]++;
       fellBack = true;
       return kOk;
     }
-    if (fastLevel >= 1 && fastLevel <= 4) ctx.formCount[std::min(fastLevel, 3)]++;
-    noteBandSize(ctx, pin + 64 + (size_t)iBand * kCellBytes, dt);
   }
   for (int iBand = 0; iBand < rq.nBands; iBand++)
   {
@@ -905,31 +889,30 @@ static u32 decodeImpl(Context& ctx, const DecodeRequest& rq, int fastLevel, bool
     // The scan's cut of a masked band is a proposal: where it had to guess (a raw block's length is in the mask, not in the stream) the
     // decode kernel, which checks every block against the mask, may refuse it.  The general discovery has the last word.
     ctx.lastNote = "the decode kernels refused the scan's block offsets: the general discovery takes the band";
-    ctx.refusalCount[0]++;
+    ctx.tiers.refusalCount[0]++;
     ctx.scanOffsetsBan = true;
     fellBack = true;
     return kOk;
   }
   if (hs.error) { ctx.lastError = "device kernel reported an error"; return hs.error; }
-  ctx.formCount[0] += nScanned;    // (lerc_amd_decode_forms: out[0] counts masked bands whose blocks the scan found)
+  ctx.tiers.formCount[0] += nScanned;    // (lerc_amd_decode_forms: out[0] counts masked bands whose blocks the scan found)
   return kOk;
 }
 
 // Host-pointer calls on a device copy of the blob: the same, with the pixels' (and the mask bytes') way back to the host
 // enqueued behind the kernels, so that the calling thread waits once.  handled == false: the device did not vouch for
 // what it wrote (the caller goes the long way and overwrites it).
-u32 decodeSpeculativeToHost(Context& ctx, const DecodeRequest& rq, void* hOut, size_t outBytes, u8* hMask, size_t maskBytes, bool& handled, bool& tried)
+u32 decodeSpeculativeToHost(Context& ctx, const DecodeRequest& rq, void* hOut, size_t outBytes, u8* hMask, size_t maskBytes, bool& handled, StreamTicket& ticket)
 {
-  handled = false; tried = false;
+  handled = false;
+  ticket = StreamTicket();
   u8* pin = (u8*)ctx.pinned(64 + kCellBytes);
-  u32 epoch = 0;
-  if (!pin || !decodeEnqueueStreaming(ctx, rq, pin, epoch)) return kOk;
-  tried = true;
+  if (!pin || !decodeEnqueueStreaming(ctx, rq, pin, ticket)) return kOk;
   hipStream_t st = ctx.activeStream();
   hipMemcpyAsync(hOut, rq.dOut, outBytes, hipMemcpyDeviceToHost, st);
   if (hMask && rq.dValidBytes) hipMemcpyAsync(hMask, rq.dValidBytes, maskBytes, hipMemcpyDeviceToHost, st);
   if (!ctx.sync()) return kFailed;
-  handled = decodeStreamingVerdict(ctx, pin, epoch, nullptr, -1, rq.dt);
+  handled = decodeStreamingVerdict(ctx, pin, ticket);
   if (handled) { ctx.pathCount[2]++; ctx.lastDecodeStreamed = true; }
   return kOk;
 }
@@ -938,38 +921,35 @@ u32 decodeDevice(Context& ctx, const DecodeRequest& rq)
 {
   // tiers: the scanning decoder, the walking one-launch decoder, the two-launch form (each follows streams the one in front cannot), the general kernels
   ctx.scanOffsetsBan = false;
-  int level = rq.noStreaming ? 0 : pickForm(ctx, rq.maxForm, rq.nRows, rq.nCols);
+  DecodeTiers& tiers = ctx.tiers;
+  const RasterShape shape = { rq.dt, rq.nRows, rq.nCols };
+  int level = rq.noStreaming ? (int)kFormGeneral : tiers.pick(rq.maxForm, shape);
   // A band whose header says "not for the streaming kernels" (a mask, another mode) costs the blind attempt a launch and a wait before
   // the host reads the header itself.  The bands of one job are alike: after such a refusal the next few requests of that shape go
   // to the header-reading path at once (which still hands an unmasked band to the streaming kernels, a header read later).
-  const bool sameShape = ctx.blindShape[0] == rq.dt && ctx.blindShape[1] == rq.nRows && ctx.blindShape[2] == rq.nCols;
-  bool blind = true;
-  if (ctx.blindSkip > 0 && sameShape) { ctx.blindSkip--; blind = false; }
-  while (blind && level > 0)
+  const bool blind = !tiers.notBlind.take(shape);
+  while (blind && level > kFormGeneral)
   {
-    bool handled = false, tried = false;
+    bool handled = false;
     DecodeRequest r = rq;
     r.maxForm = level;
     u32 bits = 0;
-    const u32 src = decodeSpeculative(ctx, r, handled, tried, &bits);
+    StreamTicket ticket;
+    const u32 src = decodeSpeculative(ctx, r, handled, ticket, &bits);
     if (src != kOk) return src;
     if (handled) { ctx.pathCount[2]++; return kOk; }
-    if (!tried) break;    // (not a request the streaming kernels take blind: decodeImpl looks at every band)
-    if (bits == 0x200u) return kFailed;    // (decoded by the streaming kernels, and the checksum is wrong: no other tier would say anything else)
-    if (bits & 0x100u)           // (the header says it is no band for the streaming kernels -- a mask, another mode: the other form would say the same)
-    {
-      ctx.blindSkip = 8; ctx.blindShape[0] = rq.dt; ctx.blindShape[1] = rq.nRows; ctx.blindShape[2] = rq.nCols;
-      break;
-    }
-    level = lowerForm(ctx, level, rq.nRows, rq.nCols);
+    if (ticket.form == kFormGeneral) break;    // (not a request the streaming kernels take blind: decodeImpl looks at every band)
+    if (bits == kVerdictBadChecksum) return kFailed;    // (decoded by the streaming kernels, and the checksum is wrong: no other tier would say anything else)
+    if (bits & kVerdictNotOurs) { tiers.notBlind.open(shape, DecodeTiers::kBlindSkip); break; }    // (a mask, another mode: the other forms would say the same)
+    level = tiers.below(level, shape);
   }
   bool fellBack = false;
   u32 rc = decodeImpl(ctx, rq, level, fellBack);
   bool repeated = false;
-  while (rc == kOk && fellBack && level > 0)
+  while (rc == kOk && fellBack && level > kFormGeneral)
   {
-    level = lowerForm(ctx, level, rq.nRows, rq.nCols);
-    repeated = level == 0;
+    level = tiers.below(level, shape);
+    repeated = level == kFormGeneral;
     rc = decodeImpl(ctx, rq, level, fellBack);
   }
   if (rc == kOk) ctx.pathCount[(repeated || !ctx.lastDecodeStreamed) ? 3 : 2]++;
@@ -988,15 +968,15 @@ u32 decodeTilesDevice(Context& ctx, const TilesDecodeRequest& rq)
   if (tilesBytesDecodeEligible(rq)) return decodeTilesBytes(ctx, rq);
   const int tbytes = dtSize(rq.dt);
   const u64 tileElems = (u64)rq.nRows * (u64)rq.nCols;
-  int batchForm = 0;
+  const RasterShape shape = { rq.dt, rq.nRows, rq.nCols };
+  int batchForm = kFormGeneral;    // (no batch launch yet)
   auto decodeOne = [&](int t) -> u32
   {
     DecodeRequest one;
     one.dBlob = rq.dArena + rq.hOffsets[t]; one.blobSize = rq.hSizes[t]; one.dt = rq.dt; one.nDepth = 1; one.nCols = rq.nCols;
     one.nRows = rq.nRows; one.nBands = 1; one.nMasks = 0; one.dValidBytes = nullptr;
     one.dOut = (u8*)rq.dOut + (size_t)t * tileElems * tbytes;
-    one.maxForm = batchForm > 0 ? batchForm - 1 : 4;    // the batch's kernels have just been tried: the next form (or, if the batch was the two-launch form, the general kernels); no batch launch: every form
-    one.noStreaming = one.maxForm <= 0;
+    if (batchForm > kFormGeneral) one.startAt(ctx.tiers.below(batchForm, shape));    // the batch's kernels have just been tried: the next form (or, if the batch was the two-launch form, the general kernels); no batch launch: every form
     const u32 rc = decodeDevice(ctx, one);
     ctx.tileBatchCount[3]++;
     if (rc == kFailed)    // (a failed decode leaves zeros, include/lerc_amd.h: the streaming kernels may have written pixels of a damaged blob)
@@ -1045,13 +1025,15 @@ u32 decodeTilesDevice(Context& ctx, const TilesDecodeRequest& rq)
     hipMemcpyAsync(dSize, hSize, (size_t)n * 4, hipMemcpyHostToDevice, st);
     FastDecodeParams* dParams = reinterpret_cast<FastDecodeParams*>(dCells + 64);
     u32* dFallback = reinterpret_cast<u32*>(dCells + 64 + (size_t)n * sizeof(FastDecodeParams));
-    const u32 epoch = ctx.nextEpoch();
     // (batches count late, form 3: a tile is a handful of pieces -- nothing to gain from early counts --, and one piece in some thousands
     // has a false survivor that its mending strikes: with early counts that tile would be decoded once more by itself, a wait and
     // a launch of its own; 65 536 tiles: 0.386 of peak against 0.456)
-    batchForm = pickForm(ctx, 3, rq.nRows, rq.nCols);
-    if (!launchFastBands(ctx, batchForm, rq.dt, rq.nRows, rq.nCols, rq.dArena, maxSize, (u32)n, dOff, dSize,
-                         (u8*)rq.dOut + (size_t)t0 * tileElems * tbytes, dParams, dFallback, epoch))
+    StreamTicket ticket;
+    ticket.epoch = ctx.nextEpoch();
+    ticket.shape = shape;
+    ticket.form = batchForm = ctx.tiers.pick(kFormScan, shape);
+    const u32 epoch = ticket.epoch;
+    if (!launchFastBands(ctx, ticket, rq.dArena, maxSize, (u32)n, dOff, dSize, (u8*)rq.dOut + (size_t)t0 * tileElems * tbytes, dParams, dFallback))
       return kFailed;
     hipMemcpyAsync(pin, dCells, cellsBytes, hipMemcpyDeviceToHost, st);
     if (!ctx.sync()) return kFailed;
@@ -1060,13 +1042,13 @@ u32 decodeTilesDevice(Context& ctx, const TilesDecodeRequest& rq)
     const u32* hfb = reinterpret_cast<const u32*>(pin + 64 + (size_t)n * sizeof(FastDecodeParams));
     redo.clear();
     bool gaveUp = false;
-    for (int i = 0; i < n; i++) gaveUp = gaveUp || (fastFlagBits(hfb + 4 * i, epoch) & 0x8u) != 0u;
+    for (int i = 0; i < n; i++) gaveUp = gaveUp || (fastFlagBits(hfb + 4 * i, epoch) & kVerdictGaveUp) != 0u;
     if (gaveUp) ctx.wipePersistentState();    // (a workgroup gave up waiting: the checksum accumulators may hold residue)
     for (int i = 0; i < n; i++)
     {
       const u32 bits = fastFlagBits(hfb + 4 * i, epoch);
       const bool good = hp[i].ok && !bits && hp[i].checksumOk;
-      if (good) { ctx.pathCount[2]++; ctx.tileBatchCount[2]++; ctx.formCount[std::min(batchForm, 3)]++; }
+      if (good) { ctx.pathCount[2]++; ctx.tileBatchCount[2]++; }
       else
       {
         if (redo.empty())
@@ -1079,8 +1061,8 @@ u32 decodeTilesDevice(Context& ctx, const TilesDecodeRequest& rq)
         redo.push_back(t0 + i);
       }
     }
-    if (batchForm == 3 && redo.size() > (size_t)n / 8) { ctx.scanSkip = kScanSkip; ctx.scanSkipRows = rq.nRows; ctx.scanSkipCols = rq.nCols; }    // (tiles the scanning decoder does not follow: the next batches start one tier down)
-    if (batchForm == 4 && redo.size() > (size_t)n / 8) { ctx.scanLate = ctx.scanLateSpan; ctx.scanLateSpan = std::min<u32>(ctx.scanLateSpan * 4u, 4096u); ctx.scanLateRows = rq.nRows; ctx.scanLateCols = rq.nCols; }    // (early counts that were wrong: the next batches count late)
+    // (more than an eighth of the tiles went on: tiles this form does not follow, the next batches start one tier down)
+    ctx.tiers.judgeBatch(ticket, (u32)(n - (int)redo.size()), redo.size() > (size_t)n / 8);
     for (int t : redo) { const u32 rc = decodeOne(t); if (rc != kOk) return rc; }    // (reuses the workspace: the batch is done with it)
   }
   return kOk;

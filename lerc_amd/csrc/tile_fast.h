@@ -243,7 +243,6 @@ static const u32 kResolveChunks = 4;
 #else
 static const u32 kResolveChunks = 256;     // chunks a resolving block takes, one per thread
 #endif
-static const int kOneDiscChunks = (int)(16384u / kFastChunkBytes);       // (kept for the two-launch kernels' templates; no launch uses it any more)
 // The one-launch decoder (tile_fast_decode_one.hip): a workgroup stages kOneStage bytes of the blob as sub-chunks of fastOneSub()
 // bytes (short walks: half a discovery chunk), walks them all, and decodes the blocks that start in all of them but the
 // first -- that one is the last sub-chunk of the workgroup in front, walked again here so that the entry of this workgroup's
@@ -346,6 +345,16 @@ struct FastChunkRec
 // Flags the kernels raise are epoch tagged: cell k == epoch means "raised during this call", so nothing has to be
 // cleared between calls (a stale or never written cell matching the epoch by accident only costs a detour through
 // the general path).  k: 0 discovery, 1 resolve, 2 gather, 3 decode.
+// The host reads a band's four cells as bits 0 .. 3 of its VERDICT and adds two of its own from the parameters the kernels left
+// (codec_decode.cpp: fastBandVerdict).  0: decoded, checksum good.
+static const u32 kVerdictTierFlags = 0x7u;       // flags 0 .. 2: the tier's kernels do not follow this stream (the next tier may)
+static const u32 kVerdictBlockCount = 0x4u;      // flag 2 of them: the blocks found are not the raster's -- also what a scan launch says that held too few pieces for its band
+static const u32 kVerdictGaveUp = 0x8u;          // flag 3: a workgroup gave up waiting for a hand-off (the persistent cells may hold residue)
+static const u32 kVerdictNotOurs = 0x100u;       // the header says the band is not for the streaming kernels: no tier would say anything else
+static const u32 kVerdictBadChecksum = 0x200u;   // decoded, and the checksum is wrong: final
+static const u32 kVerdictFinal = kVerdictNotOurs | kVerdictBadChecksum;
+LERC_HD bool verdictTierRefused(u32 v) { return (v & kVerdictTierFlags) != 0u && (v & kVerdictFinal) == 0u; }    // the stream's fault: the tier below is worth a launch
+LERC_HD bool verdictLaunchWasted(u32 v) { return v != 0u && (v & kVerdictFinal) == 0u; }                         // a tier's launch thrown away (refused, or gave up waiting)
 struct FastDecodeBuffers
 {
   FastChunkRec* recs;  // [nChunks]
@@ -354,7 +363,6 @@ struct FastDecodeBuffers
                        // epoch (32) | the walk that is the true path, 0xFFFF: none (16) | blocks that start in the chunk (16)
   u64* groupCell;      // [ceil(nChunks / kResolveChunks)] epoch (32) | blocks of a resolving block's chunks (32)
   u64* waveFletcher;   // [2 * nWaves] Fletcher partial sums (mod 65535) of the bytes each discovery workgroup staged
-  u64* discCell;       // (unused)
   // the one-launch decoder's hand-offs (tile_fast_decode_one.hip)
   u32 wgStride, wgGroupStride;    // cells / group cells (and accumulators) from one tile's set to the next
   u64* wgCell;         // [fastOneWgStride] epoch (32) | where the path of the workgroup's last sub-chunk ends, relative to the next workgroup's first staged byte (16) | blocks of the workgroup's own sub-chunks (16)
@@ -397,7 +405,7 @@ LERC_HD u32 fastGroupStride(u32 nChunks) { return (nChunks + kResolveChunks - 1u
 
 bool fastDecodeEligible(int dt, int version, int mb, int nRows, int nCols, int nDepth, bool allValid);
 FastWalkPlan makeFastWalkPlan(int nRows, int nCols, u32 sizeGiven, u32 nTiles = 1);
-static const int kFastDecodeStages = 2;    // one kernel each: discover (+ header + checksum terms), resolve + decode; stage 2: all of it in one launch
+static const int kFastDecodeStages = 2;    // one kernel each: discover (+ header + checksum terms), resolve + decode
 void launchFastDecodeOne(int dt, int nRows, int nCols, const FastDecodeBatch& t, const u8* blob, u32 sizeGiven,
                          const FastDecodeBuffers& b, void* out, hipStream_t st);
 void launchFastDecode(int stage, int dt, int nRows, int nCols, const FastDecodeBatch& t, const u8* blob, u32 sizeGiven,

@@ -58,7 +58,7 @@ template<int DT, u32 NCH> struct DiscGeom
   static constexpr u32 kFoundCap = 512, kHitCap = 512;            // count bytes / block headers found in the workgroup's windows (a few dozen)
   static constexpr u32 kScanWords = (W + 2 + 8 + 3) / 4 + 1;      // dwords of a window that can hold the count byte of a block starting in it
 };
-// ... and its LDS (a struct, so that the one-launch decoder can lay the three roles' LDS over each other)
+// ... and its LDS
 template<int DT, u32 NCH, u32 NT> struct DiscShared
 {
   typedef DiscGeom<DT, NCH> G;
@@ -72,12 +72,10 @@ template<int DT, u32 NCH, u32 NT> struct DiscShared
   u32 exit[NCH][G::NW];
   u64 fa[NT / 64], fb[NT / 64];
   u32 over;
-  u16 cnt[NCH][G::NW];                           // (ONE: the walks' counts on their way to the records)
+  u16 cnt[NCH][G::NW];                           // (not used: left in place so that the kernels' LDS size, and with it what the compiler makes of them, stays as measured)
 };
 
-// ONE: a workgroup of the one-launch decoder (k_fast_decode1): what it leaves is read by other workgroups of the SAME launch, on
-// other XCDs -- lists, records and checksum terms leave as write-through stores, and a tagged cell per workgroup says "all out"
-template<int DT, bool RAG, u32 NCH, u32 NT, bool ONE>
+template<int DT, bool RAG, u32 NCH, u32 NT>
 __device__ __forceinline__ void
 fastDiscoverBody(DiscShared<DT, NCH, NT>& S, const u8* __restrict__ blob, u32 sizeGiven, int nRows, int nCols, const FastDecodeBuffers& b, u32 wg)
 {
@@ -105,7 +103,7 @@ fastDiscoverBody(DiscShared<DT, NCH, NT>& S, const u8* __restrict__ blob, u32 si
   if (wg == 0)
   {
     const FastDecodeParams hp = parseBandHeader<DT>(blob, sizeGiven, nRows, nCols);
-    if (threadIdx.x == 0) { storeParams<ONE>(b.params, hp); if (b.hostParams) *b.hostParams = hp; }
+    if (threadIdx.x == 0) { storeParams<false>(b.params, hp); if (b.hostParams) *b.hostParams = hp; }
     hl.ok = hp.ok; hl.version = hp.version; hl.dataBegin = hp.dataBegin; hl.blobEnd = hp.blobEnd;
   }
   else hl = parseHeadLite<DT>(blob, sizeGiven);
@@ -187,8 +185,7 @@ fastDiscoverBody(DiscShared<DT, NCH, NT>& S, const u8* __restrict__ blob, u32 si
     u64 A = 0, B = 0;
 #pragma unroll
     for (u32 k = 0; k < kWaves; k++) { A += s_fa[k]; B += s_fb[k]; }
-    if (ONE) { publish64(b.waveFletcher + 2 * (size_t)wg, A % 65535u); publish64(b.waveFletcher + 2 * (size_t)wg + 1, B % 65535u); }
-    else { b.waveFletcher[2 * (size_t)wg] = A % 65535u; b.waveFletcher[2 * (size_t)wg + 1] = B % 65535u; }
+    b.waveFletcher[2 * (size_t)wg] = A % 65535u; b.waveFletcher[2 * (size_t)wg + 1] = B % 65535u;
   }
 
   // ---- bit-stuffed block headers in the first `window` bytes of every chunk (+ the next workgroup's first one).
@@ -323,7 +320,6 @@ fastDiscoverBody(DiscShared<DT, NCH, NT>& S, const u8* __restrict__ blob, u32 si
     const u32 sigStep = (pattern == 14u) ? 2u : 1u;
     u32 rel = walker ? startRel + (u32)s_final[wc][slot] : kOver;
     u32 count = 0;
-    u64 acc = 0ull;    // (ONE: the block starts of the current group of four)
     LeanWords<DT> xw = leanFetch<DT>(s_in, min(rel, kMaxRel));
     u32 sig = (__builtin_amdgcn_alignbit(xw.x1, xw.x0, 8u * rel) >> 2) & pattern;
     bool active = rel < endRel;
@@ -340,13 +336,7 @@ fastDiscoverBody(DiscShared<DT, NCH, NT>& S, const u8* __restrict__ blob, u32 si
         & ((d == 0u) | (d == sigStep) | (sg == 0u));
       const bool ok = active & valid & (count < (u32)kFastListCap);
 #ifndef LERC_WALK_NOSTORE
-      if (ONE)
-      {
-        // (four block starts leave together: two-byte write-through stores would each be a memory transaction of their own)
-        if (ok) acc |= (u64)(rel - startRel) << (16u * (count & 3u));
-        if (ok && (count & 3u) == 3u) { publish64(reinterpret_cast<u64*>(list) + (count >> 2), acc); acc = 0ull; }
-      }
-      else if (ok) list[count] = (u16)(rel - startRel);
+      if (ok) list[count] = (u16)(rel - startRel);
 #endif
       rel = active ? (ok ? nxt : kOver) : rel;
       count += ok ? 1u : 0u;
@@ -373,21 +363,14 @@ fastDiscoverBody(DiscShared<DT, NCH, NT>& S, const u8* __restrict__ blob, u32 si
       const bool room = count < (u32)kFastListCap;
       const bool ok = active && len != 0u && room;
       tooMany = tooMany || (active && len != 0u && !room);
-      if (ONE)
-      {
-        if (ok) acc |= (u64)(cur - wStart) << (16u * (count & 3u));
-        if (ok && (count & 3u) == 3u) { publish64(reinterpret_cast<u64*>(list) + (count >> 2), acc); acc = 0ull; }
-      }
-      else if (ok) list[count] = (u16)(cur - wStart);
+      if (ok) list[count] = (u16)(cur - wStart);
       alive = alive && (!active || ok);
       cur += ok ? len : 0u;
       count += ok ? 1u : 0u;
       sig = ok ? sg : sig;
     }
     s_exit[wc][slot] = alive ? cur : kNoOffset;
-    if (ONE && (count & 3u) != 0u) publish64(reinterpret_cast<u64*>(list) + (count >> 2), acc);
-    if (ONE) S.cnt[wc][slot] = alive ? (u16)count : (u16)0xFFFFu;
-    else if (wLive) b.recs[wChunk].count[slot] = alive ? (u16)count : (u16)0xFFFFu;
+    if (wLive) b.recs[wChunk].count[slot] = alive ? (u16)count : (u16)0xFFFFu;
     if (__any(tooMany) && lane == 0) s_over = 1u;
   }
   PROBE(21);
@@ -404,26 +387,9 @@ fastDiscoverBody(DiscShared<DT, NCH, NT>& S, const u8* __restrict__ blob, u32 si
       if (e != kNoOffset) { lo = min(lo, e); hi = max(hi, e); n++; }
     }
     FastChunkRec* rec = b.recs + c0 + threadIdx.x;
-    const u32 ex = (n != 0u && lo == hi) ? lo : kNoOffset;
-    if (ONE)
-    {
-      static_assert(sizeof(FastChunkRec) == 24 && kDiscWalks == 8, "a record is three 8-byte stores");
-      u64* dst = reinterpret_cast<u64*>(rec);
-      const u16* cn = S.cnt[threadIdx.x];
-      publish64(dst, (u64)ex | ((u64)n << 32));
-      publish64(dst + 1, (u64)cn[0] | ((u64)cn[1] << 16) | ((u64)cn[2] << 32) | ((u64)cn[3] << 48));
-      publish64(dst + 2, (u64)cn[4] | ((u64)cn[5] << 16) | ((u64)cn[6] << 32) | ((u64)cn[7] << 48));
-    }
-    else { rec->exit = ex; rec->nLive = n; }
+    rec->exit = (n != 0u && lo == hi) ? lo : kNoOffset; rec->nLive = n;
   }
   if (threadIdx.x == 0 && s_over) raiseFlag(b, 0);
-  if (ONE)
-  {
-    // everything this workgroup leaves is on its way: wait until it has arrived, then say so
-    drainVmem();
-    __syncthreads();
-    if (threadIdx.x == 0) publish64(b.discCell + wg, ((u64)b.publishEpoch << 32) | 1u);
-  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -438,41 +404,16 @@ struct ResolveShared
   u64 a[kResolveWG / 64], b[kResolveWG / 64];
   u32 base[kResolveWG / 64];
 };
-// (ONE: a resolving block of the one-launch decoder.  It reads the band header itself, waits for the discovery workgroups of
-// its chunks -- and of the chunk in front of them -- to say "all out", and reads what they left past the L2; the LAST
-// resolving block folds the checksum terms: it is the one that has, by way of the totals in front of it, waited for everybody)
-template<int DT, bool ONE>
-__device__ __forceinline__ void fastResolveBody(ResolveShared& S, const FastDecodeBuffers& b, u32 nWavesBound, u32 discChunks, u32 group,
-                                                const u8* __restrict__ blob = nullptr, u32 sizeGiven = 0, int nRows = 0, int nCols = 0)
+__device__ __forceinline__ void fastResolveBody(ResolveShared& S, const FastDecodeBuffers& b, u32 nWavesBound, u32 discChunks, u32 group)
 {
   auto& s_w = S.w; auto& s_a = S.a; auto& s_b = S.b; auto& s_base = S.base;
-  constexpr u32 kDiscPer = (u32)kOneDiscChunks;
-  const FastDecodeParams hp = ONE ? parseBandHeader<DT>(blob, sizeGiven, nRows, nCols) : *b.params;
+  const FastDecodeParams hp = *b.params;
   const u32 blobEnd = hp.blobEnd;
   const u32 c = group * kResolveChunks + threadIdx.x;
   const u32 cPrev = c ? c - 1u : 0u;
-  u32 prevExit = 0;
-  if (!ONE) prevExit = b.recs[cPrev].exit;    // (the records first: their addresses do not hang on the header)
+  const u32 prevExit = b.recs[cPrev].exit;    // (the records first: their addresses do not hang on the header)
   if (!hp.ok || group * kResolveChunks >= hp.nChunks) return;    // (the grid is sized for the largest stream the blob could hold)
   const int lane = laneId(), w = waveId();
-  if (ONE)
-  {
-    // the discovery workgroups of chunks [first - 1, last]: one thread each
-    const u32 first = group * kResolveChunks, last = min(first + kResolveChunks, hp.nChunks) - 1u;
-    const u32 d0 = (first ? first - 1u : 0u) / kDiscPer, d1 = last / kDiscPer;
-    static_assert(kResolveChunks / kOneDiscChunks + 2 <= kResolveWG, "one thread per discovery workgroup");
-    const u32 d = d0 + threadIdx.x;
-    const bool mineD = d <= d1;
-    u64 cell = mineD ? observe64(b.discCell + d) : 0ull;
-    for (u32 spin = 0; mineD && (u32)(cell >> 32) != b.epoch && spin < b.spinLimit; spin++)
-    {
-      __builtin_amdgcn_s_sleep(8);
-      cell = observe64(b.discCell + d);
-    }
-    if (mineD && (u32)(cell >> 32) != b.epoch) raiseFlag(b, 1);    // (gave up waiting: never seen; the general path takes the band)
-    __syncthreads();
-    prevExit = (u32)observe64(reinterpret_cast<const u64*>(b.recs + cPrev));
-  }
   u32 count = 0, laneOfPath = kNoOffset;
   bool bad = false;
   const bool mine = threadIdx.x < kResolveChunks && c < hp.nChunks;
@@ -484,16 +425,7 @@ __device__ __forceinline__ void fastResolveBody(ResolveShared& S, const FastDeco
     else if (e >= chunkEnd) bad = (e != blobEnd);    // the last block may begin before the last chunk and end with it
     else
     {
-      FastChunkRec rec;
-      if (ONE)
-      {
-        const u64* src = reinterpret_cast<const u64*>(b.recs + c);
-        const u64 r0 = observe64(src), r1 = observe64(src + 1), r2 = observe64(src + 2);
-        rec.exit = (u32)r0; rec.nLive = (u32)(r0 >> 32);
-#pragma unroll
-        for (int l = 0; l < 4; l++) { rec.count[l] = (u16)(r1 >> (16 * l)); rec.count[4 + l] = (u16)(r2 >> (16 * l)); }
-      }
-      else rec = b.recs[c];
+      const FastChunkRec rec = b.recs[c];
       const u32 rel = e - chunkStart;
       // the walk the entry lies on: normally a walk starts there; else it is one of the first blocks of a walk that
       // began a little earlier (something in front of the entry that looks like a block ending right there)
@@ -502,9 +434,7 @@ __device__ __forceinline__ void fastResolveBody(ResolveShared& S, const FastDeco
       {
         if (rec.count[l] == 0xFFFFu) continue;
         const u16* lp = b.lists + ((size_t)c * kDiscWalks + l) * kFastListCap;    // its first four block starts
-        uint2 pre;
-        if (ONE) { const u64 v = observe64(reinterpret_cast<const u64*>(lp)); pre = make_uint2((u32)v, (u32)(v >> 32)); }
-        else pre = *reinterpret_cast<const uint2*>(lp);
+        const uint2 pre = *reinterpret_cast<const uint2*>(lp);
         const u32 st[4] = { pre.x & 0xFFFFu, pre.x >> 16, pre.y & 0xFFFFu, pre.y >> 16 };
 #pragma unroll
         for (u32 k = 0; k < 4; k++)
@@ -554,15 +484,13 @@ __device__ __forceinline__ void fastResolveBody(ResolveShared& S, const FastDeco
   // the chunks hold all the raster's blocks, or the band goes the long way
   if (group == nGroups - 1u && threadIdx.x == kResolveWG - 1 && base + before + inc != hp.nBlocks) raiseFlag(b, 2);
 
-  if (group != (ONE ? nGroups - 1u : 0u)) return;
+  if (group != 0u) return;
   // checksum: Fletcher32 over blob[14 ..) from the discovery waves' partial sums (Lerc2.cpp:1037-1064)
-  const u32 perWave = ONE ? (u32)kOneDiscChunks : discChunks;
-  const u32 nWaves = min((hp.nChunks + perWave - 1u) / perWave, nWavesBound);
+  const u32 nWaves = min((hp.nChunks + discChunks - 1u) / discChunks, nWavesBound);
   u64 A = 0, B = 0;
   for (u32 i = threadIdx.x; i < nWaves; i += kResolveWG)    // each < 65535
   {
-    if (ONE) { A += observe64(b.waveFletcher + 2 * (size_t)i); B += observe64(b.waveFletcher + 2 * (size_t)i + 1); }
-    else { A += b.waveFletcher[2 * (size_t)i]; B += b.waveFletcher[2 * (size_t)i + 1]; }
+    A += b.waveFletcher[2 * (size_t)i]; B += b.waveFletcher[2 * (size_t)i + 1];
   }
   A = waveSum(A % 65535u); B = waveSum(B % 65535u);
   if (lane == 0) { s_a[w] = A; s_b[w] = B; }
@@ -576,7 +504,7 @@ __device__ __forceinline__ void fastResolveBody(ResolveShared& S, const FastDeco
   if (s1 == 0) s1 = 0xffff;
   if (s2 == 0) s2 = 0xffff;
   const u32 good = ((u32)((s2 << 16) | s1) == hp.expectChecksum) ? 1u : 0u;
-  if (ONE) publish32(&b.params->checksumOk, good); else b.params->checksumOk = good;
+  b.params->checksumOk = good;
   if (b.hostParams) b.hostParams->checksumOk = good;
 }
 
@@ -604,16 +532,13 @@ template<class T, bool RAG> struct DecodeShared
   u8 dims[RAG ? kMaxBlocks : 1];       // RAG: width | height << 4 of each block (8 x 8 but for the raster's last block column / row)
 };
 
-// (ONE: a decoding workgroup of the one-launch decoder: it reads the band header itself and, once its chunks' cells are
-// there, what the discovery workgroups left past the L2 -- not before: a line read too early would stay in this XCD's L2)
-template<class T, bool RAG, bool ONE>
+template<class T, bool RAG>
 __device__ __forceinline__ void
-fastDecodeBody(DecodeShared<T, RAG>& S, const FastDecodeBuffers& b, const u8* __restrict__ blob, T* __restrict__ outPix, u32 wgIndex,
-               u32 sizeGiven = 0, int nRows = 0, int nCols = 0)
+fastDecodeBody(DecodeShared<T, RAG>& S, const FastDecodeBuffers& b, const u8* __restrict__ blob, T* __restrict__ outPix, u32 wgIndex)
 {
   constexpr int DT = DtOf<T>::v;
-  const FastDecodeParams hp = ONE ? parseBandHeader<DT>(blob, sizeGiven, nRows, nCols) : *b.params;
-  const u32 raised0 = ONE ? ~b.epoch : b.fallback[0];    // (read together with the parameters: one round trip, not two)
+  const FastDecodeParams hp = *b.params;
+  const u32 raised0 = b.fallback[0];    // (read together with the parameters: one round trip, not two)
   typedef DCfg<T> C;
   constexpr int V = C::V, LPR = C::LPR, BPW = C::BPW;
   typedef DecodeShared<T, RAG> G;
@@ -653,20 +578,11 @@ fastDecodeBody(DecodeShared<T, RAG>& S, const FastDecodeBuffers& b, const u8* __
   }
   // ... walk 0's lists ...
   static_assert(CPD * CAP * 2 / 16 <= 256, "one 16-byte load per thread");
-  // (ONE: past the L2, so that a list that is not there yet leaves nothing behind in it.  Such a list is only used by a workgroup
-  // that found its cells at the first look -- they are written microseconds after the lists have arrived -- and whatever is
-  // used is checked block by block against the stream: first start == the chunk's entry, every block ends where the next begins)
   if (threadIdx.x < CPD * CAP / 8)
   {
     const u32 q = threadIdx.x / (CAP / 8), part = threadIdx.x % (CAP / 8);
     const u16* src = b.lists + ((size_t)(c0 + q) * kDiscWalks) * kFastListCap + 8u * part;    // (chunks behind the last one: the buffer's slack)
-    uint4 l;
-    if (ONE)
-    {
-      const u64 lo = observe64(reinterpret_cast<const u64*>(src)), hi = observe64(reinterpret_cast<const u64*>(src) + 1);
-      l = make_uint4((u32)lo, (u32)(lo >> 32), (u32)hi, (u32)(hi >> 32));
-    }
-    else l = *reinterpret_cast<const uint4*>(src);
+    const uint4 l = *reinterpret_cast<const uint4*>(src);
     *reinterpret_cast<uint4*>(&s_spec[q][8u * part]) = l;
   }
   // ... and the chunks' cells: which walk is the path, how many blocks, the index of the first one (the resolving blocks of
@@ -680,16 +596,14 @@ fastDecodeBody(DecodeShared<T, RAG>& S, const FastDecodeBuffers& b, const u8* __
     {
       u64 cell = observe64(b.chunkCell + 2 * (size_t)c + 1);
       firstCell = observe64(b.chunkCell + 2 * (size_t)c);
-      const bool waited = (u32)(cell >> 32) != epoch;
       for (u32 spin = 0; (u32)(cell >> 32) != epoch && spin < b.spinLimit; spin++)    // (never that long: the resolving blocks were dispatched first)
       {
-        __builtin_amdgcn_s_sleep(ONE ? 16 : 4);
+        __builtin_amdgcn_s_sleep(4);
         cell = observe64(b.chunkCell + 2 * (size_t)c + 1);
       }
       if ((u32)(cell >> 32) != epoch) { raiseFlag(b, 3); cell = 0xFFFFull << 16; }    // (gave up waiting: never seen)
       n = (u32)cell & 0xFFFFu; ln = ((u32)cell >> 16) & 0xFFFFu;
       if (ln == 0xFFFFu) { n = 0; ln = 0; }    // (no path through this chunk: the resolving block has raised the flag)
-      if (ONE && waited) ln |= 0x4000u;         // (the list fetched at the start may have been fetched too early)
     }
     s_n[threadIdx.x] = n; s_lane[threadIdx.x] = ln;
   }
@@ -712,8 +626,7 @@ fastDecodeBody(DecodeShared<T, RAG>& S, const FastDecodeBuffers& b, const u8* __
     const u32 src = min(((ls >> 8) & 3u) + i, CAP - 1u);
     const u16* lp = b.lists + ((size_t)(c0 + q) * kDiscWalks + (ls & 7u)) * kFastListCap + src;
     u32 v;
-    if ((ls & 0x4007u) == 0u) v = (u32)s_spec[q][src];
-    else if (ONE) v = (u32)(observe64(reinterpret_cast<const u64*>(lp - (src & 3u))) >> (16u * (src & 3u))) & 0xFFFFu;    // (written in groups of four)
+    if ((ls & 0x4007u) == 0u) v = (u32)s_spec[q][src];    // (walk 0's list is here already.  Nobody sets bit 14; the mask stays as it was measured: with 7u the compiler lays the kernel out anew)
     else v = (u32)*lp;
     s_pos[f] = (u16)(q * CH + v);
   }
@@ -722,14 +635,7 @@ fastDecodeBody(DecodeShared<T, RAG>& S, const FastDecodeBuffers& b, const u8* __
   {
     u32 last = CPD - 1;
     while (last > 0 && s_n[last] == 0u) last--;    // (a last chunk in which no block starts has no walks and no exit)
-    const u32 ex = ONE ? (u32)observe64(reinterpret_cast<const u64*>(b.recs + c0 + last)) : b.recs[c0 + last].exit;
-    if (ONE)    // the first block starts at its chunk's entry: the exit of the chunk in front (the stream's first block: behind the header)
-    {
-      u32 qf = 0;
-      while (qf < CPD - 1 && s_n[qf] == 0u) qf++;
-      const u32 entry = (c0 + qf == 0u) ? hp.dataBegin : (u32)observe64(reinterpret_cast<const u64*>(b.recs + c0 + qf - 1u));
-      if (entry != r0 + (u32)s_pos[0]) s_bad = 1u;
-    }
+    const u32 ex = b.recs[c0 + last].exit;
     s_pos[nAll] = (u16)min(ex - min(ex, r0), 0xFFFFu);
   }
   // ---- stage the bytes
@@ -993,7 +899,7 @@ k_fast_discover(FastDecodeBuffers b, FastDecodeBatch t, const u8* blob, u32 size
   constexpr u32 NT = (u32)(NCH * kDiscThreads / kDiscChunks);
   tileSlice(b, t, blob, sizeGiven, blockIdx.y);
   __shared__ DiscShared<DT, (u32)NCH, NT> sm;
-  fastDiscoverBody<DT, RAG, (u32)NCH, NT, false>(sm, blob, sizeGiven, nRows, nCols, b, blockIdx.x);
+  fastDiscoverBody<DT, RAG, (u32)NCH, NT>(sm, blob, sizeGiven, nRows, nCols, b, blockIdx.x);
 }
 // The first blocks of the launch resolve (kResolveChunks chunks each; all tiles' resolving blocks first, so that a batch's decode
 // workgroups find the cells of their tile ready like those of a single raster do), the others decode (kDecodeChunks chunks each).
@@ -1009,8 +915,8 @@ k_fast_decode(FastDecodeBuffers b, FastDecodeBatch t, const u8* blob, T* __restr
   u32 sizeGiven = 0;
   tileSlice(b, t, blob, sizeGiven, tile);
   __shared__ union Sm { ResolveShared r; DecodeShared<T, RAG> x; } sm;
-  if (resolving) fastResolveBody<DtOf<T>::v, false>(sm.r, b, t.nWaves, t.discChunks, index);
-  else fastDecodeBody<T, RAG, false>(sm.x, b, blob, outPix + (size_t)tile * t.tileElems, index);
+  if (resolving) fastResolveBody(sm.r, b, t.nWaves, t.discChunks, index);
+  else fastDecodeBody<T, RAG>(sm.x, b, blob, outPix + (size_t)tile * t.tileElems, index);
 }
 
 template<class T>

@@ -702,3 +702,29 @@ def byte_tiling_cases():
             arr = (a & 255).astype(np.uint8).view(dt) if dt is np.int8 else (a & 255).astype(np.uint8)
             out.append((f"bytes-regions-{np.dtype(dt).name}-depth{nd}", arr if nd > 1 else arr[:, :, 0], dict(n_depth=nd) if nd > 1 else {}))
     return out
+
+
+_QUEUED_TWO_SHAPES = []
+
+
+def queued_bands_of_two_shapes(oracle):
+    """Three float32 rasters with their blobs (the oracle's) for the tests on queued decodes whose verdicts come back together: a smooth
+    and a noisy one of a ragged shape -- the noisy blob larger than the smooth one's size + an eighth + 64 KiB by more than a piece of
+    the scanning decoder (32 KiB; the emulator's: 8 KiB), so that a launch sized by the smooth band is too small for the noisy one --
+    and a noisy one of another, larger shape.  Made once."""
+    if not _QUEUED_TWO_SHAPES:
+        rng = np.random.default_rng(41)
+        smooth = terrain(250, 1021, rng, amp=300, base=1000, sigma=0.01).astype(np.float32)
+        noisy = (terrain(250, 1021, rng, amp=300, base=1000, sigma=1.5) + rng.normal(0, 40, (250, 1021))).astype(np.float32)
+        other = (terrain(256, 2048, rng, amp=300, base=1000, sigma=1.5) + rng.normal(0, 40, (256, 2048))).astype(np.float32)
+        out = []
+        for arr, e in ((smooth, 0.05), (noisy, 0.0005), (other, 0.0005)):
+            rc, blob = oracle.encode(arr, e)
+            assert rc == 0
+            out.append((arr, blob))
+        guess = len(out[0][1]) + len(out[0][1]) // 8 + 65536
+        for piece in (8192, 32768):
+            assert -(-len(out[1][1]) // piece) > -(-guess // piece), (piece, len(out[0][1]), len(out[1][1]))    # (else the tests show nothing)
+        assert len(out[2][1]) > len(out[1][1])
+        _QUEUED_TWO_SHAPES.extend(out)
+    return list(_QUEUED_TWO_SHAPES)

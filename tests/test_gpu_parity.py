@@ -1128,6 +1128,47 @@ def test_queued_device_calls(O):
         codec.close()
 
 
+def test_queued_verdicts_are_judged_against_their_own_launch(O):
+    """tests/test_sim_kernels.py: test_sim_queued_verdicts_are_judged_against_their_own_launch on the device, the same rasters: a band
+    whose launch was sized by a smaller band of its shape and, in flight behind it, a band of another shape with a larger launch.  The
+    first is judged against its own launch: the size guess is forgotten (one launch thrown away), the shape stays on the scanning
+    decoder."""
+    import torch
+    from lerc_amd import api
+    dev = torch.device("cuda:0")
+    codec = api.DeviceCodec(torch.cuda.current_stream().cuda_stream)
+    keep = []
+
+    def queue(arr, b0, bound=None):
+        blob = torch.zeros(arr.nbytes + 4096, dtype=torch.uint8, device=dev)
+        blob[:len(b0)] = torch.frombuffer(bytearray(b0), dtype=torch.uint8).to(dev)
+        y = torch.empty(arr.shape, dtype=torch.float32, device=dev)
+        rc, t = api.decode_device_async(codec, blob, bound or blob.numel(), y)
+        assert rc == 0 and t
+        keep.append((blob, y))
+        return t, y
+
+    try:
+        (smooth, bs), (noisy, bn), (other, bo) = cases.queued_bands_of_two_shapes(O)
+        t1, y1 = queue(smooth, bs)
+        assert codec.finish(t1)[0] == 0                                   # the size guess for the shape is now small
+        q0 = codec.decode_refusals()
+        t2, y2 = queue(noisy, bn)                                         # sized by the small guess: too few pieces
+        t3, y3 = queue(other, bo, len(bo))                                # another shape, a larger launch: in flight behind it
+        assert codec.finish(t2)[0] == 0 and codec.finish(t3)[0] == 0
+        f1, q1 = codec.decode_forms(), codec.decode_refusals()
+        for arr, b0, y in ((smooth, bs, y1), (noisy, bn, y2), (other, bo, y3)):
+            assert _same(O.decode(b0)[1].reshape(arr.shape), y.cpu().numpy()), arr.shape
+        assert q1[2] == q0[2] + 1, (q0, q1, codec.last_note())
+        t4, y4 = queue(noisy, bn)
+        assert codec.finish(t4)[0] == 0
+        f2, q2 = codec.decode_forms(), codec.decode_refusals()
+        assert _same(O.decode(bn)[1].reshape(noisy.shape), y4.cpu().numpy())
+        assert f2[3] == f1[3] + 1 and f2[2] == f1[2] and list(q2) == list(q1), ("the scanning decoder did not serve the shape", f1, f2, q1, q2, codec.last_note())
+    finally:
+        codec.close()
+
+
 def test_random_sizes_stay_on_the_streaming_kernels():
     """tools/fallback_hunt.py in the suite: a few thousand round trips of rasters of random sizes (rows / columns multiples of 8 and
     not; float32 and int32) on a fresh context and on a warm one.  Synthetic terrain has nothing that sends a band elsewhere: every

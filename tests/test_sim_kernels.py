@@ -1413,6 +1413,61 @@ def test_sim_queued_decode_whose_launch_was_sized_by_a_smaller_band(libs):
         L.lerc_amd_destroy(h)
 
 
+def test_sim_queued_verdicts_are_judged_against_their_own_launch(libs):
+    """Two queued decodes in flight: a large band of a ragged shape whose launch was sized by a smaller band of that shape (too few
+    pieces: it says so), and behind it a band of ANOTHER shape whose launch is larger than either.  The first verdict is judged
+    against what its own launch held, not against the launch enqueued last: the guess is forgotten (one launch thrown away, counted),
+    and the shape is NOT taken for one the scanning decoder cannot follow -- the same large band once more is served by the scanning
+    decoder.  (Judged against the last launch, the band read as "a stream the scan does not follow" and its shape kept off the
+    scanning decoder for 16 calls.)"""
+    import ctypes as ct
+    O, S = libs
+    L = _async_lib(S)
+    h = L.lerc_amd_create(None)
+    assert h
+    L.lerc_amd_decode_forms.argtypes = [ct.c_void_p, ct.POINTER(ct.c_ulonglong)]
+    L.lerc_amd_decode_refusals.argtypes = [ct.c_void_p, ct.POINTER(ct.c_ulonglong)]
+
+    def counters():
+        f = (ct.c_ulonglong * 4)(); q = (ct.c_ulonglong * 4)()
+        L.lerc_amd_decode_forms(h, f); L.lerc_amd_decode_refusals(h, q)
+        return list(f), list(q)
+
+    keep = []
+
+    def queue(arr, b0, bound=None):
+        blob = _aligned(arr.nbytes + 4096)
+        blob[:] = 0
+        blob[:len(b0)] = np.frombuffer(b0, np.uint8)
+        out = _aligned(arr.nbytes).view(arr.dtype).reshape(arr.shape)
+        t = ct.c_uint(0)
+        rc = L.lerc_amd_decode_device_async(h, blob.ctypes.data, bound or blob.size, 0, None, 1, arr.shape[1], arr.shape[0], 1, capi.dt_code(arr.dtype),
+                                            out.ctypes.data, ct.byref(t))
+        assert rc == 0 and t.value
+        keep.append((blob, out))
+        return t.value, out
+
+    try:
+        (smooth, bs), (noisy, bn), (other, bo) = cases.queued_bands_of_two_shapes(O)
+        t1, o1 = queue(smooth, bs)
+        assert L.lerc_amd_finish(h, t1, None) == 0                       # the size guess for the shape is now small
+        f0, q0 = counters()
+        t2, o2 = queue(noisy, bn)                                         # sized by the small guess: too few pieces
+        t3, o3 = queue(other, bo, len(bo))                                # another shape, a larger launch: in flight behind it
+        assert L.lerc_amd_finish(h, t2, None) == 0 and L.lerc_amd_finish(h, t3, None) == 0
+        f1, q1 = counters()
+        for arr, b0, out in ((smooth, bs, o1), (noisy, bn, o2), (other, bo, o3)):
+            assert _same(O.decode(b0)[1].reshape(arr.shape), out), arr.shape
+        assert q1[2] == q0[2] + 1, (q0, q1)
+        t4, o4 = queue(noisy, bn)
+        assert L.lerc_amd_finish(h, t4, None) == 0
+        f2, q2 = counters()
+        assert _same(O.decode(bn)[1].reshape(noisy.shape), o4)
+        assert f2[3] == f1[3] + 1 and f2[2] == f1[2] and q2 == q1, ("the scanning decoder did not serve the shape", f1, f2, q1, q2)
+    finally:
+        L.lerc_amd_destroy(h)
+
+
 def test_sim_early_counts_that_the_mending_changes(libs):
     """The scanning decoder's pieces say how many blocks they hold as soon as the survivors are counted (form 4, EARLY).  A raster with
     flat stretches has constant blocks, which the scan does not see and the mending enters: the piece's count changes after it has
