@@ -266,11 +266,11 @@ bool decodeStreamingVerdict(Context& ctx, const u8* slot, const StreamTicket& ti
 u32 decodeSpeculativeToHost(Context& ctx, const DecodeRequest& rq, void* hOut, size_t outBytes, u8* hMask, size_t maskBytes, bool& handled, StreamTicket& ticket);    // ticket.form > 0: the streaming kernels were enqueued (and may have written pixels)
 u32 encodeTilesDevice(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed);
 u32 decodeTilesDevice(Context& ctx, const TilesDecodeRequest& rq);
-// the same with a validity mask per tile (codec_tiles_masked.cpp, tile_mask_batch.hip); without mask pointers they ARE the two calls above
+// the same with a validity mask per tile (codec_tiles_batch.cpp, tile_mask_batch.hip); without mask pointers they ARE the two calls above
 u32 encodeTilesDeviceMasked(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed);
 u32 decodeTilesDeviceMasked(Context& ctx, const TilesDecodeRequest& rq);
 
-// 8-bit tiles, every pixel valid, lossless (codec_tiles_bytes.cpp, tile_byte_batch.hip): encodeTilesDevice / decodeTilesDevice hand such requests on
+// 8-bit tiles, every pixel valid, lossless (codec_tiles_batch.cpp, tile_byte_batch.hip): encodeTilesDevice / decodeTilesDevice hand such requests on
 bool tilesBytesEncodeEligible(const TilesEncodeRequest& rq);
 bool tilesBytesDecodeEligible(const TilesDecodeRequest& rq);
 u32 encodeTilesBytes(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed);

@@ -1,0 +1,419 @@
+// codec_tiles_batch.cpp -- host side of the tile batches that do a mosaic's tiles in ONE set of launches and one host wait per sub-batch:
+// the masked batch (lerc_amd_encode_tiles_device_masked / lerc_amd_decode_tiles_device_masked; kernels in tile_mask_batch.hip) and the
+// 8-bit batch (DT_Char / DT_Byte, every pixel valid, lossless, through the tile batch calls; kernels in tile_byte_batch.hip).  One
+// driver, tbEncode / tbDecode, runs both: the sub-batches, the workspace, the records' way home, the arena's bookkeeping.  Tiles the
+// kernels hand back (TileBatchRec::flags) are done one by one behind their sub-batch by encodeDevice / decodeDevice -- byte for byte
+// what those calls make, and their exact status.  A family (MaskedBatch, BytesBatch) supplies what differs: its workspace, its
+// launches, whether a tile by itself carries a mask, its words for a reason.
+#include "codec.h"
+#include "tile_mask_batch.h"
+#include "tile_byte_batch.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+namespace lerc {
+
+// the fields every family's geometry has, the others zero
+template<class G>
+static G tileGeom(int dt, int nRows, int nCols)
+{
+  G g;
+  memset(&g, 0, sizeof(g));
+  g.nRows = nRows; g.nCols = nCols; g.nTV = (nRows + 7) / 8; g.nTH = (nCols + 7) / 8; g.dt = dt;
+  g.tileElems = (u64)nRows * (u64)nCols;
+  g.posStride = ((u32)(g.nTV * g.nTH) + 1u + 3u) & ~3u;
+  return g;
+}
+
+// ================================================================================================
+// the masked family
+// ================================================================================================
+static bool tmbShapeOk(int dt, int nRows, int nCols)
+{
+  const u64 nPix = (u64)nRows * (u64)nCols, nPos = (u64)((nRows + 7) / 8) * (u64)((nCols + 7) / 8);
+  return dt >= DT_Short && dt <= DT_Double && nPix <= (u64)kTmbMaxMaskBytes * 8u && nPos <= kTmbMaxBlocks;
+}
+
+struct MaskedBatch
+{
+  static constexpr bool kMasked = true;    // a tile done by itself carries its mask
+  static constexpr const char* kName = "masked";
+  static constexpr const char* kLaunchError = "lerc_amd: a masked tile batch kernel could not be launched";
+  static constexpr const char* kEncodeScope = "tiles_masked_encode";
+  static constexpr const char* kDecodeScope = "tiles_masked_decode";
+  static constexpr size_t kRecBytes = sizeof(TmbTile);
+
+  TmbGeom g;
+  TmbEncodeBuffers eb;
+  TmbDecodeBuffers db;
+
+  MaskedBatch(int dt, int nRows, int nCols) : g(tileGeom<TmbGeom>(dt, nRows, nCols))
+  {
+    const u32 nBytes = (u32)((g.tileElems + 7) >> 3);
+    g.bitStride = (nBytes + 16u + 15u) & ~15u;
+    g.rleStride = (2u * nBytes + 64u + 15u) & ~15u;    // (no stream is longer: a literal byte costs 1 + 2 / 32767, a run of five 3)
+    g.pos16Stride = ((u32)(((nRows + 15) / 16) * ((nCols + 15) / 16)) + 1u + 3u) & ~3u;
+  }
+
+  size_t encodeBytesPerTile() const { return sizeof(TmbTile) + g.bitStride + g.rleStride + ((size_t)g.posStride + g.pos16Stride) * 4; }
+  size_t decodeBytesPerTile() const { return sizeof(TmbTile) + g.bitStride + (size_t)g.posStride * 4 + 16; }
+
+  // the workspace of n tiles -> their records, nullptr: no room
+  void* carveEncode(Context& ctx, size_t n)
+  {
+    eb.tiles = ctx.allocT<TmbTile>(n);
+    eb.bits = ctx.allocT<u8>(n * g.bitStride);
+    eb.rle = ctx.allocT<u8>(n * g.rleStride);
+    eb.blockOff = ctx.allocT<u32>(n * g.posStride);
+    eb.blockOff16 = ctx.allocT<u32>(n * g.pos16Stride);
+    return (eb.bits && eb.rle && eb.blockOff && eb.blockOff16) ? eb.tiles : nullptr;
+  }
+  void* carveDecode(Context& ctx, size_t n)
+  {
+    db.tiles = ctx.allocT<TmbTile>(n);
+    db.bits = ctx.allocT<u8>(n * g.bitStride);
+    db.blockOff = ctx.allocT<u32>(n * g.posStride);
+    return (db.bits && db.blockOff) ? db.tiles : nullptr;
+  }
+  void launchEncode(u32 n, double maxZErr, const void* dTiles, const u8* dValid, u8* dArena, u64 arenaBase, u64 arenaCapacity, u64 slotBytes, u64 firstTile,
+                    hipStream_t st)
+  {
+    g.nTiles = n;
+    const bool isFlt = g.dt >= DT_Float;
+    u32 cand = 0;    // TryRaiseMaxZError candidates whose error bound beats maxZErr
+    if (isFlt)
+    {
+      static const double errCand[9] = { 1, 0.5, 0.1, 0.05, 0.01, 0.005, 0.001, 0.0005, 0.0001 };
+      for (int c = 0; c < 9; c++) if (errCand[c] / 2 > maxZErr) cand |= 1u << c;
+    }
+    BandParams bp = tbFillBandParams(g, 8);
+    bp.maxQ = maxValToQuantize(g.dt);
+    bp.maxZErr = isFlt ? maxZErr : std::max(0.5, floor(maxZErr));
+    bp.scale = 1 / (2 * bp.maxZErr);
+    bp.invScale = 2 * bp.maxZErr;
+    bp.intLossless = (!isFlt && bp.maxZErr == 0.5) ? 1 : 0;
+    launchTmbEncode(g, bp, bp.maxZErr, cand, dTiles, dValid, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, eb, st);
+  }
+  void launchDecode(u32 n, const u8* dArena, const u64* dOff, const u32* dSize, void* dTiles, u8* dValid, hipStream_t st)
+  {
+    g.nTiles = n;
+    launchTmbDecode(g, dArena, dOff, dSize, dTiles, dValid, db, st);
+  }
+
+  static const char* reason(u32 flags)
+  {
+    if (flags & kTmbNaN) return "a NaN at a valid pixel";
+    if (flags & kTbCapacity) return "the blob does not fit its slot";
+    if (flags & kTbArenaFull) return "the arena is full";
+    if (flags & kTmbRle) return "the mask's run-length stream outgrew its scratch";
+    if (flags & kTbHeader) return "not a header the batch takes";
+    if (flags & kTbChecksum) return "the checksum differs";
+    if (flags & kTmbMaskStream) return "the mask's run-length stream is damaged";
+    if (flags & (kTbBlocks | kTbSibling)) return "the block stream";
+    return "unknown";
+  }
+};
+
+// ================================================================================================
+// the 8-bit family
+// ================================================================================================
+static bool tbbShapeOk(int dt, int nRows, int nCols)
+{
+  const u64 nPix = (u64)nRows * (u64)nCols, nPos = (u64)((nRows + 7) / 8) * (u64)((nCols + 7) / 8);
+  return (dt == DT_Char || dt == DT_Byte) && nPix <= kTbbMaxPixels && nPos <= kTbbMaxBlocks;
+}
+
+bool tilesBytesEncodeEligible(const TilesEncodeRequest& rq)
+{
+  // (maxZErr < 1 on an integer type is lossless: the header says 0.5.  From 1 on there is no Huffman mode: the general path's business)
+  return !rq.dValidBytes && rq.maxZErr < 1 && tbbShapeOk(rq.dt, rq.nRows, rq.nCols);
+}
+
+bool tilesBytesDecodeEligible(const TilesDecodeRequest& rq) { return !rq.dValidBytes && tbbShapeOk(rq.dt, rq.nRows, rq.nCols); }
+
+struct BytesBatch
+{
+  static constexpr bool kMasked = false;
+  static constexpr const char* kName = "8-bit";
+  static constexpr const char* kLaunchError = "lerc_amd: an 8-bit tile batch kernel could not be launched";
+  static constexpr const char* kEncodeScope = "tiles_bytes_encode";
+  static constexpr const char* kDecodeScope = "tiles_bytes_decode";
+  static constexpr size_t kRecBytes = sizeof(TbbTile);
+
+  TbbGeom g;
+  TbbEncodeBuffers eb;
+  TbbDecodeBuffers db;
+
+  BytesBatch(int dt, int nRows, int nCols) : g(tileGeom<TbbGeom>(dt, nRows, nCols)) {}
+
+  size_t encodeBytesPerTile() const { return sizeof(TbbTile) + 512 * 4 + (size_t)g.posStride * 4 + 256 * 8 + kTbbTableCap; }
+  size_t decodeBytesPerTile() const { return sizeof(TbbTile) + (size_t)g.posStride * 4 + 256 * 4 + 256 + 16; }
+
+  void* carveEncode(Context& ctx, size_t n)
+  {
+    eb.tiles = ctx.allocT<TbbTile>(n);
+    eb.histo = ctx.allocT<u32>(n * 512);
+    eb.blockOff = ctx.allocT<u32>(n * g.posStride);
+    eb.codes = ctx.allocT<u64>(n * 256);
+    eb.table = ctx.allocT<u8>(n * kTbbTableCap);
+    return (eb.histo && eb.blockOff && eb.codes && eb.table) ? eb.tiles : nullptr;
+  }
+  void* carveDecode(Context& ctx, size_t n)
+  {
+    db.tiles = ctx.allocT<TbbTile>(n);
+    db.blockOff = ctx.allocT<u32>(n * g.posStride);
+    db.codes = ctx.allocT<u32>(n * 256);
+    db.lens = ctx.allocT<u8>(n * 256);
+    return (db.blockOff && db.codes && db.lens) ? db.tiles : nullptr;
+  }
+  void launchEncode(u32 n, double, const void* dTiles, const u8*, u8* dArena, u64 arenaBase, u64 arenaCapacity, u64 slotBytes, u64 firstTile, hipStream_t st)
+  {
+    g.nTiles = n;
+    BandParams bp = tbFillBandParams(g, 8);    // (lossless: the header says 0.5)
+    bp.allValid = 1;
+    bp.maxQ = maxValToQuantize(g.dt);
+    bp.maxZErr = 0.5; bp.scale = 1.0; bp.invScale = 1.0;
+    bp.intLossless = 1;
+    launchTbbEncode(g, bp, dTiles, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, eb, st);
+  }
+  void launchDecode(u32 n, const u8* dArena, const u64* dOff, const u32* dSize, void* dTiles, u8*, hipStream_t st)
+  {
+    g.nTiles = n;
+    launchTbbDecode(g, dArena, dOff, dSize, dTiles, db, st);
+  }
+
+  static const char* reason(u32 flags)
+  {
+    if (flags & kTbbConst) return "a constant tile";
+    if (flags & kTbbRetry16) return "the low-bit-rate rule asks for 16 x 16 blocks";
+    if (flags & kTbbOneSweep) return "one sweep";
+    if (flags & kTbCapacity) return "the blob does not fit its slot";
+    if (flags & kTbArenaFull) return "the arena is full";
+    if (flags & kTbHeader) return "not a header the batch takes";
+    if (flags & kTbChecksum) return "the checksum differs";
+    if (flags & kTbbTable) return "the code table";
+    if (flags & (kTbBlocks | kTbSibling)) return "the block stream";
+    if (flags & kTbbStream) return "the pixel stream is short";
+    return "unknown";
+  }
+};
+
+// ================================================================================================
+// the driver
+// ================================================================================================
+// tiles per sub-batch: a tile is a blockIdx.y, at most 65535 of them per launch, and 256 MiB of workspace.  LERC_AMD_TEST_TILE_SUBBATCH=n
+// (tests only, read per call) makes it n, so that a handful of tiles takes several sub-batches.
+static int tbMaxBatch(int nTiles, size_t perTile)
+{
+  size_t most = std::min<size_t>(65535, ((size_t)256 << 20) / perTile);
+  const char* e = getenv("LERC_AMD_TEST_TILE_SUBBATCH");
+  const long knob = e ? strtol(e, nullptr, 0) : 0;
+  if (knob >= 1) most = std::min<size_t>(most, (size_t)knob);
+  return (int)std::max<size_t>(1, std::min<size_t>((size_t)nTiles, most));
+}
+
+static const TileBatchRec& tbRec(const u8* recs, size_t stride, int i) { return *reinterpret_cast<const TileBatchRec*>(recs + (size_t)i * stride); }
+
+// per sub-batch, the first tile handed back
+template<class F>
+static void tbNote(Context& ctx, int tile, const char* what, u32 flags)
+{
+  char msg[192];
+  snprintf(msg, sizeof(msg), "tile %d of the %s batch is %s by itself: %s (reason bits 0x%x)", tile, F::kName, what, F::reason(flags), flags);
+  ctx.lastNote = msg;
+}
+
+// batchOk == false: every tile one by one (a request the family's kernels do not take)
+template<class F>
+static u32 tbEncode(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed, bool batchOk)
+{
+  arenaUsed = 0;
+  const bool slotted = rq.slotBytes != 0;
+  const int tb = dtSize(rq.dt);
+  const u64 tileElems = (u64)rq.nRows * (u64)rq.nCols;
+  u64 end = 0;    // arena bytes in use
+
+  auto encodeOne = [&](int t) -> u32
+  {
+    end = slotted ? (u64)t * rq.slotBytes : (end + 15) & ~15ull;
+    EncodeRequest one;
+    one.dData = (const u8*)rq.dData + (size_t)t * tileElems * tb;
+    one.dt = rq.dt; one.nDepth = 1; one.nCols = rq.nCols; one.nRows = rq.nRows; one.nBands = 1; one.nMasks = F::kMasked ? 1 : 0;
+    one.dValidBytes = F::kMasked ? rq.dValidBytes + (size_t)t * tileElems : nullptr;
+    one.maxZErr = rq.maxZErr;
+    one.dOut = rq.dArena + end;
+    one.outCapacity = (u32)std::min<u64>(slotted ? rq.slotBytes : (rq.arenaCapacity > end ? rq.arenaCapacity - end : 0), 0xFFFFFFFFull);
+    u32 needed = 0, written = 0;
+    const u32 rc = encodeDevice(ctx, one, needed, written);
+    if (rc != kOk) return rc;
+    rq.hOffsets[t] = end; rq.hSizes[t] = written;
+    end += written;
+    ctx.tileBatchCount[1]++;
+    return kOk;
+  };
+
+  if (slotted && rq.arenaCapacity < (u64)rq.nTiles * rq.slotBytes) return kBufferTooSmall;
+  if (!batchOk)
+  {
+    for (int t = 0; t < rq.nTiles; t++) { const u32 rc = encodeOne(t); if (rc != kOk) return rc; }
+    arenaUsed = slotted ? (u64)rq.nTiles * rq.slotBytes : end;
+    return kOk;
+  }
+
+  hipStream_t st = ctx.activeStream();
+  F f(rq.dt, rq.nRows, rq.nCols);
+  const size_t perTile = f.encodeBytesPerTile();
+  const int maxBatch = tbMaxBatch(rq.nTiles, perTile);
+  std::vector<int> redo;
+  for (int t0 = 0; t0 < rq.nTiles; t0 += maxBatch)
+  {
+    const int n = std::min(maxBatch, rq.nTiles - t0);
+    ctx.reset();
+    if (!ctx.reserve((size_t)n * perTile + (1u << 16))) return kFailed;
+    const size_t recBytes = (size_t)n * F::kRecBytes;
+    void* rec = f.carveEncode(ctx, (size_t)n);
+    u8* pin = (u8*)ctx.pinned(recBytes);
+    if (!rec || !pin) return kFailed;
+    end = (end + 15) & ~15ull;
+    (void)hipGetLastError();
+    {
+      ProfScope ps(ctx, F::kEncodeScope);
+      f.launchEncode((u32)n, rq.maxZErr, (const u8*)rq.dData + (size_t)t0 * tileElems * tb, F::kMasked ? rq.dValidBytes + (size_t)t0 * tileElems : nullptr,
+                     rq.dArena, end, rq.arenaCapacity, rq.slotBytes, (u64)t0, st);
+    }
+    if (hipGetLastError() != hipSuccess) { ctx.lastError = F::kLaunchError; return kFailed; }
+    hipMemcpyAsync(pin, rec, recBytes, hipMemcpyDeviceToHost, st);
+    if (!ctx.sync()) return kFailed;
+    if (ctx.profOn()) ctx.profCollect();
+    redo.clear();
+    for (int i = 0; i < n; i++)
+    {
+      const TileBatchRec& r = tbRec(pin, F::kRecBytes, i);
+      if (r.flags)
+      {
+        if (!slotted && (r.flags & kTbArenaFull)) return kBufferTooSmall;
+        if (redo.empty()) tbNote<F>(ctx, t0 + i, "encoded", r.flags);
+        redo.push_back(t0 + i);    // (slotted: a tile that does not fit its slot says so when it is encoded by itself)
+        continue;
+      }
+      rq.hOffsets[t0 + i] = r.offset;
+      rq.hSizes[t0 + i] = r.blobSize;
+      // (the arena is in use up to the last byte of the batch's last blob: an arena of exactly that size is enough)
+      if (!slotted) end = std::max<u64>(end, r.offset + r.blobSize);
+      ctx.pathCount[0]++; ctx.tileBatchCount[0]++;
+    }
+    for (int t : redo) { const u32 rc = encodeOne(t); if (rc != kOk) return rc; }    // (reuses the workspace: the batch is done with it)
+  }
+  arenaUsed = slotted ? (u64)rq.nTiles * rq.slotBytes : end;
+  return kOk;
+}
+
+template<class F>
+static u32 tbDecode(Context& ctx, const TilesDecodeRequest& rq, bool batchOk)
+{
+  const int tb = dtSize(rq.dt);
+  const u64 tileElems = (u64)rq.nRows * (u64)rq.nCols;
+  hipStream_t st = ctx.activeStream();
+  u32 firstError = kOk;
+  // a tile by itself; one that fails is left zeroed, mask too, and the call goes on with the tiles behind it
+  auto decodeOne = [&](int t)
+  {
+    DecodeRequest one;
+    one.dBlob = rq.dArena + rq.hOffsets[t]; one.blobSize = rq.hSizes[t]; one.dt = rq.dt; one.nDepth = 1; one.nCols = rq.nCols;
+    one.nRows = rq.nRows; one.nBands = 1; one.nMasks = F::kMasked ? 1 : 0;
+    one.dValidBytes = F::kMasked ? rq.dValidBytes + (size_t)t * tileElems : nullptr;
+    one.dOut = (u8*)rq.dOut + (size_t)t * tileElems * tb;
+    const u32 rc = decodeDevice(ctx, one);
+    ctx.tileBatchCount[3]++;
+    if (rc != kOk)
+    {
+      hipStream_t s = ctx.activeStream();
+      hipMemsetAsync(one.dOut, 0, (size_t)tileElems * tb, s);
+      if (F::kMasked) hipMemsetAsync(one.dValidBytes, 0, (size_t)tileElems, s);
+      hipStreamSynchronize(s);
+      if (firstError == kOk) firstError = rc;
+    }
+  };
+  if (!batchOk)
+  {
+    for (int t = 0; t < rq.nTiles; t++) decodeOne(t);
+    return firstError;
+  }
+
+  F f(rq.dt, rq.nRows, rq.nCols);
+  const size_t perTile = f.decodeBytesPerTile();
+  const int maxBatch = tbMaxBatch(rq.nTiles, perTile);
+  std::vector<int> redo;
+  for (int t0 = 0; t0 < rq.nTiles; t0 += maxBatch)
+  {
+    const int n = std::min(maxBatch, rq.nTiles - t0);
+    ctx.reset();
+    if (!ctx.reserve((size_t)n * perTile + (1u << 16))) return kFailed;
+    void* rec = f.carveDecode(ctx, (size_t)n);
+    u64* dOff = ctx.allocT<u64>((size_t)n + 1);
+    u32* dSize = ctx.allocT<u32>((size_t)n + 1);
+    // (pinned: the tables on their way up, then -- a region of its own -- the records' way back)
+    const size_t upBytes = ((size_t)n * 12 + 64 + 63) & ~(size_t)63, recBytes = (size_t)n * F::kRecBytes;
+    u8* pinUp = (u8*)ctx.pinned(upBytes + recBytes);
+    if (!rec || !dOff || !dSize || !pinUp) return kFailed;
+    u8* pin = pinUp + upBytes;
+    u64* hOff = reinterpret_cast<u64*>(pinUp);
+    u32* hSize = reinterpret_cast<u32*>(pinUp + (size_t)n * 8);
+    for (int i = 0; i < n; i++) { hOff[i] = rq.hOffsets[t0 + i]; hSize[i] = rq.hSizes[t0 + i]; }
+    (void)hipGetLastError();
+    hipMemcpyAsync(dOff, hOff, (size_t)n * 8, hipMemcpyHostToDevice, st);
+    hipMemcpyAsync(dSize, hSize, (size_t)n * 4, hipMemcpyHostToDevice, st);
+    {
+      ProfScope ps(ctx, F::kDecodeScope);
+      f.launchDecode((u32)n, rq.dArena, dOff, dSize, (u8*)rq.dOut + (size_t)t0 * tileElems * tb, F::kMasked ? rq.dValidBytes + (size_t)t0 * tileElems : nullptr, st);
+    }
+    if (hipGetLastError() != hipSuccess) { ctx.lastError = F::kLaunchError; return kFailed; }
+    hipMemcpyAsync(pin, rec, recBytes, hipMemcpyDeviceToHost, st);
+    if (!ctx.sync()) return kFailed;
+    if (ctx.profOn()) ctx.profCollect();
+    redo.clear();
+    for (int i = 0; i < n; i++)
+    {
+      const u32 flags = tbRec(pin, F::kRecBytes, i).flags;
+      if (!flags) { ctx.pathCount[2]++; ctx.tileBatchCount[2]++; continue; }
+      if (redo.empty()) tbNote<F>(ctx, t0 + i, "decoded", flags);
+      redo.push_back(t0 + i);
+    }
+    for (int t : redo) decodeOne(t);    // (reuses the workspace: the batch is done with it)
+  }
+  return firstError;
+}
+
+// ================================================================================================
+// the calls
+// ================================================================================================
+u32 encodeTilesDeviceMasked(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed)
+{
+  if (!rq.dValidBytes) return encodeTilesDevice(ctx, rq, arenaUsed);
+  arenaUsed = 0;
+  if (!rq.dData || !rq.dArena || !rq.hOffsets || !rq.hSizes || rq.nTiles <= 0 || rq.nRows <= 0 || rq.nCols <= 0 || rq.dt < 0 || rq.dt > DT_Double
+    || rq.maxZErr < 0 || (rq.slotBytes & 15u) != 0)
+    return kWrongParam;
+  // (an error bound of 0 on float values is the lossless float mode's business, 777 the bit plane mode's)
+  const bool batchOk = tmbShapeOk(rq.dt, rq.nRows, rq.nCols) && rq.maxZErr != 777 && !(rq.dt >= DT_Float && rq.maxZErr == 0);
+  return tbEncode<MaskedBatch>(ctx, rq, arenaUsed, batchOk);
+}
+
+u32 decodeTilesDeviceMasked(Context& ctx, const TilesDecodeRequest& rq)
+{
+  if (!rq.dValidBytes) return decodeTilesDevice(ctx, rq);
+  if (!rq.dArena || !rq.hOffsets || !rq.hSizes || !rq.dOut || rq.nTiles <= 0 || rq.nRows <= 0 || rq.nCols <= 0 || rq.dt < 0 || rq.dt > DT_Double)
+    return kWrongParam;
+  return tbDecode<MaskedBatch>(ctx, rq, tmbShapeOk(rq.dt, rq.nRows, rq.nCols));
+}
+
+// (encodeTilesDevice / decodeTilesDevice have checked the arguments and the eligibility)
+u32 encodeTilesBytes(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed) { return tbEncode<BytesBatch>(ctx, rq, arenaUsed, true); }
+
+u32 decodeTilesBytes(Context& ctx, const TilesDecodeRequest& rq) { return tbDecode<BytesBatch>(ctx, rq, true); }
+
+}    // namespace lerc

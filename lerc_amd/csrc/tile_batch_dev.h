@@ -1,8 +1,14 @@
-// tile_batch_dev.h -- what a workgroup of 256 threads that owns one tile of a batch needs (tile_mask_batch.hip, tile_byte_batch.hip):
-// sums, Fletcher32 over a finished blob, an exclusive scan in place.
+// tile_batch_dev.h -- the device code the two families of tile batches share (tile_mask_batch.hip, tile_byte_batch.hip).  What a
+// workgroup of 256 threads that owns one tile needs: sums, Fletcher32 over a finished blob, an exclusive scan in place, the codec 6
+// header to and from bytes, the blobs' places in a packed arena, the walk over a tile's block headers.  And what a wave that owns one
+// block needs: the block encoder's and the block decoder's body.  Every piece of LDS is handed in by the kernel that owns it.
 #pragma once
 #include "lerc_common.h"
 #include "wave_utils.h"
+#include "block_plan.h"
+#include "tile_encode_dev.h"
+#include "tile_decode_dev.h"
+#include "tile_batch.h"
 
 namespace lerc {
 
@@ -76,6 +82,310 @@ __device__ __forceinline__ u32 blockScanInPlace(u32* __restrict__ x, u32 n, u32*
   const u32 total = s[256];
   if (threadIdx.x == 0) x[n] = total;
   return total;
+}
+
+// ---- Fletcher32 over blob[14 .. blobSize) (Lerc2.cpp:1037-1064), compared with / stored into the header's field at byte 10 (s: 4 words of LDS)
+__device__ __forceinline__ bool tbChecksumOk(const u8* __restrict__ blob, u32 blobSize, u32 want, u64* s)
+{
+  u64 A, B;
+  blockFletcher(blob + 14, blobSize - 14u, s, A, B);
+  return fletcherFold(A, B, blobSize - 14u) == want;
+}
+
+// a workgroup per tile: the checksum of a finished blob the batch made
+__device__ __forceinline__ void tbWriteChecksum(u8* __restrict__ arena, const TileBatchRec& rec, u64* s)
+{
+  if (rec.flags) return;
+  u8* __restrict__ blob = arena + rec.offset;
+  u64 A, B;
+  blockFletcher(blob + 14, rec.blobSize - 14u, s, A, B);
+  if (threadIdx.x == 0) putBytes(blob + 10, (u64)fletcherFold(A, B, rec.blobSize - 14u), 4);
+}
+
+// ---- packed arena: the batch's blobs back to back at 16-byte aligned offsets from arenaBase on, in tile order, by ONE workgroup
+// (s: 257 words of LDS)
+template<class Rec>
+__device__ __forceinline__ void tbArenaPlace(Rec* __restrict__ tiles, u32 nTiles, u64 arenaBase, u64 arenaCapacity, u64* s)
+{
+  const u32 per = (nTiles + 255u) / 256u, from = min(nTiles, threadIdx.x * per), to = min(nTiles, from + per);
+  u64 sum = 0;
+  for (u32 i = from; i < to; i++) if (!tiles[i].head.flags) sum += ((u64)tiles[i].head.blobSize + 15ull) & ~15ull;
+  s[threadIdx.x] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) { u64 run = 0; for (u32 i = 0; i < 256u; i++) { const u64 y = s[i]; s[i] = run; run += y; } s[256] = run; }
+  __syncthreads();
+  u64 run = arenaBase + s[threadIdx.x];
+  for (u32 i = from; i < to; i++)
+  {
+    TileBatchRec& r = tiles[i].head;
+    if (r.flags) continue;
+    r.offset = run;
+    if (run + r.blobSize > arenaCapacity) r.flags |= kTbArenaFull;
+    run += ((u64)r.blobSize + 15ull) & ~15ull;
+  }
+}
+
+// ---- the codec 6 header (Lerc2.cpp:724-786), 90 bytes
+static const u32 kHdr6 = 90;    // headerBytes(6), codec_common.cpp
+
+struct TbHeader6
+{
+  int version;
+  u32 checksum;
+  int nRows, nCols, nDepth, numValid, microBlockSize, blobSize, dt, nBlobsMore;
+  u32 flagBytes;          // passNoData, isInt, two reserved bytes
+  double maxZErr, zMin, zMax;
+};
+
+// false: not the magic.  Which values a batch takes is its parse kernel's business.
+__device__ __forceinline__ bool tbReadHeader6(const u8* __restrict__ blob, TbHeader6& h)
+{
+  const char magic[6] = { 'L', 'e', 'r', 'c', '2', ' ' };
+  bool ok = true;
+  for (int i = 0; i < 6; i++) if (blob[i] != (u8)magic[i]) ok = false;
+  int ints[10];
+  for (int i = 0; i < 10; i++) ints[i] = (int)(u32)getBytes(blob + 6 + 4 * i, 4);
+  double dbl[3];
+  for (int i = 0; i < 3; i++) { const u64 bits = getBytes(blob + 50 + 8 * i, 8); memcpy(&dbl[i], &bits, 8); }
+  h.version = ints[0]; h.checksum = (u32)ints[1]; h.nRows = ints[2]; h.nCols = ints[3]; h.nDepth = ints[4]; h.numValid = ints[5];
+  h.microBlockSize = ints[6]; h.blobSize = ints[7]; h.dt = ints[8]; h.nBlobsMore = ints[9];
+  h.flagBytes = (u32)getBytes(blob + 46, 4);
+  h.maxZErr = dbl[0]; h.zMin = dbl[1]; h.zMax = dbl[2];
+  return ok;
+}
+
+// (no noData values; the checksum's field is patched once the blob is finished: tbWriteChecksum)
+__device__ __forceinline__ void tbWriteHeader6(u8* out, const TbHeader6& h)
+{
+  const char magic[6] = { 'L', 'e', 'r', 'c', '2', ' ' };
+  for (int i = 0; i < 6; i++) out[i] = (u8)magic[i];
+  const int ints[10] = { h.version, (int)h.checksum, h.nRows, h.nCols, h.nDepth, h.numValid, h.microBlockSize, h.blobSize, h.dt, h.nBlobsMore };
+  for (int i = 0; i < 10; i++) putBytes(out + 6 + 4 * i, (u64)(u32)ints[i], 4);
+  putBytes(out + 46, (u64)h.flagBytes, 4);
+  const double dbl[5] = { h.maxZErr, h.zMin, h.zMax, 0.0, 0.0 };
+  for (int i = 0; i < 5; i++) { u64 bits; memcpy(&bits, &dbl[i], 8); putBytes(out + 50 + 8 * i, bits, 8); }
+}
+
+// ---- the walk over a tile's block stream by ONE thread: block k + 1 starts where block k ends; a block's length follows from its
+// header and its count of valid pixels, nValidOf(k, elements of block k).  table[k]: where block k begins, table[nPos]: where the
+// last one ends.  p: tbFillBandParams(g, MB).  -> 0 or kTbBlocks
+template<int TBYTES, u32 MB, class NV>
+__device__ __forceinline__ u32 tbWalkBlocks(const u8* __restrict__ blob, u32 begin, u32 blobEnd, const BandParams& p, u32* __restrict__ table, NV nValidOf)
+{
+  const u32 nTH = (u32)p.nTH, nPos = (u32)(p.nTV * p.nTH);
+  const u32 pattern = 14u;    // codec >= 5: bit 2 of the flag is the difference flag
+  u32 pos = begin, fl = 0;
+  for (u32 k = 0; k < nPos; k++)
+  {
+    table[k] = pos;
+    const u32 it = k / nTH, jt = k - it * nTH;
+    const u32 nElem = min(MB, (u32)p.nRows - it * MB) * min(MB, (u32)p.nCols - jt * MB);
+    const int nv = nValidOf(k, nElem);
+    BlkInfo bi;
+    const int rc = parseBlock<TBYTES>(blob, pos, blobEnd, p, nv, nElem, bi);
+    // (a block of a position without valid pixels is the one "all zero" byte)
+    if (rc != 0 || bi.len == 0 || (((u32)bi.flag >> 2) & pattern) != (((jt * MB) >> 3) & pattern) || bi.diff || (nv == 0 && bi.mode != 2)) { fl = kTbBlocks; break; }
+    pos += bi.len;
+  }
+  if (!fl && pos != blobEnd) fl = kTbBlocks;
+  table[nPos] = pos;
+  return fl;
+}
+
+// ---- the block encoder's wave body: k_encode_tiles (tile_encode.hip) for one value a pixel and a tile of a batch.  The wave owns block
+// pos of the tile px (p: the tile's nRows, nCols, nTH, block size, error bound); lane l holds elements l, l + 64, ... of the block.
+// MASKED: maskBits says which pixels are valid unless p.allValid, and the error bound may be any; else every pixel is valid and the
+// tile lossless (p.maxZErr 0.5, p.intLossless).  WRITE: the block's bytes go to data + table[pos] (data: where the tile's block stream
+// begins); else its size goes to table[pos].  LDS of the wave: valBuf E * 64 values; WRITE: obuf (1 + E * 64 * sizeof(T) + 3) / 4 + 4
+// words, lutBuf E * 64 words.
+template<class T, int E, bool MASKED, bool WRITE>
+__device__ __forceinline__ void tbEncodeBlock(const BandParams& p, int pos, const T* __restrict__ px, const u8* __restrict__ maskBits,
+                                              u32* __restrict__ table, u8* __restrict__ data, T* valBuf, u32* obuf, u32* lutBuf)
+{
+  constexpr int MB = E == 1 ? 8 : 16;
+  const int lane = laneId();
+  const int it = pos / p.nTH, jt = pos - it * p.nTH;
+  const int i0 = it * MB, j0 = jt * MB;
+  const int tileH = min(MB, p.nRows - i0), tileW = min(MB, p.nCols - j0);
+  const int nElem = tileH * tileW;
+  const bool allValid = !MASKED || p.allValid;
+
+  int rank[E];
+  i64 pix[E];
+  T v[E];
+  u32 q[E];
+  int n = MASKED ? 0 : nElem;
+#pragma unroll
+  for (int k = 0; k < E; k++)
+  {
+    const int e = k * 64 + lane;
+    const bool inb = e < nElem;
+    const int r = inb ? e / tileW : 0, c = inb ? e - r * tileW : 0;
+    pix[k] = (i64)(i0 + r) * p.nCols + (j0 + c);
+    if (MASKED)
+    {
+      const bool valid = inb && (p.allValid || maskBit(maskBits, pix[k]));
+      const u64 bal = __ballot(valid);
+      rank[k] = valid ? n + __popcll(bal & laneMaskLt()) : -1;
+      n += __popcll(bal);
+    }
+    else rank[k] = inb ? e : -1;
+  }
+
+  if (MASKED && n == 0)    // empty position: one "all zero" byte (Lerc2.cpp:1534-1538, :1960-1966)
+  {
+    if (WRITE) { if (lane == 0) data[table[pos]] = (u8)(((u32)(((j0 >> 3) & 15) << 2) & 0x38u) | 2u); }
+    else if (lane == 0) table[pos] = 1u;
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < E; k++)
+  {
+    v[k] = T(0);
+    if (rank[k] >= 0) { v[k] = px[pix[k]]; valBuf[rank[k]] = v[k]; }
+  }
+  waveSync();
+
+  // --- statistics (GetValidDataAndStats)
+  T mn = valBuf[0], mx = valBuf[0];
+#pragma unroll
+  for (int k = 0; k < E; k++)
+    if (rank[k] >= 0) { mn = (v[k] < mn) ? v[k] : mn; mx = (v[k] > mx) ? v[k] : mx; }
+  mn = waveMinT(mn);
+  mx = waveMaxT(mx);
+  int same = 0;
+#pragma unroll
+  for (int k = 0; k < E; k++)
+  {
+    bool s = false;
+    if (rank[k] > 0) s = (v[k] == valBuf[rank[k] - 1]);
+    else if (rank[k] == 0) s = allValid ? (v[k] == T(0)) : false;    // prevVal starts at 0 (all-valid branch only)
+    same += __popcll(__ballot(s));
+  }
+  const bool tryLut = (n > 4) && ((double)mx > (double)mn + 3 * p.maxZErr) && (2 * same > n);
+
+  double mv = 0;
+  bool quantOk = false;
+  if (!MASKED || p.maxZErr > 0)    // (not MASKED: 0.5)
+  {
+    mv = ((double)mx - (double)mn) * p.scale;
+    quantOk = !(mv > (double)p.maxQ || (u32)(mv + 0.5) == 0);
+  }
+  u32 qMax = 0;
+#pragma unroll
+  for (int k = 0; k < E; k++) q[k] = 0;
+  if (quantOk)
+  {
+#pragma unroll
+    for (int k = 0; k < E; k++)
+      if (rank[k] >= 0)
+      {
+        q[k] = (!MASKED || p.intLossless) ? quantLossless<T>(v[k], mn) : (u32)(((double)v[k] - (double)mn) * p.scale + 0.5);
+        qMax = q[k] > qMax ? q[k] : qMax;
+      }
+    qMax = waveMax(qMax);
+  }
+  u32 nDistinct = 0;
+  if (tryLut && quantOk)
+  {
+    u32 idxTmp[E];
+    nDistinct = extractDistinct<E>(q, rank, nullptr, idxTmp);
+  }
+  const Plan plan = planBlock<T>(p, n, mn, mx, p.dt, tryLut, mv, qMax, nDistinct);
+  if (!WRITE) { if (lane == 0) table[pos] = (u32)plan.nBytes; return; }
+
+  composeBlock<T, E>(obuf, lutBuf, p, plan, n, j0, false, mn, v, q, rank, qMax);
+  const u8* ob8 = reinterpret_cast<const u8*>(obuf);
+  u8* __restrict__ dst = data + table[pos];
+  for (int i = lane; i < plan.nBytes; i += 64) dst[i] = ob8[i];
+}
+
+// ---- the block decoder's wave body: k_decode_tiles (tile_decode.hip) for one value a pixel and a tile of a batch.  The wave owns block
+// pos, which begins at blob + off; p: the tile's nRows, nCols, nTH, block size, invScale, version; zMax: the header's.  MASKED: as
+// above; pixels of the block that are not valid are written as 0.  LDS of the wave: lut 256 words, head 64 bytes (16-byte aligned).
+// -> true: the block cannot be decoded (the caller raises kTbSibling)
+template<class T, int E, bool MASKED>
+__device__ __forceinline__ bool tbDecodeBlock(const BandParams& p, double zMax, int pos, const u8* __restrict__ blob, u32 blobEnd, u32 off,
+                                              const u8* __restrict__ maskBits, T* __restrict__ out, u32* lut, u8* head)
+{
+  constexpr int MB = E == 1 ? 8 : 16;
+  const int lane = laneId();
+  const int it = pos / p.nTH, jt = pos - it * p.nTH;
+  const int i0 = it * MB, j0 = jt * MB;
+  const int tileH = min(MB, p.nRows - i0), tileW = min(MB, p.nCols - j0);
+  const int nElem = tileH * tileW;
+
+  int rank[E];
+  i64 px[E];
+  int nValid = MASKED ? 0 : nElem;
+#pragma unroll
+  for (int k = 0; k < E; k++)
+  {
+    const int e = k * 64 + lane;
+    const bool inb = e < nElem;
+    const int r = inb ? e / tileW : 0, c = inb ? e - r * tileW : 0;
+    px[k] = inb ? (i64)(i0 + r) * p.nCols + (j0 + c) : -1;
+    if (MASKED)
+    {
+      const bool valid = inb && (p.allValid || maskBit(maskBits, px[k]));
+      const u64 bal = __ballot(valid);
+      rank[k] = valid ? nValid + __popcll(bal & laneMaskLt()) : -1;
+      nValid += __popcll(bal);
+    }
+    else rank[k] = inb ? e : -1;
+  }
+
+  head[lane] = ((u64)off + (u64)lane < (u64)blobEnd) ? blob[(u64)off + lane] : (u8)0;
+  waveSync();
+  BlkInfo bi;
+  const int rc = (off < blobEnd) ? parseBlockWords<(int)sizeof(T)>(reinterpret_cast<const u32*>(head), 0u, blobEnd - off, p, nValid, (u32)nElem, bi) : 1;
+  bool failed = rc != 0 || (((u32)bi.flag >> 2) & 14u) != (((u32)j0 >> 3) & 14u) || bi.diff;
+  if (!failed)
+  {
+    double offset = 0;
+    if (bi.mode == 1 || bi.mode == 3) offset = typedFromBits(getBytes(head + 1, bi.offBytes), bi.dtUsed);
+    const u64 payloadBit = 8ull * ((u64)off + bi.payload);
+    const int nbIdx = bi.lut ? bitLen(bi.nLut) : 0;
+    u64 idxBit = 0;
+    if (bi.mode == 1 && bi.lut)
+    {
+      lut[0] = 0;
+      for (u32 i = (u32)lane; i < bi.nLut; i += 64) lut[i + 1] = unstuffElement(blob, payloadBit, i, bi.nb, bi.nLut, blobEnd, p.version);
+      idxBit = payloadBit + 8ull * (((u64)bi.nLut * bi.nb + 7) >> 3);
+      waveSync();
+    }
+    bool badIdx = false;
+#pragma unroll
+    for (int k = 0; k < E; k++)
+    {
+      T val = T(0);
+      if (rank[k] >= 0)
+      {
+        if (bi.mode == 2) val = T(0);
+        else if (bi.mode == 0)
+        {
+          const u64 bits = getBytes(blob + off + 1 + (u64)rank[k] * sizeof(T), (int)sizeof(T));
+          memcpy(&val, &bits, sizeof(T));
+        }
+        else if (bi.mode == 3) val = (T)offset;
+        else
+        {
+          u32 q;
+          if (!bi.lut) q = unstuffElement(blob, payloadBit, (u32)rank[k], bi.nb, bi.cnt, blobEnd, p.version);
+          else
+          {
+            const u32 ix = unstuffElement(blob, idxBit, (u32)rank[k], nbIdx, bi.cnt, blobEnd, p.version);
+            if (ix > bi.nLut) { badIdx = true; q = 0; } else q = lut[ix];
+          }
+          const double z = offset + (double)q * p.invScale;
+          val = (T)(z < zMax ? z : zMax);    // std::min(z, zMax)
+        }
+      }
+      if (px[k] >= 0) out[px[k]] = val;
+    }
+    failed = __any(badIdx);
+  }
+  return failed;
 }
 
 }    // namespace lerc

@@ -1,48 +1,37 @@
 // tile_byte_batch.h -- batches of 8-BIT tiles (tile_byte_batch.hip): what the host hands the kernels and reads back.
 #pragma once
-#include "lerc_common.h"
+#include "tile_batch.h"
 
 namespace lerc {
 
-// why a tile left the batch (it is then encoded / decoded by itself behind the batch); the bits tile_mask_batch.h uses keep their meaning
+// why a tile left the batch (it is then encoded / decoded by itself behind the batch): this family's own reasons beside the shared ones
+// (tile_batch.h).  kTbHeader here: codec < 6, another shape or type, a mask, 16 x 16 blocks, constant, one sweep, ...
 enum : u32
 {
   kTbbConst = 2u,         // every pixel has the same value
   kTbbRetry16 = 32u,      // the low-bit-rate rule asks for 16 x 16 blocks (Lerc2.cpp:335-338)
-  kTbbCapacity = 64u,     // the blob does not fit its slot (encoded by itself, that tile says BufferTooSmall)
-  kTbbArenaFull = 128u,   // the blob does not fit what is left of the arena
   kTbbOneSweep = 256u,    // the raw form is no longer than the coded one
   // decode
-  kTbbHeader = 1024u,     // not a header the batch takes (codec < 6, another shape or type, a mask, 16 x 16 blocks, constant, one sweep, ...)
-  kTbbChecksum = 2048u,   // Fletcher32 differs
   kTbbTable = 4096u,      // the code table fails one of parseTable's checks, or is one the batch leaves alone
-  kTbbBlocks = 8192u,     // tiling mode: a block header that cannot be, or the blocks do not end where the blob does
-  kTbbSibling = 16384u,   // tiling mode: a block's decode failed (raised by the block kernel's waves)
   kTbbStream = 32768u     // the pixel stream holds fewer code words than the tile has pixels
 };
 
 struct TbbTile    // one per tile, device; copied home after the batch
 {
-  u32 flags;              // 0: the batch's kernels did the tile
+  TileBatchRec head;
   u32 mode;               // ImageEncodeMode: 0 tiling, 1 delta Huffman, 2 Huffman
   u32 nBytesTiling;       // bytes of the 8 x 8 block stream
   u32 nBytesHuffman;      // code table + pixel stream + padding words of the better code book (0: none)
   u32 tableBytes;         // encode: the serialised code table; decode: where the pixel stream begins in the blob
-  u32 blobSize;
-  u64 offset;             // where the blob lies in the arena
   u64 nBits;              // bits of the pixel stream
   u32 symMin, symMax;     // range as histogram bins (value + 128 for DT_Char)
   u32 checksum;           // decode: the header's
   u32 pad;
 };
 
-struct TbbGeom
-{
-  int nRows, nCols, nTV, nTH, dt;
-  u32 nTiles;
-  u32 posStride;          // words between the tiles' block tables (>= nTV * nTH + 1)
-  u64 tileElems;
-};
+static_assert(sizeof(TbbTile) % 8 == 0, "records lie back to back");
+
+struct TbbGeom : TileGeom {};
 
 static const u32 kTbbMaxPixels = 131072;      // 257 x 257 is 66 049; a code longer than 32 bits needs more pixels than this
 static const u32 kTbbMaxBlocks = 4096;

@@ -33,16 +33,11 @@
 #include <cstdlib>
 #include "kernels.h"
 #include "wave_utils.h"
-#include "block_plan.h"
-#include "tile_encode_dev.h"
-#include "tile_decode_dev.h"
 #include "huffman_dev.h"
 #include "tile_byte_batch.h"
 #include "tile_batch_dev.h"
 
 namespace lerc {
-
-static const u32 kHdr6 = 90;    // bytes of a codec 6 header (headerBytes(6), codec_common.cpp)
 
 // histogram bin of a raw byte: value + 128 for DT_Char (Lerc2.cpp:2320), the value itself for DT_Byte
 template<class T> __device__ __forceinline__ u32 tbbBin(u32 raw) { return (DtOf<T>::v == DT_Char) ? (raw ^ 0x80u) & 255u : raw & 255u; }
@@ -85,7 +80,7 @@ __global__ void __launch_bounds__(256) k_tbb_stats(TbbGeom g, const u8* __restri
   memset(&ti, 0, sizeof(ti));
   ti.symMin = min(min(s_mn[0], s_mn[1]), min(s_mn[2], s_mn[3]));
   ti.symMax = max(max(s_mx[0], s_mx[1]), max(s_mx[2], s_mx[3]));
-  ti.flags = (ti.symMin == ti.symMax) ? kTbbConst : 0u;
+  ti.head.flags = (ti.symMin == ti.symMax) ? kTbbConst : 0u;
   b.tiles[t] = ti;
 }
 
@@ -102,65 +97,12 @@ k_tbb_blocks(TbbGeom g, BandParams p, const T* __restrict__ data, u8* __restrict
   __shared__ u32 s_lut[4][WRITE ? NMAX : 1];
   const u32 t = blockIdx.y;
   const TbbTile ti = b.tiles[t];
-  if (ti.flags || (WRITE && ti.mode != (u32)IEM_Tiling)) return;
-  const int nPos = g.nTV * g.nTH;
-  u8* __restrict__ blob = WRITE ? arena + ti.offset : nullptr;
-  const int w = waveId(), lane = laneId();
+  if (ti.head.flags || (WRITE && ti.mode != (u32)IEM_Tiling)) return;
+  const int w = waveId();
   const int pos = (int)blockIdx.x * 4 + w;
-  if (pos >= nPos) return;    // whole wave leaves together
-  const T* __restrict__ px = data + (u64)t * g.tileElems;
-  u32* __restrict__ table = b.blockOff + (u64)t * g.posStride;
-  const int it = pos / g.nTH, jt = pos - it * g.nTH;
-  const int i0 = it * 8, j0 = jt * 8;
-  const int tileH = min(8, g.nRows - i0), tileW = min(8, g.nCols - j0);
-  const int n = tileH * tileW;
-
-  int rank[1];
-  T v[1];
-  u32 q[1];
-  const bool valid = lane < n;
-  const int r = valid ? lane / tileW : 0, c = valid ? lane - r * tileW : 0;
-  const i64 pix = (i64)(i0 + r) * g.nCols + (j0 + c);
-  rank[0] = valid ? lane : -1;
-  T* valBuf = s_val[w];
-  v[0] = T(0);
-  if (valid) { v[0] = px[pix]; valBuf[lane] = v[0]; }
-  waveSync();
-
-  // --- statistics (GetValidDataAndStats)
-  T mn = valBuf[0], mx = valBuf[0];
-  if (valid) { mn = v[0]; mx = v[0]; }
-  mn = waveMinT(mn);
-  mx = waveMaxT(mx);
-  bool s = false;
-  if (rank[0] > 0) s = (v[0] == valBuf[rank[0] - 1]);
-  else if (rank[0] == 0) s = (v[0] == T(0));    // prevVal starts at 0
-  const int same = __popcll(__ballot(s));
-  const bool tryLut = (n > 4) && ((double)mx > (double)mn + 3 * p.maxZErr) && (2 * same > n);
-
-  const double mv = ((double)mx - (double)mn) * p.scale;
-  const bool quantOk = !(mv > (double)p.maxQ || (u32)(mv + 0.5) == 0);
-  u32 qMax = 0;
-  q[0] = 0;
-  if (quantOk)
-  {
-    if (valid) q[0] = quantLossless<T>(v[0], mn);
-    qMax = waveMax(q[0]);
-  }
-  u32 nDistinct = 0;
-  if (tryLut && quantOk)
-  {
-    u32 idxTmp[1];
-    nDistinct = extractDistinct<1>(q, rank, nullptr, idxTmp);
-  }
-  const Plan plan = planBlock<T>(p, n, mn, mx, p.dt, tryLut, mv, qMax, nDistinct);
-  if (!WRITE) { if (lane == 0) table[pos] = (u32)plan.nBytes; return; }
-
-  u32* obuf = s_obuf[w];
-  composeBlock<T, 1>(obuf, s_lut[w], p, plan, n, j0, false, mn, v, q, rank, qMax);
-  const u8* ob8 = reinterpret_cast<const u8*>(obuf);
-  u8* __restrict__ dst = blob + kTbbDataBegin + table[pos];
-  for (int i = lane; i < plan.nBytes; i += 64) dst[i] = ob8[i];
+  if (pos >= g.nTV * g.nTH) return;    // whole wave leaves together
+  tbEncodeBlock<T, 1, false, WRITE>(p, pos, data + (u64)t * g.tileElems, nullptr, b.blockOff + (u64)t * g.posStride,
+                                    WRITE ? arena + ti.head.offset + kTbbDataBegin : nullptr, s_val[w], s_obuf[w], s_lut[w]);
 }
 
 // ---- a code book, built by ONE thread in LDS
@@ -358,7 +300,7 @@ __global__ void __launch_bounds__(256) k_tbb_decide(TbbGeom g, u64 slotBytes, u6
   __shared__ TbbBook s_book[2];
   __shared__ u32 s_pick;
   const u32 t = blockIdx.x;
-  if (b.tiles[t].flags) return;
+  if (b.tiles[t].head.flags) return;
   const u32 nPos = (u32)(g.nTV * g.nTH);
   const u32* __restrict__ histo = b.histo + (u64)t * 512u;
   s_h[threadIdx.x] = histo[threadIdx.x]; s_h[threadIdx.x + 256u] = histo[threadIdx.x + 256u];
@@ -391,13 +333,13 @@ __global__ void __launch_bounds__(256) k_tbb_decide(TbbGeom g, u64 slotBytes, u6
     ti.nBytesHuffman = nBytesHuffman;
     ti.tableBytes = pick < 2u ? s_book[pick].tableBytes : 0u;
     ti.nBits = pick < 2u ? s_book[pick].nBits : 0ull;
-    ti.blobSize = kTbbDataBegin - 1u + nBytesData;
+    ti.head.blobSize = kTbbDataBegin - 1u + nBytesData;
     if (slotBytes)
     {
-      ti.offset = (firstTile + t) * slotBytes;
-      if ((u64)ti.blobSize > slotBytes) fl |= kTbbCapacity;
+      ti.head.offset = (firstTile + t) * slotBytes;
+      if ((u64)ti.head.blobSize > slotBytes) fl |= kTbCapacity;
     }
-    ti.flags = fl;
+    ti.head.flags = fl;
     s_pick = fl ? 2u : pick;
   }
   __syncthreads();
@@ -409,26 +351,10 @@ __global__ void __launch_bounds__(256) k_tbb_decide(TbbGeom g, u64 slotBytes, u6
   for (u32 i = threadIdx.x; i < k.tableBytes; i += 256u) tab[i] = k.table[i];
 }
 
-// packed arena: the batch's blobs back to back at 16-byte aligned offsets from arenaBase on, in tile order
 __global__ void __launch_bounds__(256) k_tbb_arena(u32 nTiles, u64 arenaBase, u64 arenaCapacity, TbbEncodeBuffers b)
 {
   __shared__ u64 s_part[257];
-  const u32 per = (nTiles + 255u) / 256u, from = min(nTiles, threadIdx.x * per), to = min(nTiles, from + per);
-  u64 sum = 0;
-  for (u32 i = from; i < to; i++) if (!b.tiles[i].flags) sum += ((u64)b.tiles[i].blobSize + 15ull) & ~15ull;
-  s_part[threadIdx.x] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) { u64 run = 0; for (u32 i = 0; i < 256u; i++) { const u64 y = s_part[i]; s_part[i] = run; run += y; } s_part[256] = run; }
-  __syncthreads();
-  u64 run = arenaBase + s_part[threadIdx.x];
-  for (u32 i = from; i < to; i++)
-  {
-    TbbTile& ti = b.tiles[i];
-    if (ti.flags) continue;
-    ti.offset = run;
-    if (run + ti.blobSize > arenaCapacity) ti.flags |= kTbbArenaFull;
-    run += ((u64)ti.blobSize + 15ull) & ~15ull;
-  }
+  tbArenaPlace(b.tiles, nTiles, arenaBase, arenaCapacity, s_part);
 }
 
 static const u32 kTbbRun = 16;                      // pixels a thread packs in one step
@@ -444,21 +370,17 @@ __global__ void __launch_bounds__(256) k_tbb_write(TbbGeom g, const u8* __restri
   __shared__ u32 s_wave[4];
   const u32 t = blockIdx.x;
   const TbbTile ti = b.tiles[t];
-  if (ti.flags) return;
+  if (ti.head.flags) return;
   const u32 nPix = (u32)g.tileElems, nCols = (u32)g.nCols;
-  u8* __restrict__ blob = arena + ti.offset;
+  u8* __restrict__ blob = arena + ti.head.offset;
   // ---- header (Lerc2.cpp:724-786; checksum patched by k_tbb_checksum), an empty mask section, ranges, "not one sweep", mode
   if (threadIdx.x == 0)
   {
     u8* h = s_hdr;
-    const char magic[6] = { 'L', 'e', 'r', 'c', '2', ' ' };
-    for (int i = 0; i < 6; i++) h[i] = (u8)magic[i];
-    const int ints[10] = { kCodecVersion, 0, g.nRows, g.nCols, 1, (int)nPix, 8, (int)ti.blobSize, g.dt, 0 };
-    for (int i = 0; i < 10; i++) putBytes(h + 6 + 4 * i, (u64)(u32)ints[i], 4);
-    putBytes(h + 46, 0ull, 4);    // passNoData, isInt, two reserved bytes
     const int off = (g.dt == DT_Char) ? 128 : 0;
-    const double dbl[5] = { 0.5, (double)((int)ti.symMin - off), (double)((int)ti.symMax - off), 0.0, 0.0 };
-    for (int i = 0; i < 5; i++) { u64 bits; memcpy(&bits, &dbl[i], 8); putBytes(h + 50 + 8 * i, bits, 8); }
+    const TbHeader6 hd = { kCodecVersion, 0u, g.nRows, g.nCols, 1, (int)nPix, 8, (int)ti.head.blobSize, g.dt, 0, 0u,
+                           0.5, (double)((int)ti.symMin - off), (double)((int)ti.symMax - off) };
+    tbWriteHeader6(h, hd);
     putBytes(h + kHdr6, 0ull, 4);
     h[kHdr6 + 4u] = (u8)((int)ti.symMin - off);
     h[kHdr6 + 5u] = (u8)((int)ti.symMax - off);
@@ -540,12 +462,7 @@ __global__ void __launch_bounds__(256) k_tbb_write(TbbGeom g, const u8* __restri
 __global__ void __launch_bounds__(256) k_tbb_checksum(u8* __restrict__ arena, TbbEncodeBuffers b)
 {
   __shared__ u64 s_red[4];
-  const TbbTile ti = b.tiles[blockIdx.x];
-  if (ti.flags) return;
-  u8* __restrict__ blob = arena + ti.offset;
-  u64 A, B;
-  blockFletcher(blob + 14, ti.blobSize - 14u, s_red, A, B);
-  if (threadIdx.x == 0) putBytes(blob + 10, (u64)fletcherFold(A, B, ti.blobSize - 14u), 4);
+  tbWriteChecksum(arena, b.tiles[blockIdx.x].head, s_red);
 }
 
 template<class T>
@@ -644,84 +561,57 @@ k_tbbd_parse(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
   const u8* __restrict__ blob = arena + offsets[t];
   const u32 sizeGiven = sizes[t];
   const u32 nPix = (u32)g.tileElems;
-  const u32 nPos = (u32)(g.nTV * g.nTH);
 
   if (threadIdx.x == 0)
   {
     TbbTile ti;
     memset(&ti, 0, sizeof(ti));
     u32 fl = 0;
-    if (sizeGiven < kTbbDataBegin + 1u) fl = kTbbHeader;
+    if (sizeGiven < kTbbDataBegin + 1u) fl = kTbHeader;
     else
     {
-      const char magic[6] = { 'L', 'e', 'r', 'c', '2', ' ' };
-      for (int i = 0; i < 6; i++) if (blob[i] != (u8)magic[i]) fl = kTbbHeader;
-      int ints[10];
-      for (int i = 0; i < 10; i++) ints[i] = (int)(u32)getBytes(blob + 6 + 4 * i, 4);
-      double dbl[3];
-      for (int i = 0; i < 3; i++) { const u64 bits = getBytes(blob + 50 + 8 * i, 8); memcpy(&dbl[i], &bits, 8); }
-      const u32 flagBytes = (u32)getBytes(blob + 46, 4);    // passNoData, isInt, reserved
-      ti.checksum = (u32)ints[1];
-      ti.blobSize = (u32)ints[7];
-      if (ints[0] != kCodecVersion || ints[2] != g.nRows || ints[3] != g.nCols || ints[4] != 1 || (u32)ints[5] != nPix || ints[6] != 8
-        || ints[7] < (int)(kTbbDataBegin + 1u) || (u32)ints[7] > sizeGiven || ints[8] != g.dt || ints[9] != 0 || (flagBytes & 0xFFu) != 0u)
-        fl = kTbbHeader;
+      TbHeader6 h;
+      if (!tbReadHeader6(blob, h)) fl = kTbHeader;
+      ti.checksum = h.checksum;
+      ti.head.blobSize = (u32)h.blobSize;
+      if (h.version != kCodecVersion || h.nRows != g.nRows || h.nCols != g.nCols || h.nDepth != 1 || (u32)h.numValid != nPix || h.microBlockSize != 8
+        || h.blobSize < (int)(kTbbDataBegin + 1u) || (u32)h.blobSize > sizeGiven || h.dt != g.dt || h.nBlobsMore != 0 || (h.flagBytes & 0xFFu) != 0u)
+        fl = kTbHeader;
       // (the mode byte is there for an error bound of 0.5 only: Lerc2::HeaderInfo::TryHuffmanInt)
-      if (!(dbl[0] == 0.5) || !(dbl[1] < dbl[2])) fl = kTbbHeader;
+      if (!(h.maxZErr == 0.5) || !(h.zMin < h.zMax)) fl = kTbHeader;
       if (!fl)
       {
         const u8* r = blob + kHdr6;
-        if (getBytes(r, 4) != 0ull || r[4] == r[5] || r[6] != 0 || r[7] > 2) fl = kTbbHeader;    // a mask, constant, one sweep, a later mode
+        if (getBytes(r, 4) != 0ull || r[4] == r[5] || r[6] != 0 || r[7] > 2) fl = kTbHeader;    // a mask, constant, one sweep, a later mode
         ti.mode = r[7];
       }
     }
-    ti.flags = fl;
+    ti.head.flags = fl;
     s_ti = ti;
   }
   __syncthreads();
-  if (s_ti.flags) { if (threadIdx.x == 0) b.tiles[t] = s_ti; return; }
-  const u32 blobEnd = s_ti.blobSize;
+  if (s_ti.head.flags) { if (threadIdx.x == 0) b.tiles[t] = s_ti; return; }
+  const u32 blobEnd = s_ti.head.blobSize;
 
   // ---- Fletcher32 over blob[14 .. blobSize)
+  if (!tbChecksumOk(blob, blobEnd, s_ti.checksum, s_red))
   {
-    u64 A, B;
-    blockFletcher(blob + 14, blobEnd - 14u, s_red, A, B);
-    if (fletcherFold(A, B, blobEnd - 14u) != s_ti.checksum)
-    {
-      if (threadIdx.x == 0) { s_ti.flags = kTbbChecksum; b.tiles[t] = s_ti; }
-      return;
-    }
+    if (threadIdx.x == 0) { s_ti.head.flags = kTbChecksum; b.tiles[t] = s_ti; }
+    return;
   }
   if (threadIdx.x != 0) return;
 
   if (s_ti.mode == (u32)IEM_Tiling)
   {
-    // ---- the walk: block k + 1 starts where block k ends
-    BandParams p;
-    memset(&p, 0, sizeof(p));
-    p.nRows = g.nRows; p.nCols = g.nCols; p.nDepth = 1; p.mb = 8; p.nTV = g.nTV; p.nTH = g.nTH; p.dt = g.dt; p.version = kCodecVersion;
-    u32* __restrict__ table = b.blockOff + (u64)t * g.posStride;
-    const u32 pattern = 14u;    // codec >= 5: bit 2 of the flag is the difference flag
-    u32 pos = kTbbDataBegin, fl = 0;
-    for (u32 k = 0; k < nPos; k++)
-    {
-      table[k] = pos;
-      const u32 it = k / (u32)g.nTH, jt = k - it * (u32)g.nTH;
-      const u32 nElem = min(8u, (u32)g.nRows - it * 8u) * min(8u, (u32)g.nCols - jt * 8u);
-      BlkInfo bi;
-      const int rc = parseBlock<1>(blob, pos, blobEnd, p, (int)nElem, nElem, bi);
-      if (rc != 0 || bi.len == 0 || (((u32)bi.flag >> 2) & pattern) != (jt & pattern) || bi.diff) { fl = kTbbBlocks; break; }
-      pos += bi.len;
-    }
-    if (!fl && pos != blobEnd) fl = kTbbBlocks;
-    table[nPos] = pos;
-    s_ti.flags = fl;
+    // ---- the walk over the block headers; every pixel of a block is valid
+    const BandParams p = tbFillBandParams(g, 8);
+    s_ti.head.flags = tbWalkBlocks<1, 8u>(blob, kTbbDataBegin, blobEnd, p, b.blockOff + (u64)t * g.posStride, [](u32, u32 nElem) { return (int)nElem; });
   }
   else
   {
     u32 used = 0;
-    if (!tbbParseTable(blob + kTbbDataBegin, blobEnd - kTbbDataBegin, b.lens + (u64)t * 256u, b.codes + (u64)t * 256u, used)) s_ti.flags = kTbbTable;
-    else if (kTbbDataBegin + used + 4u > blobEnd) s_ti.flags = kTbbStream;
+    if (!tbbParseTable(blob + kTbbDataBegin, blobEnd - kTbbDataBegin, b.lens + (u64)t * 256u, b.codes + (u64)t * 256u, used)) s_ti.head.flags = kTbbTable;
+    else if (kTbbDataBegin + used + 4u > blobEnd) s_ti.head.flags = kTbbStream;
     s_ti.tableBytes = kTbbDataBegin + used;
   }
   b.tiles[t] = s_ti;
@@ -735,73 +625,19 @@ k_tbbd_blocks(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ o
   __shared__ u32 s_lut[4][256];
   __shared__ __align__(16) u8 s_head[4][64];
   const u32 t = blockIdx.y;
-  if ((b.tiles[t].flags & ~kTbbSibling) || b.tiles[t].mode != (u32)IEM_Tiling) return;
-  const int w = waveId(), lane = laneId();
+  if ((b.tiles[t].head.flags & ~kTbSibling) || b.tiles[t].mode != (u32)IEM_Tiling) return;
+  const int w = waveId();
   const int pos = (int)blockIdx.x * 4 + w;
   if (pos >= g.nTV * g.nTH) return;
-  const u32 blobEnd = b.tiles[t].blobSize;
-  BandParams p;
-  memset(&p, 0, sizeof(p));
-  p.nRows = g.nRows; p.nCols = g.nCols; p.nDepth = 1; p.mb = 8; p.nTV = g.nTV; p.nTH = g.nTH; p.dt = g.dt; p.version = kCodecVersion;
+  BandParams p = tbFillBandParams(g, 8);
   p.allValid = 1;
   p.invScale = 1.0;    // 2 * maxZErr
   const u8* __restrict__ blob = arena + offsets[t];
   double zMax;
   { const u64 bits = getBytes(blob + 66, 8); memcpy(&zMax, &bits, 8); }
-  T* __restrict__ out = outAll + (u64)t * g.tileElems;
-  const int it = pos / g.nTH, jt = pos - it * g.nTH;
-  const int i0 = it * 8, j0 = jt * 8;
-  const int tileH = min(8, g.nRows - i0), tileW = min(8, g.nCols - j0);
-  const int nElem = tileH * tileW;
-  const bool valid = lane < nElem;
-  const int r = valid ? lane / tileW : 0, c = valid ? lane - r * tileW : 0;
-  const i64 px = (i64)(i0 + r) * g.nCols + (j0 + c);
-  const int rank = lane;
-
-  const u32 off = b.blockOff[(u64)t * g.posStride + pos];
-  s_head[w][lane] = ((u64)off + (u64)lane < (u64)blobEnd) ? blob[(u64)off + lane] : (u8)0;
-  waveSync();
-  BlkInfo bi;
-  const int rc = (off < blobEnd) ? parseBlockWords<1>(reinterpret_cast<const u32*>(s_head[w]), 0u, blobEnd - off, p, nElem, (u32)nElem, bi) : 1;
-  bool failed = rc != 0 || (((u32)bi.flag >> 2) & 14u) != (((u32)j0 >> 3) & 14u) || bi.diff;
-  if (!failed)
-  {
-    double offset = 0;
-    if (bi.mode == 1 || bi.mode == 3) offset = typedFromBits(getBytes(s_head[w] + 1, bi.offBytes), bi.dtUsed);
-    const u64 payloadBit = 8ull * ((u64)off + bi.payload);
-    const int nbIdx = bi.lut ? bitLen(bi.nLut) : 0;
-    u64 idxBit = 0;
-    if (bi.mode == 1 && bi.lut)
-    {
-      s_lut[w][0] = 0;
-      for (u32 i = (u32)lane; i < bi.nLut; i += 64) s_lut[w][i + 1] = unstuffElement(blob, payloadBit, i, bi.nb, bi.nLut, blobEnd, p.version);
-      idxBit = payloadBit + 8ull * (((u64)bi.nLut * bi.nb + 7) >> 3);
-      waveSync();
-    }
-    bool badIdx = false;
-    T val = T(0);
-    if (valid)
-    {
-      if (bi.mode == 2) val = T(0);
-      else if (bi.mode == 0) { const u64 bits = getBytes(blob + off + 1 + (u64)rank, 1); memcpy(&val, &bits, 1); }
-      else if (bi.mode == 3) val = (T)offset;
-      else
-      {
-        u32 q;
-        if (!bi.lut) q = unstuffElement(blob, payloadBit, (u32)rank, bi.nb, bi.cnt, blobEnd, p.version);
-        else
-        {
-          const u32 ix = unstuffElement(blob, idxBit, (u32)rank, nbIdx, bi.cnt, blobEnd, p.version);
-          if (ix > bi.nLut) { badIdx = true; q = 0; } else q = s_lut[w][ix];
-        }
-        const double z = offset + (double)q * p.invScale;
-        val = (T)(z < zMax ? z : zMax);    // std::min(z, zMax)
-      }
-    }
-    if (valid) out[px] = val;
-    failed = __any(badIdx);
-  }
-  if (failed && lane == 0) atomicOr(&b.tiles[t].flags, kTbbSibling);
+  const bool failed = tbDecodeBlock<T, 1, false>(p, zMax, pos, blob, b.tiles[t].head.blobSize, b.blockOff[(u64)t * g.posStride + pos], nullptr,
+                                                 outAll + (u64)t * g.tileElems, s_lut[w], s_head[w]);
+  if (failed && laneId() == 0) atomicOr(&b.tiles[t].head.flags, kTbSibling);
 }
 
 static const u32 kTbbdStageWords = 10240;    // 40 KB of stream in LDS: 4.9 bits a pixel at 256 x 256; a longer stream is read where it lies
@@ -862,11 +698,11 @@ k_tbbd_huff(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ off
   __shared__ u32 s_any, s_bad;
   const u32 t = blockIdx.x;
   const TbbTile ti = b.tiles[t];
-  if (ti.flags || ti.mode == (u32)IEM_Tiling) return;
+  if (ti.head.flags || ti.mode == (u32)IEM_Tiling) return;
   const u32 nPix = (u32)g.tileElems, nCols = (u32)g.nCols, nRows = (u32)g.nRows;
   const u8* __restrict__ blob = arena + offsets[t];
   u8* __restrict__ out = outAll + (u64)t * g.tileElems;
-  const u32 streamBegin = ti.tableBytes, blobEnd = ti.blobSize;
+  const u32 streamBegin = ti.tableBytes, blobEnd = ti.head.blobSize;
 
   // ---- the look-up table (buildDecodeTable, huffman_host.cpp): the host fills it symbol by symbol, so where two codes claim an entry
   // the larger symbol has it
@@ -909,7 +745,7 @@ k_tbbd_huff(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ off
   __syncthreads();
   if (s_bad || !s_any)    // (no code at all: codeRange fails on the host)
   {
-    if (threadIdx.x == 0) b.tiles[t].flags = kTbbTable;
+    if (threadIdx.x == 0) b.tiles[t].head.flags = kTbbTable;
     return;
   }
 
@@ -955,7 +791,7 @@ k_tbbd_huff(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ off
   __syncthreads();
   if (s_any || s_scan[256] < nPix)    // (the chain did not settle -- it cannot be --, or fewer code words than pixels)
   {
-    if (threadIdx.x == 0) b.tiles[t].flags = kTbbStream;
+    if (threadIdx.x == 0) b.tiles[t].head.flags = kTbbStream;
     return;
   }
   {

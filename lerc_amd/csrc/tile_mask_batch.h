@@ -1,23 +1,18 @@
 // tile_mask_batch.h -- batches of MASKED tiles (tile_mask_batch.hip): what the host hands the kernels and reads back.
 #pragma once
-#include "lerc_common.h"
+#include "tile_batch.h"
 
 namespace lerc {
 
-// why a tile left the batch (it is then encoded / decoded by itself behind the batch, with its mask)
+// why a tile left the batch (it is then encoded / decoded by itself behind the batch, with its mask): this family's own reasons beside
+// the shared ones (tile_batch.h).  kTbHeader here: codec < 6, another shape or type, blocks other than 8 x 8 or 16 x 16, a mode byte,
+// bytes behind the last section, a count of valid pixels the mask does not share, ...
 enum : u32
 {
   kTmbNaN = 4u,           // a NaN at a valid pixel (the mask changes)
-  kTmbCapacity = 64u,     // the blob does not fit its slot (encoded by itself, that tile says BufferTooSmall)
-  kTmbArenaFull = 128u,   // the blob does not fit what is left of the arena
   kTmbRle = 512u,         // the mask's run-length stream outgrew its scratch
   // decode
-  kTmbHeader = 1024u,     // not a header the batch takes (codec < 6, another shape or type, blocks other than 8 x 8 or 16 x 16, a mode byte,
-                          // bytes behind the last section, a count of valid pixels the mask does not share, ...)
-  kTmbChecksum = 2048u,   // Fletcher32 differs
-  kTmbMaskStream = 4096u, // the mask's run-length stream is damaged
-  kTmbBlocks = 8192u,     // the walk met a block header that cannot be, or the blocks do not end where the blob does
-  kTmbSibling = 16384u    // a block's decode failed (raised by the block kernel's waves)
+  kTmbMaskStream = 4096u  // the mask's run-length stream is damaged
 };
 
 // what a tile's blob holds behind header and mask section (TmbTile::kind)
@@ -32,13 +27,11 @@ enum : u32
 
 struct TmbTile    // one per tile, device; copied home after the batch
 {
-  u32 flags;              // 0: the batch's kernels did the tile
+  TileBatchRec head;
   u32 numValid;
   u32 rleLen;             // bytes of the mask section's run-length stream (0: every pixel valid)
   u32 nBytesTiling;       // bytes of the block stream
-  u32 blobSize;
   u32 dataBegin;          // where the block stream begins in the blob
-  u64 offset;             // where the blob lies in the arena
   u64 minBits, maxBits;   // range over the valid pixels, as raw values of the tile's type
   double zMin, zMax;
   double maxZErr;         // the tile's own error bound (encode: k_tmb_prelude decides it; decode: the header's)
@@ -50,7 +43,9 @@ struct TmbTile    // one per tile, device; copied home after the batch
   u32 rsv;
 };
 
-struct TmbGeom
+static_assert(sizeof(TmbTile) % 8 == 0, "records lie back to back");
+
+struct TmbGeom    // TileGeom's fields and this family's strides
 {
   int nRows, nCols, nTV, nTH, dt;
   u32 nTiles;

@@ -36,15 +36,10 @@
 #include <cstdlib>
 #include "kernels.h"
 #include "wave_utils.h"
-#include "block_plan.h"
-#include "tile_encode_dev.h"
-#include "tile_decode_dev.h"
 #include "tile_mask_batch.h"
 #include "tile_batch_dev.h"
 
 namespace lerc {
-
-static const u32 kHdr6 = 90;    // bytes of a codec 6 header (headerBytes(6), codec_common.cpp)
 
 template<class T> struct TmbAcc { typedef i64 type; static __device__ __forceinline__ i64 hi() { return 0x7FFFFFFFFFFFFFFFll; } static __device__ __forceinline__ i64 lo() { return -0x7FFFFFFFFFFFFFFFll - 1; } };
 template<> struct TmbAcc<float> { typedef double type; static __device__ __forceinline__ double hi() { return __builtin_huge_val(); } static __device__ __forceinline__ double lo() { return -__builtin_huge_val(); } };
@@ -209,12 +204,12 @@ k_tmb_prelude(TmbGeom g, double maxZErr, u32 cand, const T* __restrict__ data, c
     if (fits && at + 2u <= cap) { out[at] = 0x00; out[at + 1] = 0x80; at += 2; rleLen = at; }
     else fl |= kTmbRle;
   }
-  ti.flags = fl;
+  ti.head.flags = fl;
   ti.rleLen = rleLen;
   // header and mask section; where pixels differ: ranges and the "one sweep" byte
   ti.dataBegin = kHdr6 + 4u + rleLen + (ti.kind == kTmbKindBlocks8 ? 2u * (u32)sizeof(T) + 1u : 0u);
   ti.mbSize = 8u;
-  ti.blobSize = ti.dataBegin;    // (all there is of an empty or a constant tile; the others: k_tmb_decide2)
+  ti.head.blobSize = ti.dataBegin;    // (all there is of an empty or a constant tile; the others: k_tmb_decide2)
   b.tiles[t] = ti;
 }
 
@@ -250,23 +245,17 @@ __device__ __forceinline__ u32 tmbRankedSweep(const u8* bits, u32 nPix, u32* s, 
 
 // What lies in front of a tile's block stream, by one workgroup: header (Lerc2.cpp:724-786; checksum patched by k_tmb_checksum),
 // mask section; where the valid pixels differ: ranges and the "one sweep" byte, and behind a 1 the valid pixels raw in row
-// order (Lerc2::WriteDataOneSweep)
+// order (Lerc2::WriteDataOneSweep).  s_hdr: 96 bytes of LDS, s_w: 4 words.
 template<class T>
-__device__ __forceinline__ void tmbWriteFront(const TmbGeom& g, u32 t, const TmbTile& ti, const T* __restrict__ px, u8* __restrict__ blob, const TmbEncodeBuffers& b)
+__device__ __forceinline__ void tmbWriteFront(const TmbGeom& g, u32 t, const TmbTile& ti, const T* __restrict__ px, u8* __restrict__ blob, const TmbEncodeBuffers& b,
+                                              u8* s_hdr, u32* s_w)
 {
-  __shared__ u8 s_hdr[96];
-  __shared__ u32 s_w[4];
   if (threadIdx.x == 0)
   {
-    u8* h = s_hdr;
-    const char magic[6] = { 'L', 'e', 'r', 'c', '2', ' ' };
-    for (int i = 0; i < 6; i++) h[i] = (u8)magic[i];
-    const int ints[10] = { kCodecVersion, 0, g.nRows, g.nCols, 1, (int)ti.numValid, (int)ti.mbSize, (int)ti.blobSize, g.dt, 0 };
-    for (int i = 0; i < 10; i++) putBytes(h + 6 + 4 * i, (u64)(u32)ints[i], 4);
-    putBytes(h + 46, ti.isInt ? 0x100ull : 0ull, 4);    // passNoData, isInt, two reserved bytes
-    const double dbl[5] = { ti.maxZErr, ti.zMin, ti.zMax, 0.0, 0.0 };
-    for (int i = 0; i < 5; i++) { u64 bits; memcpy(&bits, &dbl[i], 8); putBytes(h + 50 + 8 * i, bits, 8); }
-    putBytes(h + kHdr6, (u64)ti.rleLen, 4);
+    const TbHeader6 h = { kCodecVersion, 0u, g.nRows, g.nCols, 1, (int)ti.numValid, (int)ti.mbSize, (int)ti.head.blobSize, g.dt, 0,
+                          ti.isInt ? 0x100u : 0u, ti.maxZErr, ti.zMin, ti.zMax };
+    tbWriteHeader6(s_hdr, h);
+    putBytes(s_hdr + kHdr6, (u64)ti.rleLen, 4);
   }
   __syncthreads();
   for (u32 i = threadIdx.x; i < kHdr6 + 4u; i += 256u) blob[i] = s_hdr[i];
@@ -310,116 +299,27 @@ k_tmb_blocks(TmbGeom g, BandParams p, const T* __restrict__ data, u8* __restrict
   __shared__ u32 s_lut[4][WRITE ? NMAX : 1];
   const u32 t = blockIdx.y;
   const TmbTile ti = b.tiles[t];
-  if (ti.flags) return;
+  if (ti.head.flags) return;
   const int nTV = (g.nRows + MB - 1) / MB, nTH = (g.nCols + MB - 1) / MB;
-  const int nPos = nTV * nTH;
-  const u32 nPix = (u32)g.tileElems;
-  u8* __restrict__ blob = WRITE ? arena + ti.offset : nullptr;
+  u8* __restrict__ blob = WRITE ? arena + ti.head.offset : nullptr;
   const T* __restrict__ px = data + (u64)t * g.tileElems;
 
-  if (WRITE && MB == 8 && blockIdx.x == gridDim.x - 1) { tmbWriteFront<T>(g, t, ti, px, blob, b); return; }
+  if constexpr (WRITE && MB == 8)
+  {
+    __shared__ u8 s_hdr[96];
+    __shared__ u32 s_w[4];
+    if (blockIdx.x == gridDim.x - 1) { tmbWriteFront<T>(g, t, ti, px, blob, b, s_hdr, s_w); return; }
+  }
   if (WRITE ? ti.kind != (MB == 8 ? kTmbKindBlocks8 : kTmbKindBlocks16) : (ti.kind != kTmbKindBlocks8 || (MB == 16 && !ti.retry))) return;
 
-  const int w = waveId(), lane = laneId();
+  const int w = waveId();
   const int pos = (int)blockIdx.x * 4 + w;
-  if (pos >= nPos) return;    // whole wave leaves together
+  if (pos >= nTV * nTH) return;    // whole wave leaves together
   p.mb = MB; p.nTV = nTV; p.nTH = nTH;
-  p.allValid = (ti.numValid == nPix) ? 1 : 0;
+  p.allValid = (ti.numValid == (u32)g.tileElems) ? 1 : 0;
   p.maxZErr = ti.maxZErr; p.scale = 1 / (2 * ti.maxZErr); p.invScale = 2 * ti.maxZErr;    // (the tile's own bound: k_tmb_prelude)
-  const u8* __restrict__ maskBits = b.bits + (u64)t * g.bitStride;
-  u32* __restrict__ table = MB == 8 ? b.blockOff + (u64)t * g.posStride : b.blockOff16 + (u64)t * g.pos16Stride;
-  const int it = pos / nTH, jt = pos - it * nTH;
-  const int i0 = it * MB, j0 = jt * MB;
-  const int tileH = min(MB, g.nRows - i0), tileW = min(MB, g.nCols - j0);
-  const int nElem = tileH * tileW;
-  const u64 lt = laneMaskLt();
-
-  int rank[E];
-  i64 pix[E];
-  T v[E];
-  u32 q[E];
-  int n = 0;
-#pragma unroll
-  for (int k = 0; k < E; k++)
-  {
-    const int e = k * 64 + lane;
-    const bool inb = e < nElem;
-    const int r = inb ? e / tileW : 0, c = inb ? e - r * tileW : 0;
-    pix[k] = (i64)(i0 + r) * g.nCols + (j0 + c);
-    const bool valid = inb && (p.allValid || maskBit(maskBits, pix[k]));
-    const u64 bal = __ballot(valid);
-    rank[k] = valid ? n + __popcll(bal & lt) : -1;
-    n += __popcll(bal);
-  }
-
-  if (n == 0)    // empty position: one "all zero" byte (Lerc2.cpp:1534-1538, :1960-1966)
-  {
-    if (WRITE) { if (lane == 0) blob[ti.dataBegin + table[pos]] = (u8)(((u32)(((j0 >> 3) & 15) << 2) & 0x38u) | 2u); }
-    else if (lane == 0) table[pos] = 1u;
-    return;
-  }
-  T* valBuf = s_val[w];
-#pragma unroll
-  for (int k = 0; k < E; k++)
-  {
-    v[k] = T(0);
-    if (rank[k] >= 0) { v[k] = px[pix[k]]; valBuf[rank[k]] = v[k]; }
-  }
-  waveSync();
-
-  // --- statistics (GetValidDataAndStats)
-  T mn = valBuf[0], mx = valBuf[0];
-#pragma unroll
-  for (int k = 0; k < E; k++)
-    if (rank[k] >= 0) { mn = (v[k] < mn) ? v[k] : mn; mx = (v[k] > mx) ? v[k] : mx; }
-  mn = waveMinT(mn);
-  mx = waveMaxT(mx);
-  int same = 0;
-#pragma unroll
-  for (int k = 0; k < E; k++)
-  {
-    bool s = false;
-    if (rank[k] > 0) s = (v[k] == valBuf[rank[k] - 1]);
-    else if (rank[k] == 0) s = p.allValid ? (v[k] == T(0)) : false;    // prevVal starts at 0 (all-valid branch only)
-    same += __popcll(__ballot(s));
-  }
-  const bool tryLut = (n > 4) && ((double)mx > (double)mn + 3 * p.maxZErr) && (2 * same > n);
-
-  double mv = 0;
-  bool quantOk = false;
-  if (p.maxZErr > 0)
-  {
-    mv = ((double)mx - (double)mn) * p.scale;
-    quantOk = !(mv > (double)p.maxQ || (u32)(mv + 0.5) == 0);
-  }
-  u32 qMax = 0;
-#pragma unroll
-  for (int k = 0; k < E; k++) q[k] = 0;
-  if (quantOk)
-  {
-#pragma unroll
-    for (int k = 0; k < E; k++)
-      if (rank[k] >= 0)
-      {
-        q[k] = p.intLossless ? quantLossless<T>(v[k], mn) : (u32)(((double)v[k] - (double)mn) * p.scale + 0.5);
-        qMax = q[k] > qMax ? q[k] : qMax;
-      }
-    qMax = waveMax(qMax);
-  }
-  u32 nDistinct = 0;
-  if (tryLut && quantOk)
-  {
-    u32 idxTmp[E];
-    nDistinct = extractDistinct<E>(q, rank, nullptr, idxTmp);
-  }
-  const Plan plan = planBlock<T>(p, n, mn, mx, p.dt, tryLut, mv, qMax, nDistinct);
-  if (!WRITE) { if (lane == 0) table[pos] = (u32)plan.nBytes; return; }
-
-  u32* obuf = s_obuf[w];
-  composeBlock<T, E>(obuf, s_lut[w], p, plan, n, j0, false, mn, v, q, rank, qMax);
-  const u8* ob8 = reinterpret_cast<const u8*>(obuf);
-  u8* __restrict__ dst = blob + ti.dataBegin + table[pos];
-  for (int i = lane; i < plan.nBytes; i += 64) dst[i] = ob8[i];
+  tbEncodeBlock<T, E, true, WRITE>(p, pos, px, b.bits + (u64)t * g.bitStride, MB == 8 ? b.blockOff + (u64)t * g.posStride : b.blockOff16 + (u64)t * g.pos16Stride,
+                                   WRITE ? blob + ti.dataBegin : nullptr, s_val[w], s_obuf[w], s_lut[w]);
 }
 
 // the 8 x 8 blocks' sizes scanned, and whether the low-bit-rate rule asks for the sizes of 16 x 16 blocks too
@@ -427,7 +327,7 @@ __global__ void __launch_bounds__(256) k_tmb_decide(TmbGeom g, u32 tb, TmbEncode
 {
   __shared__ u32 s_scan[257];
   const u32 t = blockIdx.x;
-  if (b.tiles[t].flags || b.tiles[t].kind != kTmbKindBlocks8) return;    // (neither is written in this kernel)
+  if (b.tiles[t].head.flags || b.tiles[t].kind != kTmbKindBlocks8) return;    // (neither is written in this kernel)
   const u32 nPos = (u32)(g.nTV * g.nTH);
   const u32 nBytesTiling = blockScanInPlace(b.blockOff + (u64)t * g.posStride, nPos, s_scan);
   if (threadIdx.x != 0) return;
@@ -446,7 +346,7 @@ __global__ void __launch_bounds__(256) k_tmb_decide2(TmbGeom g, u32 tb, u64 slot
   __shared__ u32 s_rec[3];
   const u32 t = blockIdx.x;
   // (the record is read once, in front of a barrier: thread 0 rewrites it further down)
-  if (threadIdx.x == 0) { s_rec[0] = b.tiles[t].flags; s_rec[1] = b.tiles[t].kind; s_rec[2] = b.tiles[t].retry; }
+  if (threadIdx.x == 0) { s_rec[0] = b.tiles[t].head.flags; s_rec[1] = b.tiles[t].kind; s_rec[2] = b.tiles[t].retry; }
   __syncthreads();
   if (s_rec[0]) return;
   const bool blocks = s_rec[1] == kTmbKindBlocks8, retry = blocks && s_rec[2];
@@ -458,47 +358,26 @@ __global__ void __launch_bounds__(256) k_tmb_decide2(TmbGeom g, u32 tb, u64 slot
   {
     if (retry && nBytes16 <= ti.nBytesTiling) { ti.kind = kTmbKindBlocks16; ti.mbSize = 16u; ti.nBytesTiling = nBytes16; }
     const u64 oneSweep = (u64)tb * ti.numValid;
-    if (oneSweep <= (u64)ti.nBytesTiling) { ti.kind = kTmbKindOneSweep; ti.blobSize = ti.dataBegin + (u32)oneSweep; }
-    else ti.blobSize = ti.dataBegin + ti.nBytesTiling;
+    if (oneSweep <= (u64)ti.nBytesTiling) { ti.kind = kTmbKindOneSweep; ti.head.blobSize = ti.dataBegin + (u32)oneSweep; }
+    else ti.head.blobSize = ti.dataBegin + ti.nBytesTiling;
   }
   if (slotBytes)
   {
-    ti.offset = (firstTile + t) * slotBytes;
-    if ((u64)ti.blobSize > slotBytes) ti.flags = kTmbCapacity;
+    ti.head.offset = (firstTile + t) * slotBytes;
+    if ((u64)ti.head.blobSize > slotBytes) ti.head.flags = kTbCapacity;
   }
 }
 
-// packed arena: the batch's blobs back to back at 16-byte aligned offsets from arenaBase on, in tile order
 __global__ void __launch_bounds__(256) k_tmb_arena(u32 nTiles, u64 arenaBase, u64 arenaCapacity, TmbEncodeBuffers b)
 {
   __shared__ u64 s_part[257];
-  const u32 per = (nTiles + 255u) / 256u, from = min(nTiles, threadIdx.x * per), to = min(nTiles, from + per);
-  u64 sum = 0;
-  for (u32 i = from; i < to; i++) if (!b.tiles[i].flags) sum += ((u64)b.tiles[i].blobSize + 15ull) & ~15ull;
-  s_part[threadIdx.x] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) { u64 run = 0; for (u32 i = 0; i < 256u; i++) { const u64 y = s_part[i]; s_part[i] = run; run += y; } s_part[256] = run; }
-  __syncthreads();
-  u64 run = arenaBase + s_part[threadIdx.x];
-  for (u32 i = from; i < to; i++)
-  {
-    TmbTile& ti = b.tiles[i];
-    if (ti.flags) continue;
-    ti.offset = run;
-    if (run + ti.blobSize > arenaCapacity) ti.flags |= kTmbArenaFull;
-    run += ((u64)ti.blobSize + 15ull) & ~15ull;
-  }
+  tbArenaPlace(b.tiles, nTiles, arenaBase, arenaCapacity, s_part);
 }
 
 __global__ void __launch_bounds__(256) k_tmb_checksum(u8* __restrict__ arena, TmbEncodeBuffers b)
 {
   __shared__ u64 s_red[4];
-  const TmbTile ti = b.tiles[blockIdx.x];
-  if (ti.flags) return;
-  u8* __restrict__ blob = arena + ti.offset;
-  u64 A, B;
-  blockFletcher(blob + 14, ti.blobSize - 14u, s_red, A, B);
-  if (threadIdx.x == 0) putBytes(blob + 10, (u64)fletcherFold(A, B, ti.blobSize - 14u), 4);
+  tbWriteChecksum(arena, b.tiles[blockIdx.x].head, s_red);
 }
 
 template<class T>
@@ -569,81 +448,74 @@ k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
     TmbTile ti;
     memset(&ti, 0, sizeof(ti));
     u32 fl = 0, nm = 0;
-    if (sizeGiven < kHdr6 + 4u) fl = kTmbHeader;
+    if (sizeGiven < kHdr6 + 4u) fl = kTbHeader;
     else
     {
-      const char magic[6] = { 'L', 'e', 'r', 'c', '2', ' ' };
-      for (int i = 0; i < 6; i++) if (blob[i] != (u8)magic[i]) fl = kTmbHeader;
-      int ints[10];
-      for (int i = 0; i < 10; i++) ints[i] = (int)(u32)getBytes(blob + 6 + 4 * i, 4);
-      double dbl[3];
-      for (int i = 0; i < 3; i++) { const u64 bits = getBytes(blob + 50 + 8 * i, 8); memcpy(&dbl[i], &bits, 8); }
-      const u32 flagBytes = (u32)getBytes(blob + 46, 4);    // passNoData, isInt, reserved
-      ti.checksum = (u32)ints[1];
-      ti.numValid = (u32)ints[5];
-      ti.blobSize = (u32)ints[7];
-      ti.maxZErr = dbl[0]; ti.zMin = dbl[1]; ti.zMax = dbl[2];
-      if (ints[0] != kCodecVersion || ints[2] != g.nRows || ints[3] != g.nCols || ints[4] != 1 || ints[5] < 0 || (u32)ints[5] > nPix
-        || (ints[6] != 8 && ints[6] != 16) || ints[7] < (int)(kHdr6 + 4u) || (u32)ints[7] > sizeGiven || ints[8] != g.dt || ints[9] != 0 || (flagBytes & 0xFFu) != 0u)
-        fl = kTmbHeader;
+      TbHeader6 h;
+      if (!tbReadHeader6(blob, h)) fl = kTbHeader;
+      ti.checksum = h.checksum;
+      ti.numValid = (u32)h.numValid;
+      ti.head.blobSize = (u32)h.blobSize;
+      ti.maxZErr = h.maxZErr; ti.zMin = h.zMin; ti.zMax = h.zMax;
+      if (h.version != kCodecVersion || h.nRows != g.nRows || h.nCols != g.nCols || h.nDepth != 1 || h.numValid < 0 || (u32)h.numValid > nPix
+        || (h.microBlockSize != 8 && h.microBlockSize != 16) || h.blobSize < (int)(kHdr6 + 4u) || (u32)h.blobSize > sizeGiven || h.dt != g.dt || h.nBlobsMore != 0
+        || (h.flagBytes & 0xFFu) != 0u)
+        fl = kTbHeader;
+      const int mbSize = h.microBlockSize;
       if (!fl)
       {
         nm = (u32)getBytes(blob + kHdr6, 4);
         const bool noStream = ti.numValid == nPix || ti.numValid == 0u;
-        if (noStream ? nm != 0u : (nm < 2u || nm > ti.blobSize)) fl = kTmbHeader;
+        if (noStream ? nm != 0u : (nm < 2u || nm > ti.head.blobSize)) fl = kTbHeader;
         else if (ti.numValid == 0u)
         {
           // no valid pixel: nothing may follow the mask section's length (Lerc2.cpp:235-241); range and error bound are not asked
           ti.kind = kTmbKindEmpty;
-          if (ti.blobSize != kHdr6 + 4u) fl = kTmbHeader;
+          if (ti.head.blobSize != kHdr6 + 4u) fl = kTbHeader;
         }
         else if (ti.zMin == ti.zMax)
         {
           // every valid pixel is (T)zMin (Lerc2.cpp:255, FillConstImage): nothing may follow the mask section
           ti.kind = kTmbKindConst;
-          if ((u64)ti.blobSize != (u64)kHdr6 + 4u + nm || !tmbIsValueOf<T>(ti.zMin)) fl = kTmbHeader;
+          if ((u64)ti.head.blobSize != (u64)kHdr6 + 4u + nm || !tmbIsValueOf<T>(ti.zMin)) fl = kTbHeader;
           ti.minBits = typedBits(ti.zMin, g.dt);
         }
-        else if (!(ti.zMin < ti.zMax) || (u64)kHdr6 + 4u + nm + 2u * TB + 1u >= (u64)ti.blobSize) fl = kTmbHeader;    // (NaN fails every comparison)
+        else if (!(ti.zMin < ti.zMax) || (u64)kHdr6 + 4u + nm + 2u * TB + 1u >= (u64)ti.head.blobSize) fl = kTbHeader;    // (NaN fails every comparison)
         else
         {
           const u8* r = blob + kHdr6 + 4u + nm;
           ti.minBits = getBytes(r, (int)TB); ti.maxBits = getBytes(r + TB, (int)TB);
           ti.dataBegin = kHdr6 + 4u + nm + 2u * TB + 1u;
-          if (ti.minBits == ti.maxBits) fl = kTmbHeader;    // (constant by its ranges)
+          if (ti.minBits == ti.maxBits) fl = kTbHeader;    // (constant by its ranges)
           else if (r[2 * TB] == 1)
           {
             // one sweep: the blob ends behind numValid raw values (Lerc2::ReadDataOneSweep); the mask's own count is compared below
             ti.kind = kTmbKindOneSweep;
-            if ((u64)ti.dataBegin + (u64)ti.numValid * TB != (u64)ti.blobSize) fl = kTmbHeader;
+            if ((u64)ti.dataBegin + (u64)ti.numValid * TB != (u64)ti.head.blobSize) fl = kTbHeader;
           }
-          else if (r[2 * TB] != 0) fl = kTmbHeader;
+          else if (r[2 * TB] != 0) fl = kTbHeader;
           else
           {
-            ti.kind = ints[6] == 16 ? kTmbKindBlocks16 : kTmbKindBlocks8;
+            ti.kind = mbSize == 16 ? kTmbKindBlocks16 : kTmbKindBlocks8;
             // (an error bound of 0 is the lossless float mode or a stream this decoder has not been pinned on)
-            if (!(ti.maxZErr > 0) || !(ti.maxZErr < 1e300)) fl = kTmbHeader;
+            if (!(ti.maxZErr > 0) || !(ti.maxZErr < 1e300)) fl = kTbHeader;
           }
         }
         ti.rleLen = nm;
       }
     }
-    ti.flags = fl;
+    ti.head.flags = fl;
     s_ti = ti; s_flags = fl; s_nm = nm;
   }
   __syncthreads();
   if (s_flags) { if (threadIdx.x == 0) b.tiles[t] = s_ti; return; }
-  const u32 blobEnd = s_ti.blobSize, nm = s_nm, kind = s_ti.kind;
+  const u32 blobEnd = s_ti.head.blobSize, nm = s_nm, kind = s_ti.kind;
 
   // ---- Fletcher32 over blob[14 .. blobSize)
+  if (!tbChecksumOk(blob, blobEnd, s_ti.checksum, s_red))
   {
-    u64 A, B;
-    blockFletcher(blob + 14, blobEnd - 14u, s_red, A, B);
-    if (fletcherFold(A, B, blobEnd - 14u) != s_ti.checksum)
-    {
-      if (threadIdx.x == 0) { s_ti.flags = kTmbChecksum; b.tiles[t] = s_ti; }
-      return;
-    }
+    if (threadIdx.x == 0) { s_ti.head.flags = kTbChecksum; b.tiles[t] = s_ti; }
+    return;
   }
 
   // ---- the mask: all ones, all zeros, or the run-length stream expanded (rleDecode, codec_common.cpp: what it does not fill stays zero)
@@ -670,7 +542,7 @@ k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
     if (!ok) s_flags = kTmbMaskStream;
   }
   __syncthreads();
-  if (s_flags) { if (threadIdx.x == 0) { s_ti.flags = s_flags; b.tiles[t] = s_ti; } return; }
+  if (s_flags) { if (threadIdx.x == 0) { s_ti.head.flags = s_flags; b.tiles[t] = s_ti; } return; }
 
   T* __restrict__ out = outAll + (u64)t * g.tileElems;
   if (kind == kTmbKindConst || kind == kTmbKindOneSweep)
@@ -689,7 +561,7 @@ k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
     }
     if ((u32)blockSum((u64)cnt, s_red) != s_ti.numValid)
     {
-      if (threadIdx.x == 0) { s_ti.flags = kTmbHeader; b.tiles[t] = s_ti; }
+      if (threadIdx.x == 0) { s_ti.head.flags = kTbHeader; b.tiles[t] = s_ti; }
       return;
     }
     tmbRankedSweep(s_bits, nPix, s_w, [&](u32 k, bool valid, u32 rank)
@@ -727,29 +599,13 @@ k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
   }
   __syncthreads();
 
-  // ---- the walk: block k + 1 starts where block k ends; a block's length follows from its header and its valid count
+  // ---- the walk: a block's length follows from its header and its valid count
   if (threadIdx.x == 0)
   {
-    BandParams p;
-    memset(&p, 0, sizeof(p));
-    p.nRows = g.nRows; p.nCols = g.nCols; p.nDepth = 1; p.mb = (int)MB; p.nTV = (int)nTV; p.nTH = (int)nTH; p.dt = g.dt; p.version = kCodecVersion;
     u32* __restrict__ table = b.blockOff + (u64)t * g.posStride;
-    const u32 pattern = 14u;    // codec >= 5: bit 2 of the flag is the difference flag
-    u32 pos = s_ti.dataBegin, fl = 0;
-    for (u32 k = 0; k < nPos; k++)
-    {
-      table[k] = pos;
-      const u32 it = k / nTH, jt = k - it * nTH;
-      const u32 nElem = min(MB, (u32)g.nRows - it * MB) * min(MB, (u32)g.nCols - jt * MB);
-      BlkInfo bi;
-      const int rc = parseBlock<(int)TB>(blob, pos, blobEnd, p, (int)s_nv[k], nElem, bi);
-      // (a block of a position without valid pixels is the one "all zero" byte)
-      if (rc != 0 || bi.len == 0 || (((u32)bi.flag >> 2) & pattern) != (((jt * MB) >> 3) & pattern) || bi.diff || (s_nv[k] == 0 && bi.mode != 2)) { fl = kTmbBlocks; break; }
-      pos += bi.len;
-    }
-    if (!fl && pos != blobEnd) fl = kTmbBlocks;
-    table[nPos] = pos;
-    s_ti.flags = fl;
+    auto nValidOf = [&](u32 k, u32) { return (int)s_nv[k]; };
+    s_ti.head.flags = MB == 16u ? tbWalkBlocks<(int)TB, 16u>(blob, s_ti.dataBegin, blobEnd, tbFillBandParams(g, 16), table, nValidOf)
+                                : tbWalkBlocks<(int)TB, 8u>(blob, s_ti.dataBegin, blobEnd, tbFillBandParams(g, 8), table, nValidOf);
     b.tiles[t] = s_ti;
   }
 }
@@ -764,97 +620,17 @@ k_tmbd_blocks(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ o
   __shared__ u32 s_lut[4][256];
   __shared__ __align__(16) u8 s_head[4][64];
   const u32 t = blockIdx.y;
-  if (b.tiles[t].flags & ~kTmbSibling) return;    // (whatever the parse kernel raised; a sibling wave's kTmbSibling: nothing to gain from leaving)
+  if (b.tiles[t].head.flags & ~kTbSibling) return;    // (whatever the parse kernel raised; a sibling wave's kTbSibling: nothing to gain from leaving)
   if (b.tiles[t].kind != (MB == 8 ? kTmbKindBlocks8 : kTmbKindBlocks16)) return;
-  const int w = waveId(), lane = laneId();
+  const int w = waveId();
   const int pos = (int)blockIdx.x * 4 + w;
-  const int nTV = (g.nRows + MB - 1) / MB, nTH = (g.nCols + MB - 1) / MB;
-  if (pos >= nTV * nTH) return;
-  const u32 blobEnd = b.tiles[t].blobSize;
-  const u32 nPix = (u32)g.tileElems;
-  BandParams p;
-  memset(&p, 0, sizeof(p));
-  p.nRows = g.nRows; p.nCols = g.nCols; p.nDepth = 1; p.mb = MB; p.nTV = nTV; p.nTH = nTH; p.dt = g.dt; p.version = kCodecVersion;
-  p.allValid = (b.tiles[t].numValid == nPix) ? 1 : 0;
+  if (pos >= ((g.nRows + MB - 1) / MB) * ((g.nCols + MB - 1) / MB)) return;
+  BandParams p = tbFillBandParams(g, MB);
+  p.allValid = (b.tiles[t].numValid == (u32)g.tileElems) ? 1 : 0;
   p.invScale = 2 * b.tiles[t].maxZErr;
-  const double zMax = b.tiles[t].zMax;
-  const u8* __restrict__ blob = arena + offsets[t];
-  const u8* __restrict__ maskBits = b.bits + (u64)t * g.bitStride;
-  T* __restrict__ out = outAll + (u64)t * g.tileElems;
-  const int it = pos / nTH, jt = pos - it * nTH;
-  const int i0 = it * MB, j0 = jt * MB;
-  const int tileH = min(MB, g.nRows - i0), tileW = min(MB, g.nCols - j0);
-  const int nElem = tileH * tileW;
-  const u64 lt = laneMaskLt();
-
-  int rank[E];
-  i64 px[E];
-  int nValid = 0;
-#pragma unroll
-  for (int k = 0; k < E; k++)
-  {
-    const int e = k * 64 + lane;
-    const bool inb = e < nElem;
-    const int r = inb ? e / tileW : 0, c = inb ? e - r * tileW : 0;
-    px[k] = inb ? (i64)(i0 + r) * g.nCols + (j0 + c) : -1;
-    const bool valid = inb && (p.allValid || maskBit(maskBits, px[k]));
-    const u64 bal = __ballot(valid);
-    rank[k] = valid ? nValid + __popcll(bal & lt) : -1;
-    nValid += __popcll(bal);
-  }
-
-  const u32 off = b.blockOff[(u64)t * g.posStride + pos];
-  s_head[w][lane] = ((u64)off + (u64)lane < (u64)blobEnd) ? blob[(u64)off + lane] : (u8)0;
-  waveSync();
-  BlkInfo bi;
-  const int rc = (off < blobEnd) ? parseBlockWords<(int)sizeof(T)>(reinterpret_cast<const u32*>(s_head[w]), 0u, blobEnd - off, p, nValid, (u32)nElem, bi) : 1;
-  bool failed = rc != 0 || (((u32)bi.flag >> 2) & 14u) != (((u32)j0 >> 3) & 14u) || bi.diff;
-  if (!failed)
-  {
-    double offset = 0;
-    if (bi.mode == 1 || bi.mode == 3) offset = typedFromBits(getBytes(s_head[w] + 1, bi.offBytes), bi.dtUsed);
-    const u64 payloadBit = 8ull * ((u64)off + bi.payload);
-    const int nbIdx = bi.lut ? bitLen(bi.nLut) : 0;
-    u64 idxBit = 0;
-    if (bi.mode == 1 && bi.lut)
-    {
-      s_lut[w][0] = 0;
-      for (u32 i = (u32)lane; i < bi.nLut; i += 64) s_lut[w][i + 1] = unstuffElement(blob, payloadBit, i, bi.nb, bi.nLut, blobEnd, p.version);
-      idxBit = payloadBit + 8ull * (((u64)bi.nLut * bi.nb + 7) >> 3);
-      waveSync();
-    }
-    bool badIdx = false;
-#pragma unroll
-    for (int k = 0; k < E; k++)
-    {
-      T val = T(0);
-      if (rank[k] >= 0)
-      {
-        if (bi.mode == 2) val = T(0);
-        else if (bi.mode == 0)
-        {
-          const u64 bits = getBytes(blob + off + 1 + (u64)rank[k] * sizeof(T), (int)sizeof(T));
-          memcpy(&val, &bits, sizeof(T));
-        }
-        else if (bi.mode == 3) val = (T)offset;
-        else
-        {
-          u32 q;
-          if (!bi.lut) q = unstuffElement(blob, payloadBit, (u32)rank[k], bi.nb, bi.cnt, blobEnd, p.version);
-          else
-          {
-            const u32 ix = unstuffElement(blob, idxBit, (u32)rank[k], nbIdx, bi.cnt, blobEnd, p.version);
-            if (ix > bi.nLut) { badIdx = true; q = 0; } else q = s_lut[w][ix];
-          }
-          const double z = offset + (double)q * p.invScale;
-          val = (T)(z < zMax ? z : zMax);    // std::min(z, zMax)
-        }
-      }
-      if (px[k] >= 0) out[px[k]] = val;
-    }
-    failed = __any(badIdx);
-  }
-  if (failed && lane == 0) atomicOr(&b.tiles[t].flags, kTmbSibling);
+  const bool failed = tbDecodeBlock<T, E, true>(p, b.tiles[t].zMax, pos, arena + offsets[t], b.tiles[t].head.blobSize, b.blockOff[(u64)t * g.posStride + pos],
+                                                b.bits + (u64)t * g.bitStride, outAll + (u64)t * g.tileElems, s_lut[w], s_head[w]);
+  if (failed && laneId() == 0) atomicOr(&b.tiles[t].head.flags, kTbSibling);
 }
 
 template<class T>

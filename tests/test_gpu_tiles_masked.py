@@ -80,3 +80,9 @@ def test_errors(batch):
 def test_soak():
     P, R = _libs()
     C.check_soak(P.lib, C.GpuMem(), R, rounds=20, max_tiles=96, r=64, c=64)
+
+
+def test_sub_batches(batch):
+    """sub-batches of 3 + 3 + 1 tiles, a tile handed back in the second one"""
+    _, R = _libs()
+    C.check_sub_batches(batch, R)

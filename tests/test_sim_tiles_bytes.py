@@ -78,3 +78,8 @@ def test_errors(libs, batch):
 
 def test_soak(libs):
     C.check_soak(libs[0].lib, C.HostMem(), libs[1], rounds=6, max_tiles=10, size=384, tile=32)
+
+
+def test_sub_batches(libs, batch):
+    """sub-batches of 3 + 3 + 1 tiles, a tile handed back in the second one"""
+    C.check_sub_batches(batch, libs[1])

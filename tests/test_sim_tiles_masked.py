@@ -82,3 +82,8 @@ def test_counters_of_the_unmasked_batch(batch):
     rc, blobs, _, _, _ = batch.encode(tiles, None, e, unmasked_call=True)
     c1 = batch.counters()
     assert rc == 0 and (c1[0] - c0[0]) + (c1[1] - c0[1]) == len(tiles)
+
+
+def test_sub_batches(libs, batch):
+    """sub-batches of 3 + 3 + 1 tiles, a tile handed back in the second one"""
+    C.check_sub_batches(batch, libs[1])

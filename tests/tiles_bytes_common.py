@@ -7,7 +7,7 @@ import struct
 import numpy as np
 
 import tiles_masked_common as M
-from tiles_masked_common import Batch, HostMem, GpuMem, check_layout, ref_blobs, resign    # noqa: F401
+from tiles_masked_common import Batch, HostMem, GpuMem, check_layout, ref_blobs, resign, sub_batches_of    # noqa: F401
 
 AT = 96    # the one-sweep byte of an all-valid single-band codec 6 byte blob; the mode byte follows
 
@@ -224,3 +224,26 @@ def check_soak(L, mem, R, rounds, max_tiles, size, tile):
             check_decode(B, R, want, (r, c), np.uint8)
         finally:
             B.close()
+
+
+def check_sub_batches(B, R, r=40, c=56):
+    """7 tiles in sub-batches of 3 + 3 + 1 (LERC_AMD_TEST_TILE_SUBBATCH), packed and slotted: the first tile and the arena's base of a
+    LATER sub-batch, and a tile done again behind one -- tile 4, in the second sub-batch, is constant: the batch hands it back, each way"""
+    rng = np.random.default_rng(47)
+    n = 7
+    yy, xx = np.mgrid[0:r, 0:c]
+    tiles = np.stack([np.clip(np.round(128 + 100 * np.sin(yy / rng.uniform(9, 40)) * np.cos(xx / rng.uniform(9, 40)) + rng.normal(0, rng.uniform(2, 6), (r, c))),
+                              0, 255).astype(np.uint8) for _ in range(n)])
+    tiles[4][:] = 77
+    want = ref_blobs(R, tiles, None, 0)
+    assert sum(must_batch(w, r * c) for w in want) == n - 1, "every tile but the constant one is the batch's own"
+    with sub_batches_of(3):
+        for slot in (0, slot_for(tiles)):
+            c0 = B.counters()
+            check_encode(B, R, tiles, want=want, slot_bytes=slot)
+            c1 = B.counters()
+            assert (c1[0] - c0[0], c1[1] - c0[1]) == (n - 1, 1), (c0, c1, B.note())
+        c0 = B.counters()
+        assert np.array_equal(check_decode(B, R, want, (r, c), np.uint8), tiles)
+        c1 = B.counters()
+        assert (c1[2] - c0[2], c1[3] - c0[3]) == (n - 1, 1), (c0, c1, B.note())

@@ -3,7 +3,9 @@ batch calls of include/lerc_amd_device.h, the "island" mosaic, and the rule for 
 
 Memory: the emulator's "device" pointers are host pointers (numpy), the product's are HIP allocations (torch uint8 tensors).
 """
+import contextlib
 import ctypes as ct
+import os
 import struct
 
 import numpy as np
@@ -35,6 +37,20 @@ def bind(L):
     L.lerc_amd_decode_device.restype = u32
     L.lerc_amd_decode_device.argtypes = [vp, vp, u32, ct.c_int, vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, u32, vp]
     return L
+
+
+@contextlib.contextmanager
+def sub_batches_of(n):
+    """LERC_AMD_TEST_TILE_SUBBATCH=n around the calls inside (the library reads it per call), then as it was"""
+    old = os.environ.get("LERC_AMD_TEST_TILE_SUBBATCH")
+    os.environ["LERC_AMD_TEST_TILE_SUBBATCH"] = str(n)
+    try:
+        yield
+    finally:
+        if old is None:
+            del os.environ["LERC_AMD_TEST_TILE_SUBBATCH"]
+        else:
+            os.environ["LERC_AMD_TEST_TILE_SUBBATCH"] = old
 
 
 class HostMem:
@@ -510,3 +526,34 @@ def check_fresh_contexts(L, mem, R, rounds, n, r, c):
             check_decode(B, R, want, (r, c), dtype)
         finally:
             B.close()
+
+
+def check_sub_batches(B, R, r=40, c=56):
+    """7 tiles in sub-batches of 3 + 3 + 1 (LERC_AMD_TEST_TILE_SUBBATCH), packed and slotted: the first tile and the arena's base of a
+    LATER sub-batch, and a tile done again behind one.  Tile 4, in the second sub-batch, has a NaN at a valid pixel: the encoding batch
+    hands it back.  Its blob is an ordinary one (the reference makes the pixel invalid), which the decoding batch must take; so the
+    blobs are decoded a second time with tile 4's replaced by the reference's lossless blob (maxZErr 0 on float values), which the
+    decoding batch hands back."""
+    rng = np.random.default_rng(43)
+    n, e = 7, 0.01
+    tiles = (terrain_int(rng, n, r, c, np.int32) + rng.normal(0, 0.3, (n, r, c))).astype(np.float32)
+    masks = random_blob_mask(rng, n, r, c)
+    tiles[4, r // 2, c // 2] = np.nan
+    masks[4, r // 2, c // 2] = 1
+    want = ref_blobs(R, tiles, masks, e)
+    with sub_batches_of(3):
+        for slot in (0, (tiles[0].nbytes + r * c // 4 + 1024 + 15) & ~15):
+            c0 = B.counters()
+            check_encode(B, R, tiles, masks, e, slot, want, cap_counters=False)
+            c1 = B.counters()
+            assert (c1[0] - c0[0], c1[1] - c0[1]) == (n - 1, 1), (c0, c1, B.note())
+        c0 = B.counters()
+        check_decode(B, R, want, (r, c), np.float32)
+        c1 = B.counters()
+        assert (c1[2] - c0[2], c1[3] - c0[3]) == (n, 0), (c0, c1, B.note())
+        rc, lossless = R.encode(tiles[3], 0, mask=masks[3])
+        assert rc == 0
+        blobs = want[:4] + [lossless] + want[5:]
+        check_decode_plain(B, R, blobs, (r, c), np.float32)
+        c2 = B.counters()
+        assert (c2[2] - c1[2], c2[3] - c1[3]) == (n - 1, 1), (c1, c2, B.note())
