@@ -88,8 +88,14 @@ LERC_AMD_API lerc_status lerc_amd_decode_tiles_device_slots(lerc_amd_context* ct
  * take float32, float64 and the 16- and 32-bit integer types, tiles of up to 131 072 pixels and 4 096 blocks (256 x 256, 257 x 257), and
  * write header, mask section (run-length coded on the device), ranges, block stream and checksum -- of tiles without a valid pixel
  * (header only), constant tiles (header and mask section), one-sweep tiles (the valid pixels raw) and tiles whose low-bit-rate retry
- * ends in 16 x 16 blocks as well.  A tile with a NaN at a valid pixel (its mask changes), and 8-bit types WITH a mask pointer, larger
- * tiles, maxZErr == 777 or 0 on float values are encoded inside the call, one by one, with the same result (8-bit tiles with dValidBytes == NULL are the 8-bit batch described above).  Status codes as for the unmasked calls. */
+ * ends in 16 x 16 blocks as well.  8-bit tiles (int8 / uint8, maxZErr < 1) WITH a mask pointer are a batch too, the masked form of the
+ * 8-bit batch described above: the mask section, both Huffman code books over the valid pixels (the reference's masked predictor), the
+ * mode choice, 8 x 8 blocks, table, pixel stream and checksum are made on the device, for partly valid, all-valid and empty tiles
+ * alike; handed back and encoded one by one inside the call, same bytes: constant tiles (a single valid pixel included), one sweep,
+ * tiles whose 16 x 16 blocks win, a blob that does not fit (lerc_amd_last_note names the reason).  A tile with a NaN at a valid pixel
+ * (its mask changes), larger tiles, 8-bit tiles at maxZErr >= 1, maxZErr == 777 or 0 on float values are encoded inside the call, one
+ * by one, with the same result (8-bit tiles with dValidBytes == NULL are the 8-bit batch described above).  Status codes as for the
+ * unmasked calls. */
 LERC_AMD_API lerc_status lerc_amd_encode_tiles_device_masked(lerc_amd_context* ctx, const void* dTiles, unsigned int dataType, int nCols, int nRows,
     int nTiles, const unsigned char* dValidBytes, double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity,
     unsigned long long slotBytes, unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed);
@@ -98,8 +104,10 @@ LERC_AMD_API lerc_status lerc_amd_encode_tiles_device_masked(lerc_amd_context* c
  * mask).  Pixels: exactly what lerc_amd_decode_device writes for that blob (0 at invalid pixels).  The batch's launches take codec 6
  * blobs of the types and sizes above, with or without a mask section: blocks of 8 x 8 or 16 x 16, one sweep, constant and empty blobs;
  * every other blob (older codecs, damaged, or one the batch's parse is not certain of: bytes behind the last section, a mask whose count
- * of valid pixels is not the header's ...) is decoded by itself inside the call.  A blob that fails leaves its tile zeroed, mask
- * too; the other tiles are decoded all the same, and the call returns the first such status. */
+ * of valid pixels is not the header's ...) is decoded by itself inside the call.  8-bit blobs (maxZErr 0.5 in the header), with or
+ * without a mask section, in a Huffman mode or with 8 x 8 blocks, and 8-bit blobs without a valid pixel, are the masked 8-bit batch's;
+ * constant, one-sweep and 16 x 16 ones go one by one.  A blob that fails leaves its tile zeroed, mask too; the other tiles are
+ * decoded all the same, and the call returns the first such status. */
 LERC_AMD_API lerc_status lerc_amd_decode_tiles_device_masked(lerc_amd_context* ctx, const unsigned char* dArena, const unsigned long long* offsets,
     const unsigned int* sizes, int nTiles, int nCols, int nRows, unsigned int dataType, void* dTiles, unsigned char* dValidBytes);
 /* Diagnostics of the tile batch calls (masked or not): out[0] tiles whose blob the batch's own launches made, out[1] tiles encoded one by

@@ -1,10 +1,10 @@
 // codec_tiles_batch.cpp -- host side of the tile batches that do a mosaic's tiles in ONE set of launches and one host wait per sub-batch:
 // the masked batch (lerc_amd_encode_tiles_device_masked / lerc_amd_decode_tiles_device_masked; kernels in tile_mask_batch.hip) and the
-// 8-bit batch (DT_Char / DT_Byte, every pixel valid, lossless, through the tile batch calls; kernels in tile_byte_batch.hip).  One
-// driver, tbEncode / tbDecode, runs both: the sub-batches, the workspace, the records' way home, the arena's bookkeeping.  Tiles the
-// kernels hand back (TileBatchRec::flags) are done one by one behind their sub-batch by encodeDevice / decodeDevice -- byte for byte
-// what those calls make, and their exact status.  A family (MaskedBatch, BytesBatch) supplies what differs: its workspace, its
-// launches, whether a tile by itself carries a mask, its words for a reason.
+// 8-bit batch (DT_Char / DT_Byte, lossless, through the tile batch calls; kernels in tile_byte_batch.hip) -- every pixel valid, or, through
+// the masked calls, with a mask per tile.  One driver, tbEncode / tbDecode, runs them all: the sub-batches, the workspace, the records'
+// way home, the arena's bookkeeping.  Tiles the kernels hand back (TileBatchRec::flags) are done one by one behind their sub-batch
+// by encodeDevice / decodeDevice -- byte for byte what those calls make, and their exact status.  A family (MaskedBatch, BytesBatch,
+// BytesMaskedBatch) supplies what differs: its workspace, its launches, whether a tile by itself carries a mask, its words for a reason.
 #include "codec.h"
 #include "tile_mask_batch.h"
 #include "tile_byte_batch.h"
@@ -145,8 +145,8 @@ struct BytesBatch
   static constexpr size_t kRecBytes = sizeof(TbbTile);
 
   TbbGeom g;
-  TbbEncodeBuffers eb;
-  TbbDecodeBuffers db;
+  TbbEncodeBuffers eb = {};
+  TbbDecodeBuffers db = {};
 
   BytesBatch(int dt, int nRows, int nCols) : g(tileGeom<TbbGeom>(dt, nRows, nCols)) {}
 
@@ -199,6 +199,68 @@ struct BytesBatch
     if (flags & (kTbBlocks | kTbSibling)) return "the block stream";
     if (flags & kTbbStream) return "the pixel stream is short";
     return "unknown";
+  }
+};
+
+// ---- the 8-bit family's masked form: the same launch set with the mask's workspace behind it (tile_byte_batch.h: TbbMaskBuffers)
+struct BytesMaskedBatch : BytesBatch
+{
+  static constexpr bool kMasked = true;
+  static constexpr const char* kName = "masked 8-bit";
+  static constexpr const char* kLaunchError = "lerc_amd: a masked 8-bit tile batch kernel could not be launched";
+  static constexpr const char* kEncodeScope = "tiles_bytes_masked_encode";
+  static constexpr const char* kDecodeScope = "tiles_bytes_masked_decode";
+
+  u32 bitStride, rleStride, pos16Stride;
+
+  BytesMaskedBatch(int dt, int nRows, int nCols) : BytesBatch(dt, nRows, nCols)
+  {
+    const u32 nBytes = (u32)((g.tileElems + 7) >> 3);
+    bitStride = (nBytes + 16u + 15u) & ~15u;
+    rleStride = (2u * nBytes + 64u + 15u) & ~15u;    // (no stream is longer: MaskedBatch)
+    pos16Stride = ((u32)(((nRows + 15) / 16) * ((nCols + 15) / 16)) + 1u + 3u) & ~3u;
+  }
+
+  size_t encodeBytesPerTile() const { return BytesBatch::encodeBytesPerTile() + sizeof(TbbMaskRec) + bitStride + rleStride + (size_t)pos16Stride * 4 + 32; }
+  size_t decodeBytesPerTile() const { return BytesBatch::decodeBytesPerTile() + sizeof(TbbMaskRec) + bitStride + (size_t)g.tileElems + 32; }
+
+  void* carveEncode(Context& ctx, size_t n)
+  {
+    void* rec = BytesBatch::carveEncode(ctx, n);
+    eb.m.rec = ctx.allocT<TbbMaskRec>(n);
+    eb.m.bits = ctx.allocT<u8>(n * bitStride);
+    eb.m.rle = ctx.allocT<u8>(n * rleStride);
+    eb.m.blockOff16 = ctx.allocT<u32>(n * pos16Stride);
+    eb.m.bitStride = bitStride; eb.m.rleStride = rleStride; eb.m.pos16Stride = pos16Stride;
+    return (eb.m.rec && eb.m.bits && eb.m.rle && eb.m.blockOff16) ? rec : nullptr;
+  }
+  void* carveDecode(Context& ctx, size_t n)
+  {
+    void* rec = BytesBatch::carveDecode(ctx, n);
+    db.m.rec = ctx.allocT<TbbMaskRec>(n);
+    db.m.bits = ctx.allocT<u8>(n * bitStride);
+    db.m.sym = ctx.allocT<u8>(n * (size_t)g.tileElems);
+    db.m.bitStride = bitStride; db.m.rleStride = 0;
+    return (db.m.rec && db.m.bits && db.m.sym) ? rec : nullptr;
+  }
+  void launchEncode(u32 n, double maxZErr, const void* dTiles, const u8* dValid, u8* dArena, u64 arenaBase, u64 arenaCapacity, u64 slotBytes, u64 firstTile,
+                    hipStream_t st)
+  {
+    eb.m.valid = const_cast<u8*>(dValid);    // (read only: k_tbb_stats)
+    BytesBatch::launchEncode(n, maxZErr, dTiles, dValid, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, st);
+  }
+  void launchDecode(u32 n, const u8* dArena, const u64* dOff, const u32* dSize, void* dTiles, u8* dValid, hipStream_t st)
+  {
+    db.m.valid = dValid;
+    BytesBatch::launchDecode(n, dArena, dOff, dSize, dTiles, dValid, st);
+  }
+
+  static const char* reason(u32 flags)
+  {
+    if (flags & kTbbConst) return "a constant tile";
+    if (flags & kTbbRle) return "the mask's run-length stream outgrew its scratch";
+    if (flags & kTbbMaskStream) return "the mask's run-length stream is damaged";
+    return BytesBatch::reason(flags);
   }
 };
 
@@ -399,6 +461,8 @@ u32 encodeTilesDeviceMasked(Context& ctx, const TilesEncodeRequest& rq, u64& are
     || rq.maxZErr < 0 || (rq.slotBytes & 15u) != 0)
     return kWrongParam;
   // (an error bound of 0 on float values is the lossless float mode's business, 777 the bit plane mode's)
+  // (8-bit tiles, lossless: the 8-bit family's masked form; from maxZErr 1 on they have no Huffman mode and go one by one)
+  if (rq.maxZErr < 1 && tbbShapeOk(rq.dt, rq.nRows, rq.nCols)) return tbEncode<BytesMaskedBatch>(ctx, rq, arenaUsed, true);
   const bool batchOk = tmbShapeOk(rq.dt, rq.nRows, rq.nCols) && rq.maxZErr != 777 && !(rq.dt >= DT_Float && rq.maxZErr == 0);
   return tbEncode<MaskedBatch>(ctx, rq, arenaUsed, batchOk);
 }
@@ -408,6 +472,7 @@ u32 decodeTilesDeviceMasked(Context& ctx, const TilesDecodeRequest& rq)
   if (!rq.dValidBytes) return decodeTilesDevice(ctx, rq);
   if (!rq.dArena || !rq.hOffsets || !rq.hSizes || !rq.dOut || rq.nTiles <= 0 || rq.nRows <= 0 || rq.nCols <= 0 || rq.dt < 0 || rq.dt > DT_Double)
     return kWrongParam;
+  if (tbbShapeOk(rq.dt, rq.nRows, rq.nCols)) return tbDecode<BytesMaskedBatch>(ctx, rq, true);
   return tbDecode<MaskedBatch>(ctx, rq, tmbShapeOk(rq.dt, rq.nRows, rq.nCols));
 }
 

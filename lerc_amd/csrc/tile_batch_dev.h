@@ -1,6 +1,7 @@
 // tile_batch_dev.h -- the device code the two families of tile batches share (tile_mask_batch.hip, tile_byte_batch.hip).  What a
 // workgroup of 256 threads that owns one tile needs: sums, Fletcher32 over a finished blob, an exclusive scan in place, the codec 6
-// header to and from bytes, the blobs' places in a packed arena, the walk over a tile's block headers.  And what a wave that owns one
+// header to and from bytes, the blobs' places in a packed arena, the walk over a tile's block headers, and a tile's mask (byte mask to
+// bit mask, its run-length stream each way, counts, ranks, header and mask section written).  And what a wave that owns one
 // block needs: the block encoder's and the block decoder's body.  Every piece of LDS is handed in by the kernel that owns it.
 #pragma once
 #include "lerc_common.h"
@@ -164,6 +165,167 @@ __device__ __forceinline__ void tbWriteHeader6(u8* out, const TbHeader6& h)
   putBytes(out + 46, (u64)h.flagBytes, 4);
   const double dbl[5] = { h.maxZErr, h.zMin, h.zMax, 0.0, 0.0 };
   for (int i = 0; i < 5; i++) { u64 bits; memcpy(&bits, &dbl[i], 8); putBytes(out + 50 + 8 * i, bits, 8); }
+}
+
+// ---- a tile's mask, by the workgroup that owns the tile (masked batches of any pixel type)
+// byte mask -> bit mask (BitMask's layout: most significant bit first) into LDS (nBytes + 16 bytes, the last 16 zero) and into global
+// memory; f(k) is called for every valid pixel k.  -> this thread's count of valid pixels.  (No barrier: the caller's comes next.)
+template<class F>
+__device__ __forceinline__ u32 tbMaskToBits(const u8* __restrict__ vb, u32 nPix, u8* s_bits, u8* __restrict__ bitsOut, F f)
+{
+  const u32 nBytes = (nPix + 7u) >> 3;
+  u32 cnt = 0;
+  for (u32 by = threadIdx.x; by < nBytes; by += 256u)
+  {
+    u32 m = 0;
+    for (u32 j = 0; j < 8u; j++)
+    {
+      const u32 k = 8u * by + j;
+      if (k >= nPix) { m |= 0x80u >> j; continue; }    // tail bits stay set, like BitMask::SetAllValid + SetInvalid (Lerc.cpp:959-975)
+      if (vb[k] == 0) continue;
+      m |= 0x80u >> j;
+      cnt++;
+      f(k);
+    }
+    s_bits[by] = (u8)m;
+    bitsOut[by] = (u8)m;
+  }
+  for (u32 by = nBytes + threadIdx.x; by < nBytes + 16u; by += 256u) s_bits[by] = 0;
+  return cnt;
+}
+
+// the mask's run-length stream by ONE thread out of LDS (RLE.cpp:123-254, the same bytes as rleEncode, codec_common.cpp):
+// [int16 n][payload] ..., n > 0 literal bytes, n < 0 one byte -n times, -32768 ends it; a run is opened only where at least 5 equal
+// bytes start and one more byte follows; segments are cut at 32767.  -> the stream's length, 0: it outgrew cap
+__device__ __forceinline__ u32 tbMaskRle(const u8* s_bits, u32 n, u8* __restrict__ out, u32 cap)
+{
+  u32 at = 0, i = 0;
+  bool fits = true;
+  while (i < n && fits)
+  {
+    const u32 litBeg = i;
+    while (i < n)
+    {
+      const bool runStarts = (i + 5 < n) && s_bits[i] == s_bits[i + 1] && s_bits[i] == s_bits[i + 2] && s_bits[i] == s_bits[i + 3] && s_bits[i] == s_bits[i + 4];
+      if (runStarts) break;
+      i++;
+    }
+    for (u32 p = litBeg; p < i && fits;)
+    {
+      const u32 len = min(32767u, i - p);
+      if (at + 2u + len + 8u > cap) { fits = false; break; }
+      out[at] = (u8)(len & 255u); out[at + 1] = (u8)(len >> 8); at += 2;
+      for (u32 q = 0; q < len; q++) out[at + q] = s_bits[p + q];
+      at += len; p += len;
+    }
+    if (i >= n || !fits) break;
+    u32 e = i;
+    while (e + 1 < n && s_bits[e + 1] == s_bits[i]) e++;
+    for (u32 left = e - i + 1; left > 0 && fits;)
+    {
+      const u32 len = min(32767u, left);
+      if (at + 3u + 8u > cap) { fits = false; break; }
+      const u32 neg = (u32)(-(int)len) & 0xFFFFu;
+      out[at] = (u8)(neg & 255u); out[at + 1] = (u8)(neg >> 8); out[at + 2] = s_bits[i]; at += 3;
+      left -= len;
+    }
+    i = e + 1;
+  }
+  if (!fits || at + 2u > cap) return 0u;
+  out[at] = 0x00; out[at + 1] = 0x80;
+  return at + 2u;
+}
+
+// the run-length stream src[0 .. nm) expanded into s_bits[0 .. nBytes) by ONE thread (rleDecode, codec_common.cpp: what it does not
+// fill stays as it is), bounded by the section's length and the mask's size.  -> false: the stream is damaged
+__device__ __forceinline__ bool tbMaskUnrle(const u8* __restrict__ src, u32 nm, u8* s_bits, u32 nBytes)
+{
+  u32 left = nm, at = 0, sp = 0;
+  for (;;)
+  {
+    if (left < 2u) return false;
+    const int cnt = (int)(short)(u16)(src[sp] | (src[sp + 1] << 8));
+    sp += 2; left -= 2;
+    if (cnt == -32768) return true;
+    const u32 n = (u32)(cnt < 0 ? -cnt : cnt), payload = cnt > 0 ? n : 1u;
+    if (left < payload + 2u || at + n > nBytes) return false;    // + 2: a count always follows (RLE.cpp:310)
+    if (cnt > 0) for (u32 k = 0; k < n; k++) s_bits[at + k] = src[sp + k];
+    else { const u8 v = src[sp]; for (u32 k = 0; k < n; k++) s_bits[at + k] = v; }
+    at += n; sp += payload; left -= payload;
+  }
+}
+
+// The pixels of a tile in row order, the valid ones with their rank among the valid ones, by one workgroup of 256 threads: a thread
+// takes a byte of the bit mask (8 pixels) a round, a round's popcounts are scanned over the workgroup.  f(pixel, valid, rank) is
+// called once for every pixel below nPix (the tail bits of an encoder's mask are set: they do not count).  s: 4 words of LDS.
+template<class F>
+__device__ __forceinline__ u32 tbRankedSweep(const u8* bits, u32 nPix, u32* s, F f)
+{
+  const u32 nBytes = (nPix + 7u) >> 3;
+  u32 run = 0;
+  for (u32 base = 0; base < nBytes; base += 256u)
+  {
+    const u32 by = base + threadIdx.x;
+    u32 m = by < nBytes ? (u32)bits[by] : 0u;
+    if (8u * by + 8u > nPix) m &= (8u * by < nPix) ? (0xFF00u >> (nPix - 8u * by)) & 0xFFu : 0u;
+    const u32 c = (u32)__popc(m), inc = waveInclusiveScan(c);
+    if (laneId() == 63) s[waveId()] = inc;
+    __syncthreads();
+    u32 r = run + inc - c;
+    for (int w = 0; w < waveId(); w++) r += s[w];
+    run += s[0] + s[1] + s[2] + s[3];
+    for (u32 j = 0; j < 8u && 8u * by + j < nPix; j++)
+    {
+      const bool valid = (m & (0x80u >> j)) != 0u;
+      f(8u * by + j, valid, r);
+      r += valid ? 1u : 0u;
+    }
+    __syncthreads();
+  }
+  return run;
+}
+
+// the mask's own count of valid pixels below nPix, by the workgroup (s: 4 words of LDS)
+__device__ __forceinline__ u32 tbMaskCount(const u8* s_bits, u32 nPix, u64* s)
+{
+  const u32 nBytes = (nPix + 7u) >> 3;
+  u32 cnt = 0;
+  for (u32 by = threadIdx.x; by < nBytes; by += 256u)
+  {
+    u32 m = s_bits[by];
+    if (8u * by + 8u > nPix) m &= (0xFF00u >> (nPix - 8u * by)) & 0xFFu;
+    cnt += (u32)__popc(m);
+  }
+  return (u32)blockSum((u64)cnt, s);
+}
+
+// valid pixels per MB x MB block out of the bit mask in LDS, nv[pos] (at most 256 each); no barrier behind it
+__device__ __forceinline__ void tbBlockValidCounts(const u8* s_bits, u32 nRows, u32 nCols, u32 MB, u16* nv)
+{
+  const u32 nTV = (nRows + MB - 1u) / MB, nTH = (nCols + MB - 1u) / MB, nPos = nTV * nTH;
+  for (u32 pos = threadIdx.x; pos < nPos; pos += 256u)
+  {
+    const u32 it = pos / nTH, jt = pos - it * nTH;
+    const u32 i1 = min(nRows, it * MB + MB), j1 = min(nCols, jt * MB + MB);
+    u32 n = 0;
+    for (u32 i = it * MB; i < i1; i++)
+      for (u32 j = jt * MB; j < j1; j++) { const u32 k = i * nCols + j; n += (s_bits[k >> 3] >> (7u - (k & 7u))) & 1u; }
+    nv[pos] = (u16)n;
+  }
+}
+
+// header (checksum patched later: tbWriteChecksum) and mask section -- the stream's length and the stream -- of a tile of any kind,
+// by the workgroup.  s_hdr: 96 bytes of LDS.
+__device__ __forceinline__ void tbWriteHeaderMask(u8* __restrict__ blob, const TbHeader6& h, const u8* __restrict__ rle, u32 rleLen, u8* s_hdr)
+{
+  if (threadIdx.x == 0)
+  {
+    tbWriteHeader6(s_hdr, h);
+    putBytes(s_hdr + kHdr6, (u64)rleLen, 4);
+  }
+  __syncthreads();
+  for (u32 i = threadIdx.x; i < kHdr6 + 4u; i += 256u) blob[i] = s_hdr[i];
+  for (u32 i = threadIdx.x; i < rleLen; i += 256u) blob[kHdr6 + 4u + i] = rle[i];
 }
 
 // ---- the walk over a tile's block stream by ONE thread: block k + 1 starts where block k ends; a block's length follows from its

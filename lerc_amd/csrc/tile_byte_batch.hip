@@ -29,6 +29,13 @@
 // Every loop over a blob is bounded by the blob's size and the pixel count; whatever does not fit raises a flag and the host repeats
 // that tile with the single-blob decoder, which also yields the exact status of a damaged blob.
 // No workgroup waits for another one inside a launch, so the emulator build runs the same path.
+//
+// MASKED (a template argument of the kernels above; the masked calls with 8-bit tiles): a byte mask per tile.  k_tbb_stats makes bit
+// mask, valid count and the mask's run-length stream first (tile_batch_dev.h, shared with tile_mask_batch.hip), the histograms count
+// valid pixels only with the masked predictor (Lerc2.cpp:2350-2379), the blocks are the masked block coder's, the decisions take the
+// valid count, k_tbb_blocks16 / k_tbb_decide16 settle the low-bit-rate retry, k_tbb_write puts the mask section in front and codes an
+// invalid pixel with length 0; k_tbbd_parse expands and checks the mask, k_tbbd_huff wants numValid code words, sends them to the
+// valid positions by rank and undoes the masked predictor row by row.  Tiles without a valid pixel stay inside.
 #include <cstdio>
 #include <cstdlib>
 #include "kernels.h"
@@ -50,10 +57,70 @@ __device__ __forceinline__ u32 tbbDelta(const u8* __restrict__ px, u32 k, u32 nC
   return ((u32)px[k] - pred) & 255u;
 }
 
+// ---- the masked predictor (Lerc2.cpp:2350-2379): only valid pixels count; the predecessor of valid pixel k is its left neighbour if
+// that is valid (never across a row's start), else the pixel above if that is valid, else the last valid pixel in scan order,
+// however far back (0 in front of the first).  "The last valid pixel below k" is asked of the bit mask: inside k's word of 32
+// pixels a bit scan, else the last non-empty word below it -- a table made once per tile.
+static const u32 kTbbMaskWords = kTbbMaxPixels / 32u;
+
+struct TbbmMask
+{
+  const u8* bits;         // the tile's bit mask in LDS (BitMask's layout: most significant bit first), 16 zero bytes behind it
+  const u16* last;        // last[w]: 1 + the last word below w with a valid pixel in it, 0: none
+  __device__ __forceinline__ u32 word(u32 w) const
+  {
+    const u8* q = bits + 4u * w;
+    return ((u32)q[0] << 24) | ((u32)q[1] << 16) | ((u32)q[2] << 8) | (u32)q[3];
+  }
+  __device__ __forceinline__ bool valid(u32 k) const { return ((bits[k >> 3] >> (7u - (k & 7u))) & 1u) != 0u; }
+  __device__ __forceinline__ int prev(u32 k) const    // -1: none
+  {
+    u32 w = k >> 5;
+    u32 x = word(w) & ~(0xFFFFFFFFu >> (k & 31u));    // pixel w * 32 + i is bit 31 - i
+    if (!x)
+    {
+      const u32 lw = last[w];
+      if (!lw) return -1;
+      w = lw - 1u;
+      x = word(w);
+    }
+    return (int)((w << 5) + 32u - (u32)__ffs((int)x));
+  }
+};
+
+// TbbmMask::last out of the bit mask in LDS (complete, behind a barrier), by the workgroup; s_scan: 256 words; a barrier ends it
+__device__ __forceinline__ void tbbmLastWords(const u8* s_bits, u32 nPix, u16* s_last, u32* s_scan)
+{
+  const TbbmMask m = { s_bits, s_last };
+  const u32 nW = (nPix + 31u) >> 5, per = (nW + 255u) / 256u, from = min(nW, threadIdx.x * per), to = min(nW, from + per);
+  u32 last = 0;
+  for (u32 w = from; w < to; w++) if (m.word(w)) last = w + 1u;
+  s_scan[threadIdx.x] = last;
+  __syncthreads();
+  if (threadIdx.x == 0) { u32 run = 0; for (u32 i = 0; i < 256u; i++) { const u32 y = s_scan[i]; s_scan[i] = run; run = max(run, y); } }
+  __syncthreads();
+  u32 run = s_scan[threadIdx.x];
+  for (u32 w = from; w < to; w++) { s_last[w] = (u16)run; if (m.word(w)) run = w + 1u; }
+  __syncthreads();
+}
+
+// the masked predictor's difference at VALID pixel k, as a raw byte
+__device__ __forceinline__ u32 tbbmDelta(const u8* __restrict__ px, const TbbmMask& m, u32 k, u32 nCols)
+{
+  const u32 i = k / nCols, j = k - i * nCols;
+  u32 pred = 0;
+  if (j > 0u && m.valid(k - 1u)) pred = px[k - 1u];
+  else if (i > 0u && m.valid(k - nCols)) pred = px[k - nCols];
+  else { const int kp = m.prev(k); if (kp >= 0) pred = px[kp]; }
+  return ((u32)px[k] - pred) & 255u;
+}
+
 // ================================================================================================
 // encode
 // ================================================================================================
-template<class T>
+// MASKED: in front of the histograms the masked batch's prelude (tile_batch_dev.h) -- byte mask -> bit mask, the count of valid pixels,
+// the mask's run-length stream by one lane -- and the histograms over valid pixels only
+template<class T, bool MASKED>
 __global__ void __launch_bounds__(256) k_tbb_stats(TbbGeom g, const u8* __restrict__ data, TbbEncodeBuffers b)
 {
   __shared__ u32 s_h[512];
@@ -62,11 +129,42 @@ __global__ void __launch_bounds__(256) k_tbb_stats(TbbGeom g, const u8* __restri
   const u32 nPix = (u32)g.tileElems, nCols = (u32)g.nCols;
   const u8* __restrict__ px = data + (u64)t * g.tileElems;
   s_h[threadIdx.x] = 0; s_h[threadIdx.x + 256u] = 0;
-  __syncthreads();
-  for (u32 k = threadIdx.x; k < nPix; k += 256u)
+  u32 numValid = nPix, rleFlag = 0;
+  if constexpr (MASKED)
   {
-    atomicAdd(&s_h[tbbBin<T>(px[k])], 1u);
-    atomicAdd(&s_h[256u + tbbBin<T>(tbbDelta(px, k, nCols))], 1u);
+    __shared__ __align__(16) u8 s_bits[kTbbMaxMaskBytes + 16];
+    __shared__ u16 s_last[kTbbMaskWords];
+    __shared__ u32 s_scan[256];
+    __shared__ u64 s_red[4];
+    const u32 cnt = tbMaskToBits(b.m.valid + (u64)t * g.tileElems, nPix, s_bits, b.m.bits + (u64)t * b.m.bitStride, [](u32) {});
+    numValid = (u32)blockSum((u64)cnt, s_red);    // (its barriers cover s_h and s_bits)
+    if (threadIdx.x == 0)
+    {
+      TbbMaskRec mr = { numValid, 0u };
+      if (numValid > 0u && numValid < nPix)
+      {
+        mr.rleLen = tbMaskRle(s_bits, (nPix + 7u) >> 3, b.m.rle + (u64)t * b.m.rleStride, b.m.rleStride);
+        if (!mr.rleLen) rleFlag = kTbbRle;
+      }
+      b.m.rec[t] = mr;
+    }
+    tbbmLastWords(s_bits, nPix, s_last, s_scan);
+    const TbbmMask m = { s_bits, s_last };
+    for (u32 k = threadIdx.x; k < nPix; k += 256u)
+    {
+      if (!m.valid(k)) continue;
+      atomicAdd(&s_h[tbbBin<T>(px[k])], 1u);
+      atomicAdd(&s_h[256u + tbbBin<T>(tbbmDelta(px, m, k, nCols))], 1u);
+    }
+  }
+  else
+  {
+    __syncthreads();
+    for (u32 k = threadIdx.x; k < nPix; k += 256u)
+    {
+      atomicAdd(&s_h[tbbBin<T>(px[k])], 1u);
+      atomicAdd(&s_h[256u + tbbBin<T>(tbbDelta(px, k, nCols))], 1u);
+    }
   }
   __syncthreads();
   u32* __restrict__ out = b.histo + (u64)t * 512u;
@@ -81,12 +179,14 @@ __global__ void __launch_bounds__(256) k_tbb_stats(TbbGeom g, const u8* __restri
   ti.symMin = min(min(s_mn[0], s_mn[1]), min(s_mn[2], s_mn[3]));
   ti.symMax = max(max(s_mx[0], s_mx[1]), max(s_mx[2], s_mx[3]));
   ti.head.flags = (ti.symMin == ti.symMax) ? kTbbConst : 0u;
+  if (MASKED && numValid == 0u) { ti.head.flags = 0u; ti.mode = kTbbModeEmpty; }    // (header and mask section are all of it: Lerc2.cpp:240)
+  if (MASKED && rleFlag) ti.head.flags = rleFlag;
   b.tiles[t] = ti;
 }
 
 // A wave per 8 x 8 block of a tile (blockIdx.y): k_encode_tiles (tile_encode.hip) for one value a pixel, every pixel valid, with the
-// tile's own place in the arena.  WRITE: tiling mode tiles only.
-template<class T, bool WRITE>
+// tile's own place in the arena.  WRITE: tiling mode tiles only.  MASKED: the masked block coder with the tile's bit mask.
+template<class T, bool WRITE, bool MASKED>
 __global__ void __launch_bounds__(256)
 k_tbb_blocks(TbbGeom g, BandParams p, const T* __restrict__ data, u8* __restrict__ arena, TbbEncodeBuffers b)
 {
@@ -98,11 +198,20 @@ k_tbb_blocks(TbbGeom g, BandParams p, const T* __restrict__ data, u8* __restrict
   const u32 t = blockIdx.y;
   const TbbTile ti = b.tiles[t];
   if (ti.head.flags || (WRITE && ti.mode != (u32)IEM_Tiling)) return;
+  if (MASKED && ti.mode == kTbbModeEmpty) return;
   const int w = waveId();
   const int pos = (int)blockIdx.x * 4 + w;
   if (pos >= g.nTV * g.nTH) return;    // whole wave leaves together
-  tbEncodeBlock<T, 1, false, WRITE>(p, pos, data + (u64)t * g.tileElems, nullptr, b.blockOff + (u64)t * g.posStride,
-                                    WRITE ? arena + ti.head.offset + kTbbDataBegin : nullptr, s_val[w], s_obuf[w], s_lut[w]);
+  if constexpr (MASKED)
+  {
+    const TbbMaskRec mr = b.m.rec[t];
+    p.allValid = (mr.numValid == (u32)g.tileElems) ? 1 : 0;
+    tbEncodeBlock<T, 1, true, WRITE>(p, pos, data + (u64)t * g.tileElems, b.m.bits + (u64)t * b.m.bitStride, b.blockOff + (u64)t * g.posStride,
+                                     WRITE ? arena + ti.head.offset + kTbbDataBegin + mr.rleLen : nullptr, s_val[w], s_obuf[w], s_lut[w]);
+  }
+  else
+    tbEncodeBlock<T, 1, false, WRITE>(p, pos, data + (u64)t * g.tileElems, nullptr, b.blockOff + (u64)t * g.posStride,
+                                      WRITE ? arena + ti.head.offset + kTbbDataBegin : nullptr, s_val[w], s_obuf[w], s_lut[w]);
 }
 
 // ---- a code book, built by ONE thread in LDS
@@ -293,6 +402,11 @@ __device__ void tbbBuildBook(const u32* __restrict__ histo, TbbBook& k)
   k.ok = 1;
 }
 
+// MASKED: the count of valid pixels where the all-valid code has the pixel count (Lerc2.cpp:331-364) -- but for the bit rate of the
+// low-bit-rate rule, which counts every pixel (:335) --, and the mask section's length in the blob's size.  Where the low-bit-rate
+// rule holds the tile is not handed back at once: with few valid pixels it holds for most Huffman tiles, and the 16 x 16 blocks
+// then lose (:346).  The tile is marked, k_tbb_blocks16 sizes its 16 x 16 blocks, and k_tbb_decide16 hands it back only if they win.
+template<bool MASKED>
 __global__ void __launch_bounds__(256) k_tbb_decide(TbbGeom g, u64 slotBytes, u64 firstTile, TbbEncodeBuffers b)
 {
   __shared__ u32 s_scan[257];
@@ -301,6 +415,19 @@ __global__ void __launch_bounds__(256) k_tbb_decide(TbbGeom g, u64 slotBytes, u6
   __shared__ u32 s_pick;
   const u32 t = blockIdx.x;
   if (b.tiles[t].head.flags) return;
+  if constexpr (MASKED)
+    if (b.tiles[t].mode == kTbbModeEmpty)
+    {
+      if (threadIdx.x != 0) return;
+      TbbTile& ti = b.tiles[t];
+      ti.head.blobSize = kHdr6 + 4u;
+      if (slotBytes)
+      {
+        ti.head.offset = (firstTile + t) * slotBytes;
+        if ((u64)ti.head.blobSize > slotBytes) ti.head.flags = kTbCapacity;
+      }
+      return;
+    }
   const u32 nPos = (u32)(g.nTV * g.nTH);
   const u32* __restrict__ histo = b.histo + (u64)t * 512u;
   s_h[threadIdx.x] = histo[threadIdx.x]; s_h[threadIdx.x + 256u] = histo[threadIdx.x + 256u];
@@ -312,6 +439,9 @@ __global__ void __launch_bounds__(256) k_tbb_decide(TbbGeom g, u64 slotBytes, u6
   {
     TbbTile& ti = b.tiles[t];
     const u64 nPix = g.tileElems;
+    u64 numValid = nPix;
+    u32 dataBegin = kTbbDataBegin;
+    if constexpr (MASKED) { const TbbMaskRec mr = b.m.rec[t]; numValid = mr.numValid; dataBegin += mr.rleLen; }
     // Lerc2.cpp:2289-2306: the better of the two books; the plain one where they tie
     const u32 n0 = s_book[0].ok ? s_book[0].nBytes : 0u, n1 = s_book[1].ok ? s_book[1].nBytes : 0u;
     u32 pick = 2u, nBytesHuffman = 0;
@@ -323,17 +453,19 @@ __global__ void __launch_bounds__(256) k_tbb_decide(TbbGeom g, u64 slotBytes, u6
     else pick = 2u;
     u32 fl = 0;
     // 16 x 16 blocks at low bit rates (Lerc2.cpp:333-357)
-    if ((double)((u64)nBytesTiling * 8u) < (double)nPix * 1.5 && (u64)nBytesTiling < 4u * nPix
+    if ((double)((u64)nBytesTiling * 8u) < (double)nPix * 1.5 && (u64)nBytesTiling < 4u * numValid
       && (nBytesHuffman == 0u || (u64)nBytesTiling < 2ull * nBytesHuffman) && (g.nRows > 8 || g.nCols > 8))
-      fl |= kTbbRetry16;
+    {
+      if (MASKED) ti.retry = 1u; else fl |= kTbbRetry16;
+    }
     nBytesData += 1u;    // the mode byte
-    if (nPix <= (u64)nBytesData) fl |= kTbbOneSweep;
+    if (numValid <= (u64)nBytesData) fl |= kTbbOneSweep;
     ti.mode = mode;
     ti.nBytesTiling = nBytesTiling;
     ti.nBytesHuffman = nBytesHuffman;
     ti.tableBytes = pick < 2u ? s_book[pick].tableBytes : 0u;
     ti.nBits = pick < 2u ? s_book[pick].nBits : 0ull;
-    ti.head.blobSize = kTbbDataBegin - 1u + nBytesData;
+    ti.head.blobSize = dataBegin - 1u + nBytesData;
     if (slotBytes)
     {
       ti.head.offset = (firstTile + t) * slotBytes;
@@ -351,6 +483,42 @@ __global__ void __launch_bounds__(256) k_tbb_decide(TbbGeom g, u64 slotBytes, u6
   for (u32 i = threadIdx.x; i < k.tableBytes; i += 256u) tab[i] = k.table[i];
 }
 
+// masked form, the tiles k_tbb_decide marked: a wave per 16 x 16 block, the block's size
+template<class T>
+__global__ void __launch_bounds__(256) k_tbb_blocks16(TbbGeom g, BandParams p, const T* __restrict__ data, TbbEncodeBuffers b)
+{
+  __shared__ T s_val[4][256];
+  __shared__ u32 s_obuf[4][1];
+  __shared__ u32 s_lut[4][1];
+  const u32 t = blockIdx.y;
+  const TbbTile ti = b.tiles[t];
+  if (ti.head.flags || !ti.retry) return;
+  const int nTV = (g.nRows + 15) / 16, nTH = (g.nCols + 15) / 16;
+  const int w = waveId();
+  const int pos = (int)blockIdx.x * 4 + w;
+  if (pos >= nTV * nTH) return;    // whole wave leaves together
+  p.mb = 16; p.nTV = nTV; p.nTH = nTH;
+  p.allValid = (b.m.rec[t].numValid == (u32)g.tileElems) ? 1 : 0;
+  tbEncodeBlock<T, 4, true, false>(p, pos, data + (u64)t * g.tileElems, b.m.bits + (u64)t * b.m.bitStride, b.m.blockOff16 + (u64)t * b.m.pos16Stride,
+                                   nullptr, s_val[w], s_obuf[w], s_lut[w]);
+}
+
+// ... and Lerc2.cpp:346: 16 x 16 blocks that are no longer than what the tile has so far win -- the tile is handed back
+__global__ void __launch_bounds__(256) k_tbb_decide16(TbbGeom g, TbbEncodeBuffers b)
+{
+  __shared__ u32 s_scan[257];
+  __shared__ u32 s_rec[2];
+  const u32 t = blockIdx.x;
+  if (threadIdx.x == 0) { s_rec[0] = b.tiles[t].head.flags; s_rec[1] = b.tiles[t].retry; }
+  __syncthreads();
+  if (s_rec[0] || !s_rec[1]) return;
+  const u32 nBytes16 = blockScanInPlace(b.m.blockOff16 + (u64)t * b.m.pos16Stride, (u32)(((g.nRows + 15) / 16) * ((g.nCols + 15) / 16)), s_scan);
+  if (threadIdx.x != 0) return;
+  TbbTile& ti = b.tiles[t];
+  const u32 nBytesData = ti.mode == (u32)IEM_Tiling ? ti.nBytesTiling : ti.nBytesHuffman;
+  if (nBytes16 <= nBytesData) ti.head.flags = kTbbRetry16;
+}
+
 __global__ void __launch_bounds__(256) k_tbb_arena(u32 nTiles, u64 arenaBase, u64 arenaCapacity, TbbEncodeBuffers b)
 {
   __shared__ u64 s_part[257];
@@ -361,7 +529,9 @@ static const u32 kTbbRun = 16;                      // pixels a thread packs in 
 static const u32 kTbbStep = 256u * kTbbRun;         // ... and the workgroup
 static const u32 kTbbStageWords = kTbbStep + 4u;    // 32 bits a code word at most, the word carried over, one to spill into
 
-template<class T>
+// MASKED: header and mask section as the masked batch writes them (tbWriteHeaderMask), for a tile without a valid pixel nothing else;
+// in the pixel stream an invalid pixel is a code of length 0 -- the step's scan is the compaction
+template<class T, bool MASKED>
 __global__ void __launch_bounds__(256) k_tbb_write(TbbGeom g, const u8* __restrict__ data, u8* __restrict__ arena, TbbEncodeBuffers b)
 {
   __shared__ u8 s_hdr[kTbbDataBegin + 2];
@@ -373,32 +543,69 @@ __global__ void __launch_bounds__(256) k_tbb_write(TbbGeom g, const u8* __restri
   if (ti.head.flags) return;
   const u32 nPix = (u32)g.tileElems, nCols = (u32)g.nCols;
   u8* __restrict__ blob = arena + ti.head.offset;
-  // ---- header (Lerc2.cpp:724-786; checksum patched by k_tbb_checksum), an empty mask section, ranges, "not one sweep", mode
-  if (threadIdx.x == 0)
+  // ---- header (Lerc2.cpp:724-786; checksum patched by k_tbb_checksum), the mask section, ranges, "not one sweep", mode
+  u32 dataBegin = kTbbDataBegin;
+  if constexpr (MASKED)
   {
-    u8* h = s_hdr;
+    const TbbMaskRec mr = b.m.rec[t];
+    const bool empty = ti.mode == kTbbModeEmpty;
     const int off = (g.dt == DT_Char) ? 128 : 0;
-    const TbHeader6 hd = { kCodecVersion, 0u, g.nRows, g.nCols, 1, (int)nPix, 8, (int)ti.head.blobSize, g.dt, 0, 0u,
-                           0.5, (double)((int)ti.symMin - off), (double)((int)ti.symMax - off) };
-    tbWriteHeader6(h, hd);
-    putBytes(h + kHdr6, 0ull, 4);
-    h[kHdr6 + 4u] = (u8)((int)ti.symMin - off);
-    h[kHdr6 + 5u] = (u8)((int)ti.symMax - off);
-    h[kHdr6 + 6u] = 0;
-    h[kHdr6 + 7u] = (u8)ti.mode;
+    const TbHeader6 hd = { kCodecVersion, 0u, g.nRows, g.nCols, 1, (int)mr.numValid, 8, (int)ti.head.blobSize, g.dt, 0, 0u,
+                           0.5, empty ? 0.0 : (double)((int)ti.symMin - off), empty ? 0.0 : (double)((int)ti.symMax - off) };
+    s_code[threadIdx.x] = b.codes[(u64)t * 256u + threadIdx.x];
+    tbWriteHeaderMask(blob, hd, b.m.rle + (u64)t * b.m.rleStride, mr.rleLen, s_hdr);    // (its barrier covers s_code)
+    if (empty) return;
+    dataBegin += mr.rleLen;
+    if (threadIdx.x == 0)
+    {
+      u8* r = blob + kHdr6 + 4u + mr.rleLen;
+      r[0] = (u8)((int)ti.symMin - off);
+      r[1] = (u8)((int)ti.symMax - off);
+      r[2] = 0;
+      r[3] = (u8)ti.mode;
+    }
   }
-  s_code[threadIdx.x] = b.codes[(u64)t * 256u + threadIdx.x];
-  __syncthreads();
-  for (u32 i = threadIdx.x; i < kTbbDataBegin; i += 256u) blob[i] = s_hdr[i];
+  else
+  {
+    if (threadIdx.x == 0)
+    {
+      u8* h = s_hdr;
+      const int off = (g.dt == DT_Char) ? 128 : 0;
+      const TbHeader6 hd = { kCodecVersion, 0u, g.nRows, g.nCols, 1, (int)nPix, 8, (int)ti.head.blobSize, g.dt, 0, 0u,
+                             0.5, (double)((int)ti.symMin - off), (double)((int)ti.symMax - off) };
+      tbWriteHeader6(h, hd);
+      putBytes(h + kHdr6, 0ull, 4);
+      h[kHdr6 + 4u] = (u8)((int)ti.symMin - off);
+      h[kHdr6 + 5u] = (u8)((int)ti.symMax - off);
+      h[kHdr6 + 6u] = 0;
+      h[kHdr6 + 7u] = (u8)ti.mode;
+    }
+    s_code[threadIdx.x] = b.codes[(u64)t * 256u + threadIdx.x];
+    __syncthreads();
+    for (u32 i = threadIdx.x; i < kTbbDataBegin; i += 256u) blob[i] = s_hdr[i];
+  }
   if (ti.mode == (u32)IEM_Tiling) return;
   const u8* __restrict__ tab = b.table + (u64)t * kTbbTableCap;
-  for (u32 i = threadIdx.x; i < ti.tableBytes; i += 256u) blob[kTbbDataBegin + i] = tab[i];
+  for (u32 i = threadIdx.x; i < ti.tableBytes; i += 256u) blob[dataBegin + i] = tab[i];
 
   // ---- the pixel stream: code words MSB first in little-endian 32-bit words (Huffman::PushValue)
   const u8* __restrict__ px = data + (u64)t * g.tileElems;
-  u8* __restrict__ stream = blob + kTbbDataBegin + ti.tableBytes;
+  u8* __restrict__ stream = blob + dataBegin + ti.tableBytes;    // (masked: any alignment, with the mask section's length)
   const bool aligned = ((uintptr_t)stream & 3u) == 0u;
   const bool delta = ti.mode == (u32)IEM_DeltaHuffman;
+  TbbmMask m = { nullptr, nullptr };
+  if constexpr (MASKED)
+  {
+    __shared__ __align__(16) u8 s_bits[kTbbMaxMaskBytes + 16];
+    __shared__ u16 s_last[kTbbMaskWords];
+    __shared__ u32 s_scan[256];
+    const u32 nBytes = (nPix + 7u) >> 3;
+    const u8* __restrict__ bits = b.m.bits + (u64)t * b.m.bitStride;
+    for (u32 i = threadIdx.x; i < nBytes + 16u; i += 256u) s_bits[i] = i < nBytes ? bits[i] : (u8)0;
+    __syncthreads();
+    if (delta) tbbmLastWords(s_bits, nPix, s_last, s_scan);
+    m.bits = s_bits; m.last = s_last;
+  }
   u32 carryBits = 0, carryWord = 0, wordBase = 0;
   for (u32 k0 = 0; k0 < nPix; k0 += kTbbStep)
   {
@@ -411,7 +618,8 @@ __global__ void __launch_bounds__(256) k_tbb_write(TbbGeom g, const u8* __restri
     {
       const u32 k = first + j;
       u64 c = 0;
-      if (k < nPix) c = s_code[tbbBin<T>(delta ? tbbDelta(px, k, nCols) : (u32)px[k])];
+      if constexpr (MASKED) { if (k < nPix && m.valid(k)) c = s_code[tbbBin<T>(delta ? tbbmDelta(px, m, k, nCols) : (u32)px[k])]; }
+      else if (k < nPix) c = s_code[tbbBin<T>(delta ? tbbDelta(px, k, nCols) : (u32)px[k])];
       len[j] = (u32)(c >> 32); code[j] = (u32)c;
       sum += len[j];
     }
@@ -465,26 +673,42 @@ __global__ void __launch_bounds__(256) k_tbb_checksum(u8* __restrict__ arena, Tb
   tbWriteChecksum(arena, b.tiles[blockIdx.x].head, s_red);
 }
 
-template<class T>
+template<class T, bool MASKED>
 static void tbbEncodeT(const TbbGeom& g, const BandParams& bp, const void* dTiles, u8* dArena, u64 arenaBase, u64 arenaCapacity, u64 slotBytes,
                        u64 firstTile, const TbbEncodeBuffers& b, hipStream_t st)
 {
   const int nPos = g.nTV * g.nTH;
   const dim3 perTile(g.nTiles), blk(256), perBlock((nPos + 3) / 4, g.nTiles);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_stats<T>), perTile, blk, 0, st, g, (const u8*)dTiles, b);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_blocks<T, false>), perBlock, blk, 0, st, g, bp, (const T*)dTiles, (u8*)nullptr, b);
-  hipLaunchKernelGGL(k_tbb_decide, perTile, blk, 0, st, g, slotBytes, firstTile, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_stats<T, MASKED>), perTile, blk, 0, st, g, (const u8*)dTiles, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_blocks<T, false, MASKED>), perBlock, blk, 0, st, g, bp, (const T*)dTiles, (u8*)nullptr, b);
+  hipLaunchKernelGGL(k_tbb_decide<MASKED>, perTile, blk, 0, st, g, slotBytes, firstTile, b);
+  if constexpr (MASKED)
+  {
+    // (over the whole batch, whether a tile is marked or not: the host knows nothing yet, and does not wait to learn it)
+    const int nPos16 = ((g.nRows + 15) / 16) * ((g.nCols + 15) / 16);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_blocks16<T>), dim3((nPos16 + 3) / 4, g.nTiles), blk, 0, st, g, bp, (const T*)dTiles, b);
+    hipLaunchKernelGGL(k_tbb_decide16, perTile, blk, 0, st, g, b);
+  }
   if (!slotBytes) hipLaunchKernelGGL(k_tbb_arena, dim3(1), blk, 0, st, g.nTiles, arenaBase, arenaCapacity, b);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_blocks<T, true>), perBlock, blk, 0, st, g, bp, (const T*)dTiles, dArena, b);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_write<T>), perTile, blk, 0, st, g, (const u8*)dTiles, dArena, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_blocks<T, true, MASKED>), perBlock, blk, 0, st, g, bp, (const T*)dTiles, dArena, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_write<T, MASKED>), perTile, blk, 0, st, g, (const u8*)dTiles, dArena, b);
   hipLaunchKernelGGL(k_tbb_checksum, perTile, blk, 0, st, dArena, b);
 }
 
 void launchTbbEncode(const TbbGeom& g, const BandParams& bp, const void* dTiles, u8* dArena, u64 arenaBase, u64 arenaCapacity, u64 slotBytes,
                      u64 firstTile, const TbbEncodeBuffers& b, hipStream_t st)
 {
-  if (g.dt == DT_Char) tbbEncodeT<signed char>(g, bp, dTiles, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st);
-  else if (g.dt == DT_Byte) tbbEncodeT<unsigned char>(g, bp, dTiles, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st);
+  const bool masked = b.m.valid != nullptr;
+  if (g.dt == DT_Char)
+  {
+    if (masked) tbbEncodeT<signed char, true>(g, bp, dTiles, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st);
+    else tbbEncodeT<signed char, false>(g, bp, dTiles, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st);
+  }
+  else if (g.dt == DT_Byte)
+  {
+    if (masked) tbbEncodeT<unsigned char, true>(g, bp, dTiles, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st);
+    else tbbEncodeT<unsigned char, false>(g, bp, dTiles, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st);
+  }
 }
 
 // ================================================================================================
@@ -551,12 +775,17 @@ __device__ bool tbbParseTable(const u8* __restrict__ p, u32 n, u8* __restrict__ 
   return used <= n;
 }
 
-template<class T>
+// MASKED: a mask section of any length in front of the ranges; the run-length stream expanded into LDS (tbMaskUnrle, as the masked
+// batch's parse does), the mask's own count held against the header's, the bit mask left in the workspace, the caller's valid
+// bytes written; tiling mode: the valid counts per block out of the bit mask
+template<class T, bool MASKED>
 __global__ void __launch_bounds__(256)
 k_tbbd_parse(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ offsets, const u32* __restrict__ sizes, TbbDecodeBuffers b)
 {
   __shared__ u64 s_red[4];
   __shared__ TbbTile s_ti;
+  __shared__ u16 s_nv[MASKED ? kTbbMaxBlocks : 1];
+  __shared__ TbbMaskRec s_mr;
   const u32 t = blockIdx.x;
   const u8* __restrict__ blob = arena + offsets[t];
   const u32 sizeGiven = sizes[t];
@@ -567,7 +796,44 @@ k_tbbd_parse(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
     TbbTile ti;
     memset(&ti, 0, sizeof(ti));
     u32 fl = 0;
-    if (sizeGiven < kTbbDataBegin + 1u) fl = kTbHeader;
+    if constexpr (MASKED)
+    {
+      TbbMaskRec mr = { 0u, 0u };
+      if (sizeGiven < kHdr6 + 4u) fl = kTbHeader;
+      else
+      {
+        TbHeader6 h;
+        if (!tbReadHeader6(blob, h)) fl = kTbHeader;
+        ti.checksum = h.checksum;
+        ti.head.blobSize = (u32)h.blobSize;
+        if (h.version != kCodecVersion || h.nRows != g.nRows || h.nCols != g.nCols || h.nDepth != 1 || h.numValid < 0 || (u32)h.numValid > nPix
+          || h.microBlockSize != 8 || h.blobSize < (int)(kHdr6 + 4u) || (u32)h.blobSize > sizeGiven || h.dt != g.dt || h.nBlobsMore != 0
+          || (h.flagBytes & 0xFFu) != 0u)
+          fl = kTbHeader;
+        if (!fl)
+        {
+          mr.numValid = (u32)h.numValid;
+          mr.rleLen = (u32)getBytes(blob + kHdr6, 4);
+          const bool noStream = mr.numValid == nPix || mr.numValid == 0u;
+          if (noStream ? mr.rleLen != 0u : (mr.rleLen < 2u || mr.rleLen > ti.head.blobSize)) fl = kTbHeader;
+          else if (mr.numValid == 0u)
+          {
+            // no valid pixel: nothing may follow the mask section's length (Lerc2.cpp:235-241); range and error bound are not asked
+            ti.mode = kTbbModeEmpty;
+            if (ti.head.blobSize != kHdr6 + 4u) fl = kTbHeader;
+          }
+          else if (!(h.maxZErr == 0.5) || !(h.zMin < h.zMax) || (u64)kTbbDataBegin + mr.rleLen + 1u > (u64)ti.head.blobSize) fl = kTbHeader;
+          else
+          {
+            const u8* r = blob + kHdr6 + 4u + mr.rleLen;
+            if (r[0] == r[1] || r[2] != 0 || r[3] > 2) fl = kTbHeader;    // constant, one sweep, a later mode
+            ti.mode = r[3];
+          }
+        }
+      }
+      s_mr = mr;
+    }
+    else if (sizeGiven < kTbbDataBegin + 1u) fl = kTbHeader;
     else
     {
       TbHeader6 h;
@@ -599,26 +865,60 @@ k_tbbd_parse(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
     if (threadIdx.x == 0) { s_ti.head.flags = kTbChecksum; b.tiles[t] = s_ti; }
     return;
   }
+  u32 dataBegin = kTbbDataBegin;
+  if constexpr (MASKED)
+  {
+    // ---- the mask: all ones, all zeros, or the run-length stream expanded (what it does not fill stays zero)
+    __shared__ __align__(16) u8 s_bits[kTbbMaxMaskBytes + 16];
+    const TbbMaskRec mr = s_mr;
+    const u32 nBytes = (nPix + 7u) >> 3;
+    const bool allValid = mr.numValid == nPix, empty = mr.numValid == 0u;
+    dataBegin += mr.rleLen;
+    for (u32 i = threadIdx.x; i < nBytes + 16u; i += 256u) s_bits[i] = (allValid && i < nBytes) ? (u8)0xFF : (u8)0;
+    __syncthreads();
+    if (!allValid && !empty && threadIdx.x == 0 && !tbMaskUnrle(blob + kHdr6 + 4u, mr.rleLen, s_bits, nBytes)) s_ti.head.flags = kTbbMaskStream;
+    __syncthreads();
+    // (a mask that names another number of valid pixels than the header does is the single-blob decoder's business: it asks the mask)
+    const u32 own = tbMaskCount(s_bits, nPix, s_red);
+    if (s_ti.head.flags || own != mr.numValid)
+    {
+      if (threadIdx.x == 0) { if (!s_ti.head.flags) s_ti.head.flags = kTbHeader; b.tiles[t] = s_ti; }
+      return;
+    }
+    u8* __restrict__ bitsOut = b.m.bits + (u64)t * b.m.bitStride;
+    for (u32 i = threadIdx.x; i < nBytes; i += 256u) bitsOut[i] = s_bits[i];
+    u8* __restrict__ vOut = b.m.valid + (u64)t * g.tileElems;
+    for (u32 k = threadIdx.x; k < nPix; k += 256u) vOut[k] = (u8)((s_bits[k >> 3] >> (7u - (k & 7u))) & 1u);
+    if (threadIdx.x == 0) b.m.rec[t] = mr;
+    if (s_ti.mode == (u32)IEM_Tiling)
+    {
+      tbBlockValidCounts(s_bits, (u32)g.nRows, (u32)g.nCols, 8u, s_nv);
+      __syncthreads();
+    }
+  }
   if (threadIdx.x != 0) return;
 
   if (s_ti.mode == (u32)IEM_Tiling)
   {
-    // ---- the walk over the block headers; every pixel of a block is valid
+    // ---- the walk over the block headers; a block's length follows from its header and its count of valid pixels
     const BandParams p = tbFillBandParams(g, 8);
-    s_ti.head.flags = tbWalkBlocks<1, 8u>(blob, kTbbDataBegin, blobEnd, p, b.blockOff + (u64)t * g.posStride, [](u32, u32 nElem) { return (int)nElem; });
+    if constexpr (MASKED)
+      s_ti.head.flags = tbWalkBlocks<1, 8u>(blob, dataBegin, blobEnd, p, b.blockOff + (u64)t * g.posStride, [&](u32 k, u32) { return (int)s_nv[k]; });
+    else
+      s_ti.head.flags = tbWalkBlocks<1, 8u>(blob, kTbbDataBegin, blobEnd, p, b.blockOff + (u64)t * g.posStride, [](u32, u32 nElem) { return (int)nElem; });
   }
-  else
+  else if (!MASKED || s_ti.mode != kTbbModeEmpty)
   {
     u32 used = 0;
-    if (!tbbParseTable(blob + kTbbDataBegin, blobEnd - kTbbDataBegin, b.lens + (u64)t * 256u, b.codes + (u64)t * 256u, used)) s_ti.head.flags = kTbbTable;
-    else if (kTbbDataBegin + used + 4u > blobEnd) s_ti.head.flags = kTbbStream;
-    s_ti.tableBytes = kTbbDataBegin + used;
+    if (!tbbParseTable(blob + dataBegin, blobEnd - dataBegin, b.lens + (u64)t * 256u, b.codes + (u64)t * 256u, used)) s_ti.head.flags = kTbbTable;
+    else if (dataBegin + used + 4u > blobEnd) s_ti.head.flags = kTbbStream;
+    s_ti.tableBytes = dataBegin + used;
   }
   b.tiles[t] = s_ti;
 }
 
 // a wave per block: k_decode_tiles (tile_decode.hip) for one value a pixel, every pixel valid, with the tile's own blob
-template<class T>
+template<class T, bool MASKED>
 __global__ void __launch_bounds__(256)
 k_tbbd_blocks(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ offsets, T* __restrict__ outAll, TbbDecodeBuffers b)
 {
@@ -635,8 +935,16 @@ k_tbbd_blocks(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ o
   const u8* __restrict__ blob = arena + offsets[t];
   double zMax;
   { const u64 bits = getBytes(blob + 66, 8); memcpy(&zMax, &bits, 8); }
-  const bool failed = tbDecodeBlock<T, 1, false>(p, zMax, pos, blob, b.tiles[t].head.blobSize, b.blockOff[(u64)t * g.posStride + pos], nullptr,
-                                                 outAll + (u64)t * g.tileElems, s_lut[w], s_head[w]);
+  bool failed;
+  if constexpr (MASKED)
+  {
+    p.allValid = (b.m.rec[t].numValid == (u32)g.tileElems) ? 1 : 0;
+    failed = tbDecodeBlock<T, 1, true>(p, zMax, pos, blob, b.tiles[t].head.blobSize, b.blockOff[(u64)t * g.posStride + pos],
+                                       b.m.bits + (u64)t * b.m.bitStride, outAll + (u64)t * g.tileElems, s_lut[w], s_head[w]);
+  }
+  else
+    failed = tbDecodeBlock<T, 1, false>(p, zMax, pos, blob, b.tiles[t].head.blobSize, b.blockOff[(u64)t * g.posStride + pos], nullptr,
+                                        outAll + (u64)t * g.tileElems, s_lut[w], s_head[w]);
   if (failed && laneId() == 0) atomicOr(&b.tiles[t].head.flags, kTbSibling);
 }
 
@@ -685,7 +993,44 @@ __device__ __forceinline__ int tbbdDecodeOne(const TbbdTable& s, u32 top, u32& s
   return 0;
 }
 
-template<class T>
+// The masked predictor undone in place by ONE wave (Lerc2.cpp:2546-2575; the wave step of k_huff_undelta, huffman_kernels.hip): row
+// by row -- a pixel and the pixel above it never share a step --, 64 pixels a step: a prefix sum over the step's differences, restarts
+// from the pixel above where a segment's head has no valid left neighbour but a valid pixel above (found by a ballot), and a carry
+// for "the last valid pixel so far".  out: the differences at valid pixels, 0 elsewhere; bits: the tile's bit mask where it lies.
+// The load of out[k - nCols] reads what ANOTHER lane of this wave stored a row earlier, with no fence between: a wave's vector memory
+// instructions are issued and performed in order, and a load behind a store of the same wave to the same address returns the stored
+// value (k_huff_undelta, huffman_kernels.hip, stands on the same ground).  It holds for ONE wave only -- do not spread the rows over waves.
+__device__ __forceinline__ void tbbdUndeltaMasked(u8* __restrict__ out, const u8* __restrict__ bits, u32 nRows, u32 nCols)
+{
+  const u32 lane = (u32)laneId();
+  const u64 le = laneMaskLt() | (1ull << lane);
+  u32 carry = 0;
+  for (u32 i = 0; i < nRows; i++)
+    for (u32 j0 = 0; j0 < nCols; j0 += 64u)
+    {
+      const u32 j = j0 + lane;
+      const bool inb = j < nCols;
+      const u32 k = i * nCols + j;
+      const bool valid = inb && maskBit(bits, (i64)k);
+      const bool leftOk = valid && j > 0u && maskBit(bits, (i64)k - 1);
+      const bool fromAbove = valid && !leftOk && i > 0u && maskBit(bits, (i64)k - nCols);
+      const u32 d = valid ? (u32)out[k] : 0u;
+      const u32 above = fromAbove ? (u32)out[k - nCols] : 0u;
+      const u32 s = waveInclusiveScan(d);
+      const u64 mine = __ballot(fromAbove) & le;
+      const int h = mine ? 63 - __clzll((long long)mine) : 0;
+      const u32 sH = __shfl(s, h), dH = __shfl(d, h), aH = __shfl(above, h);
+      const u32 val = (mine ? (aH + s - (sH - dH)) : (carry + s)) & 0xFFu;
+      if (valid) out[k] = (u8)val;
+      const u64 vmask = __ballot(valid);
+      if (vmask) carry = __shfl(val, 63 - __clzll((long long)vmask));
+    }
+}
+
+// MASKED: exactly numValid code words; a partly valid tile's symbols go to the workspace in the order of the stream and from there to
+// the valid positions (a pixel's rank: tbRankedSweep over the bit mask in the workspace), zeros elsewhere; a tile without a valid
+// pixel is zeros
+template<class T, bool MASKED>
 __global__ void __launch_bounds__(256)
 k_tbbd_huff(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ offsets, u8* __restrict__ outAll, TbbDecodeBuffers b)
 {
@@ -702,6 +1047,13 @@ k_tbbd_huff(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ off
   const u32 nPix = (u32)g.tileElems, nCols = (u32)g.nCols, nRows = (u32)g.nRows;
   const u8* __restrict__ blob = arena + offsets[t];
   u8* __restrict__ out = outAll + (u64)t * g.tileElems;
+  u32 numValid = nPix;
+  if constexpr (MASKED)
+  {
+    if (ti.mode == kTbbModeEmpty) { for (u32 k = threadIdx.x; k < nPix; k += 256u) out[k] = 0; return; }
+    numValid = b.m.rec[t].numValid;
+  }
+  const bool partial = MASKED && numValid != nPix;
   const u32 streamBegin = ti.tableBytes, blobEnd = ti.head.blobSize;
 
   // ---- the look-up table (buildDecodeTable, huffman_host.cpp): the host fills it symbol by symbol, so where two codes claim an entry
@@ -789,21 +1141,34 @@ k_tbbd_huff(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ off
   __syncthreads();
   if (threadIdx.x == 0) { u32 run = 0; for (u32 i = 0; i < 256u; i++) { const u32 y = s_scan[i]; s_scan[i] = run; run += y; } s_scan[256] = run; }
   __syncthreads();
-  if (s_any || s_scan[256] < nPix)    // (the chain did not settle -- it cannot be --, or fewer code words than pixels)
+  if (s_any || s_scan[256] < numValid)    // (the chain did not settle -- it cannot be --, or fewer code words than (valid) pixels)
   {
     if (threadIdx.x == 0) b.tiles[t].head.flags = kTbbStream;
     return;
   }
   {
+    u8* dst = partial ? b.m.sym + (u64)t * g.tileElems : out;    // (no __restrict__: `sym` below names the same bytes)
     u32 pos = start, k = s_scan[threadIdx.x];
-    for (u32 i = 0; i < count && k < nPix; i++, k++)
+    for (u32 i = 0; i < count && k < numValid; i++, k++)
     {
       u32 sy = 0;
       const int len = tbbdDecodeOne(s_tab, in.top(pos), sy);
       pos += (u32)len;
-      out[k] = (u8)tbbBin<T>(sy);    // (T)(symbol - offset): the same flip of the top bit
+      dst[k] = (u8)tbbBin<T>(sy);    // (T)(symbol - offset): the same flip of the top bit
     }
   }
+  if constexpr (MASKED)
+    if (partial)
+    {
+      const u8* __restrict__ bits = b.m.bits + (u64)t * b.m.bitStride;
+      const u8* __restrict__ sym = b.m.sym + (u64)t * g.tileElems;
+      __syncthreads();    // (every thread's symbols are in the workspace)
+      tbRankedSweep(bits, nPix, s_scan, [&](u32 k, bool valid, u32 rank) { out[k] = valid ? sym[rank] : (u8)0; });
+      if (ti.mode != (u32)IEM_DeltaHuffman) return;
+      __syncthreads();
+      if (waveId() == 0) tbbdUndeltaMasked(out, bits, nRows, nCols);
+      return;
+    }
   if (ti.mode != (u32)IEM_DeltaHuffman) return;
 
   // ---- the predictor undone (Lerc2.cpp:2499-2523): column 0 sums down the rows, then every row sums along itself; bytes wrap
@@ -837,19 +1202,28 @@ k_tbbd_huff(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ off
   }
 }
 
-template<class T>
+template<class T, bool MASKED>
 static void tbbDecodeT(const TbbGeom& g, const u8* dArena, const u64* dOffsets, const u32* dSizes, void* dTiles, const TbbDecodeBuffers& b, hipStream_t st)
 {
   const int nPos = g.nTV * g.nTH;
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_parse<T>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, dSizes, b);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_blocks<T>), dim3((nPos + 3) / 4, g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, (T*)dTiles, b);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_huff<T>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, (u8*)dTiles, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_parse<T, MASKED>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, dSizes, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_blocks<T, MASKED>), dim3((nPos + 3) / 4, g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, (T*)dTiles, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_huff<T, MASKED>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, (u8*)dTiles, b);
 }
 
 void launchTbbDecode(const TbbGeom& g, const u8* dArena, const u64* dOffsets, const u32* dSizes, void* dTiles, const TbbDecodeBuffers& b, hipStream_t st)
 {
-  if (g.dt == DT_Char) tbbDecodeT<signed char>(g, dArena, dOffsets, dSizes, dTiles, b, st);
-  else if (g.dt == DT_Byte) tbbDecodeT<unsigned char>(g, dArena, dOffsets, dSizes, dTiles, b, st);
+  const bool masked = b.m.valid != nullptr;
+  if (g.dt == DT_Char)
+  {
+    if (masked) tbbDecodeT<signed char, true>(g, dArena, dOffsets, dSizes, dTiles, b, st);
+    else tbbDecodeT<signed char, false>(g, dArena, dOffsets, dSizes, dTiles, b, st);
+  }
+  else if (g.dt == DT_Byte)
+  {
+    if (masked) tbbDecodeT<unsigned char, true>(g, dArena, dOffsets, dSizes, dTiles, b, st);
+    else tbbDecodeT<unsigned char, false>(g, dArena, dOffsets, dSizes, dTiles, b, st);
+  }
 }
 
 }    // namespace lerc

@@ -65,46 +65,34 @@ k_tmb_prelude(TmbGeom g, double maxZErr, u32 cand, const T* __restrict__ data, c
   u8* __restrict__ bitsOut = b.bits + (u64)t * g.bitStride;
   const int facCand[9] = { 1, 2, 10, 20, 100, 200, 1000, 2000, 10000 };
 
-  u32 cnt = 0, flags = 0;
+  u32 flags = 0;
   Acc mn = TmbAcc<T>::hi(), mx = TmbAcc<T>::lo();
   bool frac = false;
   double rerr[9];
 #pragma unroll
   for (int c = 0; c < 9; c++) rerr[c] = 0;
-  for (u32 by = threadIdx.x; by < nBytes; by += 256u)
+  const u32 cnt = tbMaskToBits(vb, nPix, s_bits, bitsOut, [&](u32 k)
   {
-    u32 m = 0;
-    for (u32 j = 0; j < 8u; j++)
+    const T v = px[k];
+    if (isFlt && v != v) { flags |= kTmbNaN; return; }
+    const Acc a = (Acc)v;
+    mn = a < mn ? a : mn; mx = a > mx ? a : mx;
+    if (isFlt)
     {
-      const u32 k = 8u * by + j;
-      if (k >= nPix) { m |= 0x80u >> j; continue; }    // tail bits stay set, like BitMask::SetAllValid + SetInvalid (Lerc.cpp:959-975)
-      if (vb[k] == 0) continue;
-      m |= 0x80u >> j;
-      cnt++;
-      const T v = px[k];
-      if (isFlt && v != v) { flags |= kTmbNaN; continue; }
-      const Acc a = (Acc)v;
-      mn = a < mn ? a : mn; mx = a > mx ? a : mx;
-      if (isFlt)
-      {
-        const double x = (double)v;
-        if (!(v == (T)floor(x + 0.5))) frac = true;    // Lerc.h:271 IsInt
-        // TryRaiseMaxZError (Lerc2.cpp:1233-1318): the largest rounding error per candidate factor.  Every factor is a multiple of
-        // the ones in front of it, so a value that one factor makes an integer adds nothing to the later ones either way.
+      const double x = (double)v;
+      if (!(v == (T)floor(x + 0.5))) frac = true;    // Lerc.h:271 IsInt
+      // TryRaiseMaxZError (Lerc2.cpp:1233-1318): the largest rounding error per candidate factor.  Every factor is a multiple of
+      // the ones in front of it, so a value that one factor makes an integer adds nothing to the later ones either way.
 #pragma unroll
-        for (int c = 0; c < 9; c++)
-          if ((cand >> c) & 1u)
-          {
-            const double z = x * facCand[c];
-            const double dlt = fabs(floor(z + 0.5) - z);
-            rerr[c] = dlt > rerr[c] ? dlt : rerr[c];
-          }
-      }
+      for (int c = 0; c < 9; c++)
+        if ((cand >> c) & 1u)
+        {
+          const double z = x * facCand[c];
+          const double dlt = fabs(floor(z + 0.5) - z);
+          rerr[c] = dlt > rerr[c] ? dlt : rerr[c];
+        }
     }
-    s_bits[by] = (u8)m;
-    bitsOut[by] = (u8)m;
-  }
-  for (u32 by = nBytes + threadIdx.x; by < nBytes + 16u; by += 256u) s_bits[by] = 0;
+  });
   const u32 numValid = (u32)blockSum((u64)cnt, s_red);
   const u32 anyFlags = (u32)blockSum((u64)flags, s_red) ? kTmbNaN : 0u;    // (the only flag raised so far)
   const u32 anyFrac = (u32)blockSum(frac ? 1ull : 0ull, s_red);
@@ -162,47 +150,12 @@ k_tmb_prelude(TmbGeom g, double maxZErr, u32 cand, const T* __restrict__ data, c
     }
   }
 
-  // ---- the mask's run-length stream: [int16 n][payload] ..., n > 0 literal bytes, n < 0 one byte -n times, -32768 ends it; a run
-  // is opened only where at least 5 equal bytes start and one more byte follows; segments are cut at 32767
+  // ---- the mask's run-length stream (tbMaskRle)
   u32 rleLen = 0;
   if (fl == 0 && numValid > 0 && numValid < nPix)
   {
-    u8* __restrict__ out = b.rle + (u64)t * g.rleStride;
-    const u32 cap = g.rleStride, n = nBytes;
-    u32 at = 0, i = 0;
-    bool fits = true;
-    while (i < n && fits)
-    {
-      const u32 litBeg = i;
-      while (i < n)
-      {
-        const bool runStarts = (i + 5 < n) && s_bits[i] == s_bits[i + 1] && s_bits[i] == s_bits[i + 2] && s_bits[i] == s_bits[i + 3] && s_bits[i] == s_bits[i + 4];
-        if (runStarts) break;
-        i++;
-      }
-      for (u32 p = litBeg; p < i && fits;)
-      {
-        const u32 len = min(32767u, i - p);
-        if (at + 2u + len + 8u > cap) { fits = false; break; }
-        out[at] = (u8)(len & 255u); out[at + 1] = (u8)(len >> 8); at += 2;
-        for (u32 q = 0; q < len; q++) out[at + q] = s_bits[p + q];
-        at += len; p += len;
-      }
-      if (i >= n || !fits) break;
-      u32 e = i;
-      while (e + 1 < n && s_bits[e + 1] == s_bits[i]) e++;
-      for (u32 left = e - i + 1; left > 0 && fits;)
-      {
-        const u32 len = min(32767u, left);
-        if (at + 3u + 8u > cap) { fits = false; break; }
-        const u32 neg = (u32)(-(int)len) & 0xFFFFu;
-        out[at] = (u8)(neg & 255u); out[at + 1] = (u8)(neg >> 8); out[at + 2] = s_bits[i]; at += 3;
-        left -= len;
-      }
-      i = e + 1;
-    }
-    if (fits && at + 2u <= cap) { out[at] = 0x00; out[at + 1] = 0x80; at += 2; rleLen = at; }
-    else fl |= kTmbRle;
+    rleLen = tbMaskRle(s_bits, nBytes, b.rle + (u64)t * g.rleStride, g.rleStride);
+    if (!rleLen) fl |= kTmbRle;
   }
   ti.head.flags = fl;
   ti.rleLen = rleLen;
@@ -213,36 +166,6 @@ k_tmb_prelude(TmbGeom g, double maxZErr, u32 cand, const T* __restrict__ data, c
   b.tiles[t] = ti;
 }
 
-// The pixels of a tile in row order, the valid ones with their rank among the valid ones, by one workgroup of 256 threads: a thread
-// takes a byte of the bit mask (8 pixels) a round, a round's popcounts are scanned over the workgroup.  f(pixel, valid, rank) is
-// called once for every pixel below nPix (the tail bits of an encoder's mask are set: they do not count).  s: 4 words of LDS.
-template<class F>
-__device__ __forceinline__ u32 tmbRankedSweep(const u8* bits, u32 nPix, u32* s, F f)
-{
-  const u32 nBytes = (nPix + 7u) >> 3;
-  u32 run = 0;
-  for (u32 base = 0; base < nBytes; base += 256u)
-  {
-    const u32 by = base + threadIdx.x;
-    u32 m = by < nBytes ? (u32)bits[by] : 0u;
-    if (8u * by + 8u > nPix) m &= (8u * by < nPix) ? (0xFF00u >> (nPix - 8u * by)) & 0xFFu : 0u;
-    const u32 c = (u32)__popc(m), inc = waveInclusiveScan(c);
-    if (laneId() == 63) s[waveId()] = inc;
-    __syncthreads();
-    u32 r = run + inc - c;
-    for (int w = 0; w < waveId(); w++) r += s[w];
-    run += s[0] + s[1] + s[2] + s[3];
-    for (u32 j = 0; j < 8u && 8u * by + j < nPix; j++)
-    {
-      const bool valid = (m & (0x80u >> j)) != 0u;
-      f(8u * by + j, valid, r);
-      r += valid ? 1u : 0u;
-    }
-    __syncthreads();
-  }
-  return run;
-}
-
 // What lies in front of a tile's block stream, by one workgroup: header (Lerc2.cpp:724-786; checksum patched by k_tmb_checksum),
 // mask section; where the valid pixels differ: ranges and the "one sweep" byte, and behind a 1 the valid pixels raw in row
 // order (Lerc2::WriteDataOneSweep).  s_hdr: 96 bytes of LDS, s_w: 4 words.
@@ -250,17 +173,9 @@ template<class T>
 __device__ __forceinline__ void tmbWriteFront(const TmbGeom& g, u32 t, const TmbTile& ti, const T* __restrict__ px, u8* __restrict__ blob, const TmbEncodeBuffers& b,
                                               u8* s_hdr, u32* s_w)
 {
-  if (threadIdx.x == 0)
-  {
-    const TbHeader6 h = { kCodecVersion, 0u, g.nRows, g.nCols, 1, (int)ti.numValid, (int)ti.mbSize, (int)ti.head.blobSize, g.dt, 0,
-                          ti.isInt ? 0x100u : 0u, ti.maxZErr, ti.zMin, ti.zMax };
-    tbWriteHeader6(s_hdr, h);
-    putBytes(s_hdr + kHdr6, (u64)ti.rleLen, 4);
-  }
-  __syncthreads();
-  for (u32 i = threadIdx.x; i < kHdr6 + 4u; i += 256u) blob[i] = s_hdr[i];
-  const u8* __restrict__ rle = b.rle + (u64)t * g.rleStride;
-  for (u32 i = threadIdx.x; i < ti.rleLen; i += 256u) blob[kHdr6 + 4u + i] = rle[i];
+  const TbHeader6 h = { kCodecVersion, 0u, g.nRows, g.nCols, 1, (int)ti.numValid, (int)ti.mbSize, (int)ti.head.blobSize, g.dt, 0,
+                        ti.isInt ? 0x100u : 0u, ti.maxZErr, ti.zMin, ti.zMax };
+  tbWriteHeaderMask(blob, h, b.rle + (u64)t * g.rleStride, ti.rleLen, s_hdr);
   if (ti.kind == kTmbKindEmpty || ti.kind == kTmbKindConst) return;    // (Lerc2.cpp:235-241, :255: nothing behind the mask)
   if (threadIdx.x == 0)
   {
@@ -281,7 +196,7 @@ __device__ __forceinline__ void tmbWriteFront(const TmbGeom& g, u32 t, const Tmb
   };
   const u32 nPix = (u32)g.tileElems;
   if (ti.numValid == nPix) { for (u32 k = threadIdx.x; k < nPix; k += 256u) put(k, true, k); }
-  else tmbRankedSweep(b.bits + (u64)t * g.bitStride, nPix, s_w, put);
+  else tbRankedSweep(b.bits + (u64)t * g.bitStride, nPix, s_w, put);
 }
 
 // A wave per MB x MB block of a tile (blockIdx.y): k_encode_tiles (tile_encode.hip) for one value a pixel, with the tile's own mask,
@@ -524,22 +439,7 @@ k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
   __syncthreads();
   if (!allValid && kind != kTmbKindEmpty && threadIdx.x == 0)
   {
-    const u8* src = blob + kHdr6 + 4u;
-    u32 left = nm, at = 0, sp = 0;
-    bool ok = false;
-    for (;;)
-    {
-      if (left < 2u) break;
-      const int cnt = (int)(short)(u16)(src[sp] | (src[sp + 1] << 8));
-      sp += 2; left -= 2;
-      if (cnt == -32768) { ok = true; break; }
-      const u32 n = (u32)(cnt < 0 ? -cnt : cnt), payload = cnt > 0 ? n : 1u;
-      if (left < payload + 2u || at + n > nBytes) break;    // + 2: a count always follows (RLE.cpp:310)
-      if (cnt > 0) for (u32 k = 0; k < n; k++) s_bits[at + k] = src[sp + k];
-      else { const u8 v = src[sp]; for (u32 k = 0; k < n; k++) s_bits[at + k] = v; }
-      at += n; sp += payload; left -= payload;
-    }
-    if (!ok) s_flags = kTmbMaskStream;
+    if (!tbMaskUnrle(blob + kHdr6 + 4u, nm, s_bits, nBytes)) s_flags = kTmbMaskStream;
   }
   __syncthreads();
   if (s_flags) { if (threadIdx.x == 0) { s_ti.head.flags = s_flags; b.tiles[t] = s_ti; } return; }
@@ -552,19 +452,12 @@ k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
     const u8* __restrict__ raw = blob + s_ti.dataBegin;
     const u64 constBits = s_ti.minBits;
     const bool sweep = kind == kTmbKindOneSweep;
-    u32 cnt = 0;
-    for (u32 by = threadIdx.x; by < nBytes; by += 256u)
-    {
-      u32 m = s_bits[by];
-      if (8u * by + 8u > nPix) m &= (0xFF00u >> (nPix - 8u * by)) & 0xFFu;
-      cnt += (u32)__popc(m);
-    }
-    if ((u32)blockSum((u64)cnt, s_red) != s_ti.numValid)
+    if (tbMaskCount(s_bits, nPix, s_red) != s_ti.numValid)
     {
       if (threadIdx.x == 0) { s_ti.head.flags = kTbHeader; b.tiles[t] = s_ti; }
       return;
     }
-    tmbRankedSweep(s_bits, nPix, s_w, [&](u32 k, bool valid, u32 rank)
+    tbRankedSweep(s_bits, nPix, s_w, [&](u32 k, bool valid, u32 rank)
     {
       const u64 bits = !valid ? 0ull : sweep ? getBytes(raw + (u64)rank * TB, (int)TB) : constBits;    // (0 where nothing is valid, like FillConstImage)
       T v; memcpy(&v, &bits, sizeof(T));
@@ -587,16 +480,7 @@ k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
 
   // ---- valid pixels per block
   const u32 MB = kind == kTmbKindBlocks16 ? 16u : 8u;
-  const u32 nTV = ((u32)g.nRows + MB - 1u) / MB, nTH = ((u32)g.nCols + MB - 1u) / MB, nPos = nTV * nTH;
-  for (u32 pos = threadIdx.x; pos < nPos; pos += 256u)
-  {
-    const u32 it = pos / nTH, jt = pos - it * nTH;
-    const u32 i1 = min((u32)g.nRows, it * MB + MB), j1 = min((u32)g.nCols, jt * MB + MB);
-    u32 n = 0;
-    for (u32 i = it * MB; i < i1; i++)
-      for (u32 j = jt * MB; j < j1; j++) { const u32 k = i * (u32)g.nCols + j; n += (s_bits[k >> 3] >> (7u - (k & 7u))) & 1u; }
-    s_nv[pos] = (u16)n;    // (at most 256)
-  }
+  tbBlockValidCounts(s_bits, (u32)g.nRows, (u32)g.nCols, MB, s_nv);
   __syncthreads();
 
   // ---- the walk: a block's length follows from its header and its valid count

@@ -5,11 +5,15 @@ device resident, on one MI355X:
   (a) lerc_amd_encode_tiles_device / _slots and their decoding counterparts of THIS build
   (b) the same calls on a library built from the PARENT commit (--parent-lib, or PARENT_LIB), loaded through LERC_AMD_LIBRARY
 
+and the MASKED case: the byte island -- the same mosaic under synth.island_mask (98 tiles all valid, 76 empty, 82 partial) --
+through lerc_amd_encode_tiles_device_masked / lerc_amd_decode_tiles_device_masked, packed.  The parent does every such tile one by one.
+
 each in a fresh process of its own (this script with --measure).  Build the parent with
   git worktree add /some/scratch/parent HEAD~1 && make -C /some/scratch/parent/lerc_amd/csrc
 
-Warm-up, then the median and the interquartile range of REPS (21) repetitions, HIP events around the calls.  The pass line: (b) / (a),
-each way, exceeds 1 by more than three times the larger relative interquartile range of the two runs.  Writes
+Warm-up, then the median and the interquartile range of REPS (21) repetitions, HIP events around the calls.  The pass lines, with s the
+larger relative interquartile range of the two runs: masked, (b) / (a) > 1 + 3 s each way (this build is faster); all valid,
+(b) / (a) >= 1 - 3 s (this build is no slower).  Writes
 profiles/tiles_bytes_time.txt.  Run it under a time limit of its own:  timeout -k 10 600 python tools/time_tiles_bytes.py --parent-lib ...
 """
 import argparse
@@ -82,11 +86,36 @@ def measure():
            "enc_packed": timed(enc_packed), "dec_packed": timed(dec_packed)}
     res["enc_slots"] = timed(enc_slots)
     res["dec_slots"] = timed(dec_slots)
+
+    # ---- the masked case: the byte island
+    masks_np = synth.cut_tiles(synth.island_mask(4096), 256)
+    valid = torch.from_numpy(masks_np.copy()).cuda()
+    valid_out = torch.zeros((n, r, c), dtype=torch.uint8, device="cuda")
+
+    def enc_masked():
+        rc, offs, sizes, used = api.encode_tiles_device_masked(codec, tiles, valid, 0, arena)
+        assert rc == 0, rc
+        state["masked"] = (offs, sizes)
+
+    def dec_masked():
+        offs, sizes = state["masked"]
+        assert api.decode_tiles_device_masked(codec, arena, offs, sizes, out, valid_out) == 0
+
+    c0 = codec.tile_batch_counters()
+    enc_masked()
+    dec_masked()
+    c1 = codec.tile_batch_counters()
+    assert np.array_equal(valid_out.cpu().numpy(), masks_np) and np.array_equal(out.cpu().numpy()[masks_np > 0], tiles_np[masks_np > 0])
+    res["masked_counters"] = [int(c1[i] - c0[i]) for i in range(4)]
+    res["enc_masked"] = timed(enc_masked)
+    res["dec_masked"] = timed(dec_masked)
     codec.lib.lerc_amd_profile_enable.argtypes = [ct.c_void_p, ct.c_int]
     codec.lib.lerc_amd_profile_read.argtypes = [ct.c_void_p, ct.c_char_p, ct.c_int, ct.c_int]
     codec.lib.lerc_amd_profile_enable(codec.h, 1)
     enc_packed()
     dec_packed()
+    enc_masked()
+    dec_masked()
     buf = ct.create_string_buffer(8192)
     codec.lib.lerc_amd_profile_read(codec.h, buf, 8192, 1)
     codec.lib.lerc_amd_profile_enable(codec.h, 0)
@@ -122,18 +151,21 @@ def main():
              "%d uint8 tiles of 256 x 256, lossless (%.1f Mpixel); median [interquartile range] of %d, ms; (a) this build, (b) the parent commit"
              % (a["tiles"], a["mpix"], REPS)]
     for name, r in (("a", a), ("b", b)):
-        lines.append("  (%s) one round trip: %d tiles encoded by the batch's launches, %d one by one; %d / %d decoded" % ((name,) + tuple(r["counters"])))
+        lines.append("  (%s) one round trip, all valid: %d tiles encoded by the batch's launches, %d one by one; %d / %d decoded" % ((name,) + tuple(r["counters"])))
+        lines.append("  (%s) one round trip, the island: %d tiles encoded by the batch's launches, %d one by one; %d / %d decoded"
+                     % ((name,) + tuple(r["masked_counters"])))
     ok = True
-    for key, label in (("enc_packed", "encode, packed "), ("dec_packed", "decode, packed "), ("enc_slots", "encode, slotted"), ("dec_slots", "decode, slotted")):
+    for key, label, faster in (("enc_packed", "encode, packed ", False), ("dec_packed", "decode, packed ", False), ("enc_slots", "encode, slotted", False),
+                               ("dec_slots", "decode, slotted", False), ("enc_masked", "encode, island ", True), ("dec_masked", "decode, island ", True)):
         ma, mb = a[key], b[key]
         spread = max(ma["iqr"] / ma["median"], mb["iqr"] / mb["median"])
         ratio = mb["median"] / ma["median"]
-        met = ratio > 1 + 3 * spread
+        met = ratio > 1 + 3 * spread if faster else ratio >= 1 - 3 * spread
         ok = ok and met
-        lines.append("  %s  (a) %9.3f [%7.3f] %9.1f MPix/s   (b) %9.3f [%7.3f] %9.1f MPix/s   (b)/(a) %7.2f   pass line 1 + 3 x %.4f: %s"
+        lines.append("  %s  (a) %9.3f [%7.3f] %9.1f MPix/s   (b) %9.3f [%7.3f] %9.1f MPix/s   (b)/(a) %7.2f   pass line 1 %s 3 x %.4f: %s"
                      % (label, ma["median"], ma["iqr"], a["mpix"] / ma["median"] * 1e3, mb["median"], mb["iqr"], a["mpix"] / mb["median"] * 1e3,
-                        ratio, spread, "met" if met else "NOT met"))
-    lines.append("  profile groups of one (a) encode + decode (group, ms, launches):")
+                        ratio, "+" if faster else "-", spread, "met" if met else "NOT met"))
+    lines.append("  profile groups of one (a) encode + decode, all valid and island (group, ms, launches):")
     lines += ["    " + ln for ln in a["profile"]]
     lines.append("pass line met: %s" % ("yes" if ok else "NO"))
     text = "\n".join(lines) + "\n"
