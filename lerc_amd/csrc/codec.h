@@ -253,6 +253,30 @@ struct DecodeRequest
 };
 u32 decodeDevice(Context& ctx, const DecodeRequest& rq);
 
+// ---- the general band path (codec_encode_band.cpp, codec_decode_band.cpp): every call the streaming kernels do not take blind
+u32 encodeBands(Context& ctx, const EncodeRequest& rq, u32& numBytesNeeded, u32& numBytesWritten);    // band after band (BandEncoder)
+// (fastLevel: the streaming form where a band qualifies, DecodeForm; fellBack: a streaming form handed a band on, the caller repeats one tier down)
+u32 decodeBands(Context& ctx, const DecodeRequest& rq, int fastLevel, bool& fellBack);
+bool fastEncodeOneLaunch();    // LERC_AMD_ENCODE_LAUNCHES=2 keeps the two-launch form for a single raster (codec_encode.cpp)
+// a band's result cell of the streaming decoders (codec_decode.cpp; device, zeroed before the launches, copied back in one piece):
+//   [FastDecodeParams, 128 B reserved][fallback bits 16 B][pad to 192]
+constexpr size_t kCellParams = 0, kCellFallback = 128, kCellBytes = 192;
+size_t fastBandWorkspace(int nRows, int nCols, u32 sizeGiven, u32 nTiles = 1);
+bool launchFastBand(Context& ctx, StreamTicket& t, const u8* dBand, u32 sizeGiven, void* dOutBand, u8* dCell, u8* hCell = nullptr);
+u32 fastFlagBits(const u32* cells, u32 epoch);    // reason bits of a tile's / band's four epoch tagged flag cells
+u32 fastBandVerdict(const u8* hCell, u32 epoch, u32* blobEnd = nullptr);    // 0 = decoded and checksum good, else the reason bits (tile_fast.h: kVerdict...)
+
+// ---- small pieces both directions share (codec_common.cpp)
+// masks of this many bytes or more are run-length coded / decoded on the device (rle_kernels.hip); LERC_AMD_DEVICE_RLE=0: never,
+// =<bytes>: from masks of that many bytes on -- a test knob; default: 256 KB, as for the helper threads
+size_t deviceRleFrom();
+// valid pixels in front of every group of 32 (dBase[nGroups]: all of them): three allocations, two launches; nullptr: no room
+u32* enqueueMaskCount(Context& ctx, const u8* dBits, i64 nPix, hipStream_t st);
+// one sweep under a mask: the count above, then k_one_sweep packs (src: pixels, dst: stream) or unpacks the valid pixels
+bool enqueueMaskedOneSweep(Context& ctx, bool pack, const u8* src, u8* dst, const u8* dBits, i64 nPix, int bytesPerPixel, hipStream_t st);
+// what every user of the block kernels fills alike; callers set intLossless, tryDiff, zMaxHdr, checkOverflow where they differ from 0
+BandParams makeBandParams(int dt, int nRows, int nCols, int nD, int version, int mb, double maxZErr, bool allValid);
+
 // The same two calls in two halves, for callers that keep several operations in flight on the stream (the asynchronous
 // device API, capi.cpp): the enqueue half puts the streaming kernels and the copy of their verdict into `slot` (pinned,
 // Context::kAsyncSlotBytes) on the stream and returns true -- or false when the request is not one the streaming kernels
@@ -284,6 +308,34 @@ struct BlobInfo
   double zMin = 0, zMax = 0, maxZErr = 0;
 };
 u32 getBlobInfo(const u8* blob, u32 n, BlobInfo& info, double* mins = nullptr, double* maxs = nullptr, size_t nElem = 0);
+
+// reads small pieces of a blob that lives on the host, the device, or both (codec_decode_band.cpp)
+struct BlobReader
+{
+  const u8* h;
+  const u8* d;
+  u32 n;
+  hipStream_t st;
+  // bytes already fetched (the head of the current band): served without another device round trip
+  const u8* cache = nullptr;
+  u64 cacheOff = 0;
+  size_t cacheLen = 0;
+  Context* ctx = nullptr;    // small device reads go through its pinned mirror (a pageable target costs a staging copy)
+  bool read(u64 off, size_t len, u8* dst) const;
+};
+struct BandDesc
+{
+  u64 offset = 0;
+  Header hd;
+  size_t hdrLen = 0;
+  int numBytesMask = 0;
+  u8 head[2048];         // first bytes of the band (header, and for unmasked bands ranges + mode bytes + a Huffman code table)
+  size_t headLen = 0;
+};
+// The chain of band headers (Lerc::GetLercInfo, Lerc.cpp:92-182): kOk with every band that is there; kFailed where the first is no
+// Lerc2 header (bands stays empty), does not fit blobSize (bands holds it alone), or a later one is of another shape or does not fit
+u32 walkBands(const BlobReader& rd, u32 blobSize, std::vector<BandDesc>& bands);
+int bandsMaskCount(const std::vector<BandDesc>& bands);    // how many masks a caller must have room for: 0, 1 or one per band
 
 // legacy Lerc1 ("CntZImage") blobs: decode only, on the device (lerc1_host.cpp)
 bool isLerc1(const u8* hBlob, u32 n);

@@ -241,17 +241,6 @@ bool rleDecode(const u8* src, size_t left, u8* dst, size_t dstSize, size_t* writ
 // ------------------------------------------------------------------------------------------------
 // blob info: hop over concatenated band blobs (Lerc.cpp:92-182, :1012-1042)
 // ------------------------------------------------------------------------------------------------
-static bool peekBand(const u8* p, size_t n, Header& h, bool& hasMask, size_t& hdrLen)
-{
-  if (!p || !readHeader(p, n, h, hdrLen)) return false;
-  int nm = 0;
-  if (n - hdrLen < 4) return false;
-  memcpy(&nm, p + hdrLen, 4);
-  if (nm < 0) return false;
-  hasMask = nm > 0;
-  return true;
-}
-
 // per-depth ranges of one band (Lerc2::GetRanges, Lerc2.cpp:516-573); host-side header parsing only
 static u32 bandRanges(const u8* p, size_t n, int iBand, const Header& h, size_t hdrLen, double* mins, double* maxs, size_t nElem)
 {
@@ -280,42 +269,76 @@ static u32 bandRanges(const u8* p, size_t n, int iBand, const Header& h, size_t 
 u32 getBlobInfo(const u8* blob, u32 n, BlobInfo& info, double* mins, double* maxs, size_t nElem)
 {
   info = BlobInfo();
-  Header h;
-  bool hasMask = false;
-  size_t hdrLen = 0;
-  int nMasks = 0;
-  if (!peekBand(blob, n, h, hasMask, hdrLen)) return kFailed;    // Lerc1 legacy blobs are not handled by this library
+  if (!blob) return kFailed;
+  std::vector<BandDesc> bands;
+  const BlobReader rd{ blob, nullptr, n, nullptr };
+  const u32 walked = walkBands(rd, n, bands);
+  if (bands.empty()) return kFailed;    // Lerc1 legacy blobs are not handled by this library
+  const Header& h = bands[0].hd;
   info.version = h.version; info.nDepth = h.nDepth; info.nCols = h.nCols; info.nRows = h.nRows;
-  info.numValid = h.numValid; info.blobSize = (u32)h.blobSize; info.dt = h.dt;
-  info.zMin = h.zMin; info.zMax = h.zMax; info.maxZErr = h.maxZErr; info.nUsesNoData = h.passNoData ? 1 : 0;
-  bool more = (h.version <= 5) || (h.nBlobsMore > 0);
-  if (hasMask || info.numValid == 0) nMasks = 1;
-  if (mins && maxs) { const u32 e = bandRanges(blob, n, 0, h, hdrLen, mins, maxs, nElem); if (e != kOk) return e; }
-  info.nBands = 1;
-  if (info.blobSize > n) return kFailed;
-  Header hn;
-  while (more && peekBand(blob + info.blobSize, n - info.blobSize, hn, hasMask, hdrLen))
+  info.numValid = h.numValid; info.dt = h.dt;
+  info.zMin = h.zMin; info.zMax = h.zMax; info.maxZErr = h.maxZErr;
+  for (const BandDesc& b : bands)
   {
-    if (hn.nDepth != info.nDepth || hn.nCols != info.nCols || hn.nRows != info.nRows || hn.dt != info.dt) return kFailed;
-    more = (hn.version <= 5) || (hn.nBlobsMore > 0);
-    if (hn.passNoData) info.nUsesNoData++;
-    if (hasMask || hn.numValid != info.numValid) nMasks = 2;
-    if ((size_t)info.blobSize > (size_t)UINT_MAX - (size_t)hn.blobSize) return kFailed;
-    if ((size_t)info.blobSize + (size_t)hn.blobSize > (size_t)n) return kFailed;
-    info.zMin = std::min(info.zMin, hn.zMin);
-    info.zMax = std::max(info.zMax, hn.zMax);
-    info.maxZErr = std::max(info.maxZErr, hn.maxZErr);
+    info.zMin = std::min(info.zMin, b.hd.zMin);
+    info.zMax = std::max(info.zMax, b.hd.zMax);
+    info.maxZErr = std::max(info.maxZErr, b.hd.maxZErr);
+    if (b.hd.passNoData) info.nUsesNoData++;
     if (mins && maxs)
     {
-      const u32 e = bandRanges(blob + info.blobSize, n - info.blobSize, info.nBands, hn, hdrLen, mins, maxs, nElem);
+      const u32 e = bandRanges(blob + b.offset, n - b.offset, info.nBands, b.hd, b.hdrLen, mins, maxs, nElem);
       if (e != kOk) return e;
     }
-    info.blobSize += (u32)hn.blobSize;
+    info.blobSize += (u32)b.hd.blobSize;
     info.nBands++;
   }
-  info.nMasks = nMasks > 1 ? info.nBands : nMasks;
+  if (walked != kOk) return walked;
+  info.nMasks = bandsMaskCount(bands);
   if (info.nUsesNoData > 0) info.nUsesNoData = info.nBands;
   return kOk;
+}
+
+// ------------------------------------------------------------------------------------------------
+// small pieces the encoder and the decoder share
+// ------------------------------------------------------------------------------------------------
+size_t deviceRleFrom()
+{
+  static const size_t from = []() -> size_t { const char* e = getenv("LERC_AMD_DEVICE_RLE"); const long v = e ? atol(e) : 1; return v <= 0 ? ~(size_t)0 : v < 16 ? (size_t)(256u << 10) : (size_t)v; }();
+  return from;
+}
+
+u32* enqueueMaskCount(Context& ctx, const u8* dBits, i64 nPix, hipStream_t st)
+{
+  const i64 nGroups = (nPix + 31) >> 5;
+  u32* dCounts = ctx.allocT<u32>((size_t)nGroups + 4);
+  u32* dBase = ctx.allocT<u32>((size_t)nGroups + 4);
+  u32* dScr = ctx.allocT<u32>((size_t)nGroups / 1024 + 8);
+  if (!dCounts || !dBase || !dScr) return nullptr;
+  launchMaskGroupCounts(dBits, nPix, dCounts, st);
+  launchExclusiveScan(dCounts, dBase, (u32)nGroups, dScr, st);
+  return dBase;
+}
+
+bool enqueueMaskedOneSweep(Context& ctx, bool pack, const u8* src, u8* dst, const u8* dBits, i64 nPix, int bytesPerPixel, hipStream_t st)
+{
+  const u32* dBase = enqueueMaskCount(ctx, dBits, nPix, st);
+  if (!dBase) return false;
+  launchOneSweep(pack, src, dst, dBits, dBase, nPix, bytesPerPixel, st);
+  return true;
+}
+
+BandParams makeBandParams(int dt, int nRows, int nCols, int nD, int version, int mb, double maxZErr, bool allValid)
+{
+  BandParams bp;
+  memset(&bp, 0, sizeof(bp));
+  bp.nRows = nRows; bp.nCols = nCols; bp.nDepth = nD; bp.dt = dt; bp.version = version;
+  bp.mb = mb; bp.nTV = (nRows + mb - 1) / mb; bp.nTH = (nCols + mb - 1) / mb;
+  bp.allValid = allValid ? 1 : 0;
+  bp.maxQ = maxValToQuantize(dt);
+  bp.maxZErr = maxZErr;
+  bp.scale = maxZErr > 0 ? 1 / (2 * maxZErr) : 0;
+  bp.invScale = 2 * maxZErr;
+  return bp;
 }
 
 // ------------------------------------------------------------------------------------------------
