@@ -53,7 +53,7 @@ LERC_AMD_API lerc_status lerc_amd_decode_device_async(lerc_amd_context* ctx, con
 LERC_AMD_API lerc_status lerc_amd_finish(lerc_amd_context* ctx, unsigned int ticket, unsigned int* nBytes);
 
 /* Tile mosaics: nTiles rasters of one shape, contiguous on the device ([nTiles][nRows][nCols], 1 band, nDepth 1,
- * no masks -- see the _masked calls below), in ONE call (tiles are independent blobs; ranks of a multi-GPU job take tile ranges).
+ * no masks -- see the _masked calls below, and the _bands calls for tiles that are band stacks), in ONE call (tiles are independent blobs; ranks of a multi-GPU job take tile ranges).
  * Tile t becomes exactly the blob lerc_encode() would make of it, at dArena + offsets[t] (16-byte aligned), sizes[t]
  * bytes long; offsets / sizes / arenaUsed are HOST arrays the caller provides.  BufferTooSmall(3) if the arena is
  * too small (lerc_computeCompressedSize bounds a tile; nRows * nCols * sizeof(T) + 128 per tile always suffices).
@@ -110,6 +110,42 @@ LERC_AMD_API lerc_status lerc_amd_encode_tiles_device_masked(lerc_amd_context* c
  * decoded all the same, and the call returns the first such status. */
 LERC_AMD_API lerc_status lerc_amd_decode_tiles_device_masked(lerc_amd_context* ctx, const unsigned char* dArena, const unsigned long long* offsets,
     const unsigned int* sizes, int nTiles, int nCols, int nRows, unsigned int dataType, void* dTiles, unsigned char* dValidBytes);
+/* Mosaics of BAND STACKS: every tile is nBands rasters of one shape, one blob a tile.  dTiles: device, [nTiles][nBands][nRows][nCols];
+ * dValidBytes: device, [nTiles][nMasks][nRows][nCols]; nMasks is 0 (dValidBytes must be NULL), 1 (one mask a tile, shared by its bands)
+ * or nBands.  slotBytes, offsets, sizes and arenaUsed as in the _masked calls, one blob a tile: a packed tile begins 16-byte aligned,
+ * the bands inside a tile are byte-adjacent.  Tile t's blob is byte for byte what lerc_encode(tile t, nDepth 1, nBands, nMasks, mask t,
+ * maxZErr) makes: the band blobs back to back, each header naming the number of blobs behind it, the mask section in the first band
+ * only.  With nBands == 1 these are the calls above.
+ * The batch's own launches (one set per sub-batch, one host wait; the unit is the plane, tile * nBands + band, and a tile is the
+ * batch's only if all its planes are) take the wide types -- float32, float64, the 16- and 32-bit integers -- with nMasks 0 or 1, up to
+ * 131 072 pixels and 4 096 blocks a band: per band its own statistics, error bound (all-integer float values, TryRaiseMaxZError), kind
+ * (8 x 8 or 16 x 16 blocks, one sweep, constant, empty) and checksum; the mask's run-length stream once a tile, in band 0 -- the bands
+ * behind it carry the header's count of valid pixels and an empty mask section.  With nMasks == 0 the planes run through the masked
+ * family's kernels under a mask of all ones, as all-valid tiles inside a masked batch do; the fast one-launch tile encoder of
+ * lerc_amd_encode_tiles_device is not involved.  They also take 8-bit stacks (int8 / uint8, maxZErr < 1: lossless) with nMasks 0 or
+ * 1, through the masked 8-bit batch's kernels over planes (nMasks == 0: under all ones): per band its own histograms, code book and
+ * mode -- Huffman, delta Huffman or 8 x 8 blocks --, the Huffman stream written from whatever byte the band begins at; bands without
+ * a valid pixel stay inside.
+ * Handed back and encoded one by one inside the call, a whole stack per lerc_amd_encode_device call, same bytes and status
+ * (lerc_amd_last_note names tile, band and reason): an 8-bit tile with a band of a kind the 8-bit batch hands back (constant, one
+ * sweep, winning 16 x 16 blocks -- the tile goes back whole), 8-bit stacks at maxZErr >= 1, nMasks == nBands (masks per band need the masks-differ comparison and a second mask section), a tile with a NaN at a valid
+ * pixel in any band (the mask then changes across the bands), maxZErr 777 or 0 on float values, oversized tiles, a blob that does not
+ * fit its slot. */
+LERC_AMD_API lerc_status lerc_amd_encode_tiles_device_bands(lerc_amd_context* ctx, const void* dTiles, unsigned int dataType, int nCols, int nRows,
+    int nBands, int nTiles, int nMasks, const unsigned char* dValidBytes, double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity,
+    unsigned long long slotBytes, unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed);
+/* The way back: pixels and valid bytes exactly as lerc_amd_decode_device(blob t, nMasks, ..., nBands, ...) writes them; dValidBytes is
+ * written once a tile, from band 0 (nMasks == 1).  A thread per tile walks the chain of band blobs (band b + 1 begins where band b's
+ * header says it ends; every header is checked against nBands, shape and type; the sizes add up to sizes[t]); the planes are then
+ * parsed and decoded side by side.  A band behind band 0 whose count of valid pixels lies between none and all takes band 0's mask
+ * (Lerc2's "mask stays in force").  Decoded by the single-blob decoder inside the call, a whole stack at a time, with its exact
+ * result or status: an 8-bit tile with a constant, one-sweep or 16 x 16 band, nMasks == nBands, codec < 6, a band behind band 0 with a mask section of its own or a count of valid
+ * pixels that is not band 0's, nMasks == 0 with an invalid pixel, anything damaged or uncertain.  A tile whose blob fails is left
+ * zeroed, all bands and mask; the other tiles are decoded all the same, and the call returns the first such status.
+ * lerc_amd_tile_batch_counters counts tiles, not bands. */
+LERC_AMD_API lerc_status lerc_amd_decode_tiles_device_bands(lerc_amd_context* ctx, const unsigned char* dArena, const unsigned long long* offsets,
+    const unsigned int* sizes, int nTiles, int nCols, int nRows, int nBands, unsigned int dataType, void* dTiles, int nMasks,
+    unsigned char* dValidBytes);
 /* Diagnostics of the tile batch calls (masked or not): out[0] tiles whose blob the batch's own launches made, out[1] tiles encoded one by
  * one behind the batch, out[2] / out[3] the same for decodes. */
 LERC_AMD_API void lerc_amd_tile_batch_counters(lerc_amd_context* ctx, unsigned long long out[4]);

@@ -71,6 +71,15 @@ def load_library():
                                                         ct.c_void_p, ct.c_ulonglong, ct.c_ulonglong, ct.c_void_p, ct.c_void_p, ct.c_void_p]
     lib.lerc_amd_decode_tiles_device_masked.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_uint,
                                                         ct.c_void_p, ct.c_void_p]
+    # (only a library named by LERC_AMD_LIBRARY may lack the band stack calls -- tools time against one built before them; the
+    # package's own library without them fails here, at load)
+    have_bands = not os.environ.get("LERC_AMD_LIBRARY") or hasattr(lib, "lerc_amd_encode_tiles_device_bands")
+    if have_bands:
+        lib.lerc_amd_encode_tiles_device_bands.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int,
+                                                           ct.c_void_p, ct.c_double, ct.c_void_p, ct.c_ulonglong, ct.c_ulonglong, ct.c_void_p,
+                                                           ct.c_void_p, ct.c_void_p]
+        lib.lerc_amd_decode_tiles_device_bands.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_int,
+                                                           ct.c_uint, ct.c_void_p, ct.c_int, ct.c_void_p]
     lib.lerc_amd_tile_batch_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_ulonglong)]
     lib.lerc_amd_tile_batch_counters.restype = None
     lib.lerc_amd_encode_device_async.argtypes = [ct.c_void_p] + enc + [ct.c_void_p, ct.c_uint, u32p]
@@ -80,7 +89,8 @@ def load_library():
     for n in ("lerc_computeCompressedSize", "lerc_encode", "lerc_getBlobInfo", "lerc_getDataRanges", "lerc_decode",
               "lerc_amd_encode_device", "lerc_amd_decode_device", "lerc_amd_encode_tiles_device", "lerc_amd_decode_tiles_device",
               "lerc_amd_encode_device_async", "lerc_amd_decode_device_async", "lerc_amd_finish", "lerc_amd_encode_tiles_device_slots",
-              "lerc_amd_decode_tiles_device_slots", "lerc_amd_encode_tiles_device_masked", "lerc_amd_decode_tiles_device_masked"):
+              "lerc_amd_decode_tiles_device_slots", "lerc_amd_encode_tiles_device_masked", "lerc_amd_decode_tiles_device_masked") + \
+            (("lerc_amd_encode_tiles_device_bands", "lerc_amd_decode_tiles_device_bands") if have_bands else ()):
         getattr(lib, n).restype = ct.c_uint
     _LIB = lib
     return lib
@@ -253,6 +263,23 @@ class DeviceCodec:
         return self.lib.lerc_amd_decode_tiles_device_masked(self.h, d_arena, offsets.ctypes.data, sizes.ctypes.data, n_tiles, n_cols, n_rows,
                                                             dt_code, d_tiles, d_valid or None)
 
+    def encode_tiles_bands(self, d_tiles, dt_code, n_cols, n_rows, n_bands, n_tiles, n_masks, d_valid, max_z_err, d_arena, arena_cap, slot_bytes=0):
+        """band stacks, raw device addresses: d_tiles [nTiles][nBands][nRows][nCols], d_valid [nTiles][nMasks][nRows][nCols] (n_masks 0: None)
+        -> (status, offsets uint64[nTiles], sizes uint32[nTiles], arena bytes used), one blob a tile"""
+        offsets = np.zeros(n_tiles, np.uint64)
+        sizes = np.zeros(n_tiles, np.uint32)
+        used = ct.c_ulonglong(0)
+        rc = self.lib.lerc_amd_encode_tiles_device_bands(self.h, d_tiles, dt_code, n_cols, n_rows, n_bands, n_tiles, n_masks, d_valid or None,
+                                                         float(max_z_err), d_arena, int(arena_cap), int(slot_bytes), offsets.ctypes.data,
+                                                         sizes.ctypes.data, ct.byref(used))
+        return rc, offsets, sizes, int(used.value)
+
+    def decode_tiles_bands(self, d_arena, offsets, sizes, n_tiles, n_cols, n_rows, n_bands, dt_code, d_tiles, n_masks, d_valid):
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        sizes = np.ascontiguousarray(sizes, np.uint32)
+        return self.lib.lerc_amd_decode_tiles_device_bands(self.h, d_arena, offsets.ctypes.data, sizes.ctypes.data, n_tiles, n_cols, n_rows,
+                                                           n_bands, dt_code, d_tiles, n_masks, d_valid or None)
+
     def last_note(self):
         """why the last call that left the streaming kernels (or went down a streaming tier) did so; "" if none did"""
         self.lib.lerc_amd_last_note.argtypes = [ct.c_void_p]
@@ -385,3 +412,36 @@ def decode_tiles_device_masked(codec, arena, offsets, sizes, out, valid_out):
     n_tiles, n_rows, n_cols = (int(v) for v in out.shape)
     return codec.decode_tiles_masked(arena.data_ptr(), offsets, sizes, n_tiles, n_cols, n_rows, _torch_dt_code(out), out.data_ptr(),
                                      valid_out.data_ptr() if valid_out is not None else 0)
+
+
+def _band_masks(valid, n_tiles, n_bands, n_rows, n_cols):
+    """-> (nMasks, device address) of a valid tensor [nTiles, nRows, nCols], [nTiles, 1 | nBands, nRows, nCols] or None"""
+    if valid is None:
+        return 0, 0
+    assert valid.element_size() == 1 and valid.is_contiguous()
+    shape = tuple(int(v) for v in valid.shape)
+    if shape in ((n_tiles, n_rows, n_cols), (n_tiles, 1, n_rows, n_cols)):
+        return 1, valid.data_ptr()
+    assert shape == (n_tiles, n_bands, n_rows, n_cols), "valid: a mask a tile or a mask a band"
+    return n_bands, valid.data_ptr()
+
+
+def encode_tiles_device_bands(codec, tiles, valid, max_z_err, arena, slot_bytes=0):
+    """tiles: CUDA(HIP) tensor [nTiles, nBands, nRows, nCols]; valid: uint8 CUDA tensor [nTiles, nRows, nCols] (one mask a tile),
+    [nTiles, nBands, nRows, nCols] (a mask a band) or None; arena: uint8 CUDA tensor.  One blob per tile, each exactly what encode() makes
+    of that band stack.  -> (status, offsets uint64[nTiles], sizes uint32[nTiles], arena bytes used)"""
+    n_tiles, n_bands, n_rows, n_cols = (int(v) for v in tiles.shape)
+    assert tiles.is_contiguous()
+    n_masks, d_valid = _band_masks(valid, n_tiles, n_bands, n_rows, n_cols)
+    return codec.encode_tiles_bands(tiles.data_ptr(), _torch_dt_code(tiles), n_cols, n_rows, n_bands, n_tiles, n_masks, d_valid, max_z_err,
+                                    arena.data_ptr(), arena.numel(), slot_bytes)
+
+
+def decode_tiles_device_bands(codec, arena, offsets, sizes, out, valid_out):
+    """out: CUDA(HIP) tensor [nTiles, nBands, nRows, nCols]; valid_out as `valid` above, written 1 / 0 for every tile, or None (a blob
+    with an invalid pixel is then refused).  A tile whose blob fails is left zeroed, all bands and mask."""
+    n_tiles, n_bands, n_rows, n_cols = (int(v) for v in out.shape)
+    assert out.is_contiguous()
+    n_masks, d_valid = _band_masks(valid_out, n_tiles, n_bands, n_rows, n_cols)
+    return codec.decode_tiles_bands(arena.data_ptr(), offsets, sizes, n_tiles, n_cols, n_rows, n_bands, _torch_dt_code(out), out.data_ptr(),
+                                    n_masks, d_valid)

@@ -701,6 +701,38 @@ lerc_status lerc_amd_decode_tiles_device_masked(lerc_amd_context* h, const unsig
   return decodeTilesDeviceMasked(h->ctx, rq);
 }
 
+lerc_status lerc_amd_encode_tiles_device_bands(lerc_amd_context* h, const void* dTiles, unsigned int dataType, int nCols, int nRows, int nBands,
+  int nTiles, int nMasks, const unsigned char* dValidBytes, double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity,
+  unsigned long long slotBytes, unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed)
+{
+  if (!h || !dTiles || !dArena || !offsets || !sizes || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || nBands <= 0 || nTiles <= 0 || maxZErr < 0
+    || (slotBytes & 15u) != 0 || (nMasks != 0 && nMasks != 1 && nMasks != nBands) || (nMasks == 0) != (dValidBytes == nullptr))
+    return kWrongParam;
+  if (!dimsOk(1, nCols, nRows, (size_t)dtSize((int)dataType))) return kDimsTooLarge;
+  TilesEncodeRequest rq;
+  rq.dData = dTiles; rq.dt = (int)dataType; rq.nCols = nCols; rq.nRows = nRows; rq.nTiles = nTiles; rq.maxZErr = maxZErr;
+  rq.dArena = dArena; rq.arenaCapacity = arenaCapacity; rq.hOffsets = offsets; rq.hSizes = sizes; rq.slotBytes = slotBytes;
+  rq.dValidBytes = dValidBytes; rq.nBands = nBands; rq.nMasks = nMasks;
+  u64 used = 0;
+  const u32 rc = encodeTilesDeviceBands(h->ctx, rq, used);
+  if (rc == kOk && slotBytes) for (int t = 0; t < nTiles; t++) offsets[t] = (u64)t * slotBytes;
+  if (arenaUsed) *arenaUsed = used;
+  return rc;
+}
+
+lerc_status lerc_amd_decode_tiles_device_bands(lerc_amd_context* h, const unsigned char* dArena, const unsigned long long* offsets,
+  const unsigned int* sizes, int nTiles, int nCols, int nRows, int nBands, unsigned int dataType, void* dTiles, int nMasks, unsigned char* dValidBytes)
+{
+  if (!h || !dArena || !offsets || !sizes || !dTiles || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || nBands <= 0 || nTiles <= 0
+    || (nMasks != 0 && nMasks != 1 && nMasks != nBands) || (nMasks == 0) != (dValidBytes == nullptr))
+    return kWrongParam;
+  if (!dimsOk(1, nCols, nRows, (size_t)dtSize((int)dataType))) return kDimsTooLarge;
+  TilesDecodeRequest rq;
+  rq.dArena = dArena; rq.hOffsets = offsets; rq.hSizes = sizes; rq.dt = (int)dataType; rq.nCols = nCols; rq.nRows = nRows; rq.nTiles = nTiles;
+  rq.dOut = dTiles; rq.dValidBytes = dValidBytes; rq.nBands = nBands; rq.nMasks = nMasks;
+  return decodeTilesDeviceBands(h->ctx, rq);
+}
+
 void lerc_amd_tile_batch_counters(lerc_amd_context* h, unsigned long long out[4])
 {
   for (int i = 0; i < 4; i++) out[i] = h ? h->ctx.tileBatchCount[i] : 0;

@@ -226,6 +226,9 @@ struct TilesEncodeRequest
   u32* hSizes = nullptr;              // host [nTiles]
   u64 slotBytes = 0;                  // != 0: tile t's blob goes to dArena + t * slotBytes (a multiple of 16), nothing is moved afterwards
   const u8* dValidBytes = nullptr;    // device [nTiles][nRows][nCols], 0 = invalid: a mask per tile (encodeTilesDeviceMasked); nullptr: every pixel valid
+  // band stacks (encodeTilesDeviceBands): dData [nTiles][nBands][nRows][nCols], dValidBytes [nTiles][nMasks][nRows][nCols]; nMasks < 0: the
+  // single-band calls' meaning (a mask per tile where the call takes masks)
+  int nBands = 1, nMasks = -1;
 };
 struct TilesDecodeRequest
 {
@@ -235,6 +238,7 @@ struct TilesDecodeRequest
   int dt = 0, nCols = 0, nRows = 0, nTiles = 0;
   void* dOut = nullptr;               // device: [nTiles][nRows][nCols]
   u8* dValidBytes = nullptr;          // device [nTiles][nRows][nCols], written 1 / 0 for every tile (decodeTilesDeviceMasked); nullptr: blobs with a mask are refused
+  int nBands = 1, nMasks = -1;        // band stacks (decodeTilesDeviceBands), as in TilesEncodeRequest
 };
 
 struct DecodeRequest
@@ -293,6 +297,9 @@ u32 decodeTilesDevice(Context& ctx, const TilesDecodeRequest& rq);
 // the same with a validity mask per tile (codec_tiles_batch.cpp, tile_mask_batch.hip); without mask pointers they ARE the two calls above
 u32 encodeTilesDeviceMasked(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed);
 u32 decodeTilesDeviceMasked(Context& ctx, const TilesDecodeRequest& rq);
+// tiles that are band stacks, one blob a tile (codec_tiles_batch.cpp); with one band they ARE the calls above
+u32 encodeTilesDeviceBands(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed);
+u32 decodeTilesDeviceBands(Context& ctx, const TilesDecodeRequest& rq);
 
 // 8-bit tiles, every pixel valid, lossless (codec_tiles_batch.cpp, tile_byte_batch.hip): encodeTilesDevice / decodeTilesDevice hand such requests on
 bool tilesBytesEncodeEligible(const TilesEncodeRequest& rq);

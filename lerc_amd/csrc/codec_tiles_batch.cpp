@@ -2,9 +2,10 @@
 // the masked batch (lerc_amd_encode_tiles_device_masked / lerc_amd_decode_tiles_device_masked; kernels in tile_mask_batch.hip) and the
 // 8-bit batch (DT_Char / DT_Byte, lossless, through the tile batch calls; kernels in tile_byte_batch.hip) -- every pixel valid, or, through
 // the masked calls, with a mask per tile.  One driver, tbEncode / tbDecode, runs them all: the sub-batches, the workspace, the records'
-// way home, the arena's bookkeeping.  Tiles the kernels hand back (TileBatchRec::flags) are done one by one behind their sub-batch
+// way home, the arena's bookkeeping -- per plane (tile * nBands + band) where a tile is a band stack (MaskedBandsBatch), folded into
+// tiles in one walk over the records.  Tiles the kernels hand back (TileBatchRec::flags) are done one by one behind their sub-batch
 // by encodeDevice / decodeDevice -- byte for byte what those calls make, and their exact status.  A family (MaskedBatch, BytesBatch,
-// BytesMaskedBatch) supplies what differs: its workspace, its launches, whether a tile by itself carries a mask, its words for a reason.
+// BytesMaskedBatch, and over band stacks MaskedBandsBatch, BytesBandsBatch) supplies what differs: its workspace, its launches, whether a tile by itself carries a mask, its words for a reason.
 #include "codec.h"
 #include "tile_mask_batch.h"
 #include "tile_byte_batch.h"
@@ -29,6 +30,9 @@ static G tileGeom(int dt, int nRows, int nCols)
   return g;
 }
 
+// how many bands and masks a tile has: every family is constructed with it, the single-band ones leave it unread
+struct TbStack { int nBands, nMasks; };
+
 // ================================================================================================
 // the masked family
 // ================================================================================================
@@ -51,7 +55,7 @@ struct MaskedBatch
   TmbEncodeBuffers eb;
   TmbDecodeBuffers db;
 
-  MaskedBatch(int dt, int nRows, int nCols) : g(tileGeom<TmbGeom>(dt, nRows, nCols))
+  MaskedBatch(int dt, int nRows, int nCols, TbStack = { 1, 1 }) : g(tileGeom<TmbGeom>(dt, nRows, nCols))
   {
     const u32 nBytes = (u32)((g.tileElems + 7) >> 3);
     g.bitStride = (nBytes + 16u + 15u) & ~15u;
@@ -60,6 +64,7 @@ struct MaskedBatch
   }
 
   size_t encodeBytesPerTile() const { return sizeof(TmbTile) + g.bitStride + g.rleStride + ((size_t)g.posStride + g.pos16Stride) * 4; }
+  size_t encodeBytesPerBatch() const { return 0; }    // (workspace a sub-batch needs once, whatever its tile count)
   size_t decodeBytesPerTile() const { return sizeof(TmbTile) + g.bitStride + (size_t)g.posStride * 4 + 16; }
 
   // the workspace of n tiles -> their records, nullptr: no room
@@ -79,12 +84,11 @@ struct MaskedBatch
     db.blockOff = ctx.allocT<u32>(n * g.posStride);
     return (db.bits && db.blockOff) ? db.tiles : nullptr;
   }
-  void launchEncode(u32 n, double maxZErr, const void* dTiles, const u8* dValid, u8* dArena, u64 arenaBase, u64 arenaCapacity, u64 slotBytes, u64 firstTile,
-                    hipStream_t st)
+  // what the encode kernels are told beside the geometry: the band parameters, the call's error bound, the TryRaiseMaxZError candidates
+  BandParams encodeParams(double maxZErr, u32& cand) const
   {
-    g.nTiles = n;
     const bool isFlt = g.dt >= DT_Float;
-    u32 cand = 0;    // TryRaiseMaxZError candidates whose error bound beats maxZErr
+    cand = 0;
     if (isFlt)
     {
       static const double errCand[9] = { 1, 0.5, 0.1, 0.05, 0.01, 0.005, 0.001, 0.0005, 0.0001 };
@@ -96,6 +100,14 @@ struct MaskedBatch
     bp.scale = 1 / (2 * bp.maxZErr);
     bp.invScale = 2 * bp.maxZErr;
     bp.intLossless = (!isFlt && bp.maxZErr == 0.5) ? 1 : 0;
+    return bp;
+  }
+  void launchEncode(u32 n, double maxZErr, const void* dTiles, const u8* dValid, u8* dArena, u64 arenaBase, u64 arenaCapacity, u64 slotBytes, u64 firstTile,
+                    hipStream_t st)
+  {
+    g.nTiles = n;
+    u32 cand = 0;    // TryRaiseMaxZError candidates whose error bound beats maxZErr
+    const BandParams bp = encodeParams(maxZErr, cand);
     launchTmbEncode(g, bp, bp.maxZErr, cand, dTiles, dValid, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, eb, st);
   }
   void launchDecode(u32 n, const u8* dArena, const u64* dOff, const u32* dSize, void* dTiles, u8* dValid, hipStream_t st)
@@ -115,6 +127,62 @@ struct MaskedBatch
     if (flags & kTmbMaskStream) return "the mask's run-length stream is damaged";
     if (flags & (kTbBlocks | kTbSibling)) return "the block stream";
     return "unknown";
+  }
+};
+
+// ---- the masked family over band stacks: the same kernels over planes (tile_mask_batch.h), nMasks 0 or 1.  Without masks the planes
+// run under one mask of all ones, as all-valid tiles inside a masked batch do.
+struct MaskedBandsBatch : MaskedBatch
+{
+  static constexpr const char* kName = "band stack";
+  static constexpr const char* kLaunchError = "lerc_amd: a band stack tile batch kernel could not be launched";
+  static constexpr const char* kEncodeScope = "tiles_bands_encode";
+  static constexpr const char* kDecodeScope = "tiles_bands_decode";
+
+  int nBands, nMasks;
+  u8* ones = nullptr;         // encode without masks: tileElems bytes of 1
+  u64* planeOff = nullptr;    // decode: [planes], k_tmbd_chain's
+  u32* planeSize = nullptr;
+
+  MaskedBandsBatch(int dt, int nRows, int nCols, TbStack s) : MaskedBatch(dt, nRows, nCols), nBands(s.nBands), nMasks(s.nMasks) {}
+
+  size_t encodeBytesPerTile() const { return (size_t)nBands * MaskedBatch::encodeBytesPerTile(); }
+  size_t decodeBytesPerTile() const { return (size_t)nBands * (MaskedBatch::decodeBytesPerTile() + 16); }
+  size_t encodeBytesPerBatch() const { return nMasks ? 0 : (size_t)g.tileElems + 64; }    // (the all-ones mask, one for the sub-batch)
+
+  void* carveEncode(Context& ctx, size_t n)
+  {
+    void* rec = MaskedBatch::carveEncode(ctx, n * (size_t)nBands);
+    if (!nMasks) { ones = ctx.allocT<u8>((size_t)g.tileElems); if (!ones) return nullptr; }
+    return rec;
+  }
+  void* carveDecode(Context& ctx, size_t n)
+  {
+    void* rec = MaskedBatch::carveDecode(ctx, n * (size_t)nBands);
+    planeOff = ctx.allocT<u64>(n * (size_t)nBands);
+    planeSize = ctx.allocT<u32>(n * (size_t)nBands);
+    return (planeOff && planeSize) ? rec : nullptr;
+  }
+  void launchEncode(u32 n, double maxZErr, const void* dTiles, const u8* dValid, u8* dArena, u64 arenaBase, u64 arenaCapacity, u64 slotBytes, u64 firstTile,
+                    hipStream_t st)
+  {
+    g.nTiles = n * (u32)nBands;
+    u32 cand = 0;
+    const BandParams bp = encodeParams(maxZErr, cand);
+    if (!nMasks) hipMemsetAsync(ones, 1, (size_t)g.tileElems, st);
+    launchTmbEncodeBands(g, (u32)nBands, bp, bp.maxZErr, cand, dTiles, nMasks ? dValid : ones, nMasks ? g.tileElems : 0, dArena, arenaBase, arenaCapacity,
+                         slotBytes, firstTile, eb, st);
+  }
+  void launchDecode(u32 n, const u8* dArena, const u64* dOff, const u32* dSize, void* dTiles, u8* dValid, hipStream_t st)
+  {
+    g.nTiles = n * (u32)nBands;
+    launchTmbDecodeBands(g, (u32)nBands, dArena, dOff, dSize, planeOff, planeSize, dTiles, nMasks ? dValid : nullptr, db, st);
+  }
+
+  static const char* reason(u32 flags)
+  {
+    if (flags == kTbBand) return "another band of the tile";
+    return MaskedBatch::reason(flags & ~kTbBand);
   }
 };
 
@@ -148,9 +216,10 @@ struct BytesBatch
   TbbEncodeBuffers eb = {};
   TbbDecodeBuffers db = {};
 
-  BytesBatch(int dt, int nRows, int nCols) : g(tileGeom<TbbGeom>(dt, nRows, nCols)) {}
+  BytesBatch(int dt, int nRows, int nCols, TbStack = { 1, 0 }) : g(tileGeom<TbbGeom>(dt, nRows, nCols)) {}
 
   size_t encodeBytesPerTile() const { return sizeof(TbbTile) + 512 * 4 + (size_t)g.posStride * 4 + 256 * 8 + kTbbTableCap; }
+  size_t encodeBytesPerBatch() const { return 0; }
   size_t decodeBytesPerTile() const { return sizeof(TbbTile) + (size_t)g.posStride * 4 + 256 * 4 + 256 + 16; }
 
   void* carveEncode(Context& ctx, size_t n)
@@ -213,7 +282,7 @@ struct BytesMaskedBatch : BytesBatch
 
   u32 bitStride, rleStride, pos16Stride;
 
-  BytesMaskedBatch(int dt, int nRows, int nCols) : BytesBatch(dt, nRows, nCols)
+  BytesMaskedBatch(int dt, int nRows, int nCols, TbStack = { 1, 1 }) : BytesBatch(dt, nRows, nCols)
   {
     const u32 nBytes = (u32)((g.tileElems + 7) >> 3);
     bitStride = (nBytes + 16u + 15u) & ~15u;
@@ -264,14 +333,80 @@ struct BytesMaskedBatch : BytesBatch
   }
 };
 
+// ---- the 8-bit family over band stacks: the masked form's kernels over planes (tile_byte_batch.h), nMasks 0 or 1.  Without masks
+// the planes run under one mask of all ones.  A band of a kind this family hands back takes its whole tile with it.
+struct BytesBandsBatch : BytesMaskedBatch
+{
+  static constexpr const char* kName = "8-bit band stack";
+  static constexpr const char* kLaunchError = "lerc_amd: an 8-bit band stack tile batch kernel could not be launched";
+  static constexpr const char* kEncodeScope = "tiles_bytes_bands_encode";
+  static constexpr const char* kDecodeScope = "tiles_bytes_bands_decode";
+
+  int nBands, nMasks;
+  u8* ones = nullptr;         // encode without masks: tileElems bytes of 1
+  u64* planeOff = nullptr;    // decode: [planes], k_tbbd_chain's
+  u32* planeSize = nullptr;
+
+  BytesBandsBatch(int dt, int nRows, int nCols, TbStack s) : BytesMaskedBatch(dt, nRows, nCols), nBands(s.nBands), nMasks(s.nMasks) {}
+
+  size_t encodeBytesPerTile() const { return (size_t)nBands * BytesMaskedBatch::encodeBytesPerTile(); }
+  size_t decodeBytesPerTile() const { return (size_t)nBands * (BytesMaskedBatch::decodeBytesPerTile() + 16); }
+  size_t encodeBytesPerBatch() const { return nMasks ? 0 : (size_t)g.tileElems + 64; }
+
+  void* carveEncode(Context& ctx, size_t n)
+  {
+    void* rec = BytesMaskedBatch::carveEncode(ctx, n * (size_t)nBands);
+    if (!nMasks) { ones = ctx.allocT<u8>((size_t)g.tileElems); if (!ones) return nullptr; }
+    return rec;
+  }
+  void* carveDecode(Context& ctx, size_t n)
+  {
+    void* rec = BytesMaskedBatch::carveDecode(ctx, n * (size_t)nBands);
+    planeOff = ctx.allocT<u64>(n * (size_t)nBands);
+    planeSize = ctx.allocT<u32>(n * (size_t)nBands);
+    return (planeOff && planeSize) ? rec : nullptr;
+  }
+  void launchEncode(u32 n, double, const void* dTiles, const u8* dValid, u8* dArena, u64 arenaBase, u64 arenaCapacity, u64 slotBytes, u64 firstTile,
+                    hipStream_t st)
+  {
+    g.nTiles = n * (u32)nBands;
+    BandParams bp = tbFillBandParams(g, 8);    // (lossless: the header says 0.5)
+    bp.allValid = 1;
+    bp.maxQ = maxValToQuantize(g.dt);
+    bp.maxZErr = 0.5; bp.scale = 1.0; bp.invScale = 1.0;
+    bp.intLossless = 1;
+    if (!nMasks) hipMemsetAsync(ones, 1, (size_t)g.tileElems, st);
+    eb.m.valid = nMasks ? const_cast<u8*>(dValid) : ones;    // (read only: k_tbb_stats)
+    launchTbbEncodeBands(g, (u32)nBands, bp, dTiles, nMasks ? g.tileElems : 0, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, eb, st);
+  }
+  void launchDecode(u32 n, const u8* dArena, const u64* dOff, const u32* dSize, void* dTiles, u8* dValid, hipStream_t st)
+  {
+    g.nTiles = n * (u32)nBands;
+    db.m.valid = nMasks ? dValid : nullptr;
+    launchTbbDecodeBands(g, (u32)nBands, dArena, dOff, dSize, planeOff, planeSize, dTiles, db, st);
+  }
+
+  static const char* reason(u32 flags)
+  {
+    if (flags == kTbBand) return "another band of the tile";
+    return BytesMaskedBatch::reason(flags & ~kTbBand);
+  }
+};
+
 // ================================================================================================
 // the driver
 // ================================================================================================
-// tiles per sub-batch: a tile is a blockIdx.y, at most 65535 of them per launch, and 256 MiB of workspace.  LERC_AMD_TEST_TILE_SUBBATCH=n
-// (tests only, read per call) makes it n, so that a handful of tiles takes several sub-batches.
-static int tbMaxBatch(int nTiles, size_t perTile)
+// tiles per sub-batch: a tile is a blockIdx.y, at most 65535 of them per launch, and 256 MiB of workspace (perBatch of it needed once).
+// LERC_AMD_TEST_TILE_SUBBATCH=n (tests only, read per call) makes it n, so that a handful of tiles takes several sub-batches.
+static const size_t kTbWorkspace = (size_t)256 << 20;
+static const size_t kTbMaxPlanes = 65535;
+
+// one tile's planes fit a launch's grid and the workspace; where not, the tiles go one by one
+static bool tbTileFits(size_t perTile, size_t perBatch, int nBands) { return (size_t)nBands <= kTbMaxPlanes && perTile + perBatch <= kTbWorkspace; }
+
+static int tbMaxBatch(int nTiles, size_t perTile, size_t perBatch, int nBands)
 {
-  size_t most = std::min<size_t>(65535, ((size_t)256 << 20) / perTile);
+  size_t most = std::min<size_t>(kTbMaxPlanes / (size_t)nBands, (kTbWorkspace - perBatch) / perTile);    // (a band stack's planes are blockIdx.y each)
   const char* e = getenv("LERC_AMD_TEST_TILE_SUBBATCH");
   const long knob = e ? strtol(e, nullptr, 0) : 0;
   if (knob >= 1) most = std::min<size_t>(most, (size_t)knob);
@@ -289,6 +424,29 @@ static void tbNote(Context& ctx, int tile, const char* what, u32 flags)
   ctx.lastNote = msg;
 }
 
+// a tile's planes folded: all their flags (0: the batch did every band), the band that says why -- the first with a reason of its own
+struct TbFold { u32 flags; int band; u32 bandFlags; };
+static TbFold tbFold(const u8* recs, size_t stride, int tile, int nBands)
+{
+  TbFold f = { 0u, -1, 0u };
+  for (int k = 0; k < nBands; k++)
+  {
+    const u32 fl = tbRec(recs, stride, tile * nBands + k).flags;
+    f.flags |= fl;
+    if (fl && (f.band < 0 || (f.bandFlags == kTbBand && fl != kTbBand))) { f.band = k; f.bandFlags = fl; }
+  }
+  return f;
+}
+
+template<class F>
+static void tbNoteBand(Context& ctx, int tile, const TbFold& f, const char* what)
+{
+  char msg[224];
+  snprintf(msg, sizeof(msg), "tile %d of the %s batch is %s by itself, all its bands: band %d, %s (reason bits 0x%x)", tile, F::kName, what, f.band,
+           F::reason(f.bandFlags), f.bandFlags);
+  ctx.lastNote = msg;
+}
+
 // batchOk == false: every tile one by one (a request the family's kernels do not take)
 template<class F>
 static u32 tbEncode(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed, bool batchOk)
@@ -296,16 +454,17 @@ static u32 tbEncode(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed, 
   arenaUsed = 0;
   const bool slotted = rq.slotBytes != 0;
   const int tb = dtSize(rq.dt);
-  const u64 tileElems = (u64)rq.nRows * (u64)rq.nCols;
+  const int nB = rq.nBands, nM = rq.nMasks >= 0 ? rq.nMasks : (F::kMasked ? 1 : 0);
+  const u64 tileElems = (u64)rq.nRows * (u64)rq.nCols, tileBytes = tileElems * (u64)tb * (u64)nB, maskBytes = tileElems * (u64)nM;
   u64 end = 0;    // arena bytes in use
 
   auto encodeOne = [&](int t) -> u32
   {
     end = slotted ? (u64)t * rq.slotBytes : (end + 15) & ~15ull;
     EncodeRequest one;
-    one.dData = (const u8*)rq.dData + (size_t)t * tileElems * tb;
-    one.dt = rq.dt; one.nDepth = 1; one.nCols = rq.nCols; one.nRows = rq.nRows; one.nBands = 1; one.nMasks = F::kMasked ? 1 : 0;
-    one.dValidBytes = F::kMasked ? rq.dValidBytes + (size_t)t * tileElems : nullptr;
+    one.dData = (const u8*)rq.dData + (size_t)t * tileBytes;
+    one.dt = rq.dt; one.nDepth = 1; one.nCols = rq.nCols; one.nRows = rq.nRows; one.nBands = nB; one.nMasks = nM;
+    one.dValidBytes = nM ? rq.dValidBytes + (size_t)t * maskBytes : nullptr;
     one.maxZErr = rq.maxZErr;
     one.dOut = rq.dArena + end;
     one.outCapacity = (u32)std::min<u64>(slotted ? rq.slotBytes : (rq.arenaCapacity > end ? rq.arenaCapacity - end : 0), 0xFFFFFFFFull);
@@ -319,24 +478,26 @@ static u32 tbEncode(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed, 
   };
 
   if (slotted && rq.arenaCapacity < (u64)rq.nTiles * rq.slotBytes) return kBufferTooSmall;
-  if (!batchOk)
+  auto oneByOne = [&]() -> u32
   {
     for (int t = 0; t < rq.nTiles; t++) { const u32 rc = encodeOne(t); if (rc != kOk) return rc; }
     arenaUsed = slotted ? (u64)rq.nTiles * rq.slotBytes : end;
     return kOk;
-  }
+  };
+  if (!batchOk) return oneByOne();
 
   hipStream_t st = ctx.activeStream();
-  F f(rq.dt, rq.nRows, rq.nCols);
-  const size_t perTile = f.encodeBytesPerTile();
-  const int maxBatch = tbMaxBatch(rq.nTiles, perTile);
+  F f(rq.dt, rq.nRows, rq.nCols, TbStack{ nB, nM });
+  const size_t perTile = f.encodeBytesPerTile(), perBatch = f.encodeBytesPerBatch();
+  if (!tbTileFits(perTile, perBatch, nB)) return oneByOne();
+  const int maxBatch = tbMaxBatch(rq.nTiles, perTile, perBatch, nB);
   std::vector<int> redo;
   for (int t0 = 0; t0 < rq.nTiles; t0 += maxBatch)
   {
     const int n = std::min(maxBatch, rq.nTiles - t0);
     ctx.reset();
-    if (!ctx.reserve((size_t)n * perTile + (1u << 16))) return kFailed;
-    const size_t recBytes = (size_t)n * F::kRecBytes;
+    if (!ctx.reserve((size_t)n * perTile + perBatch + (1u << 16))) return kFailed;
+    const size_t recBytes = (size_t)n * (size_t)nB * F::kRecBytes;
     void* rec = f.carveEncode(ctx, (size_t)n);
     u8* pin = (u8*)ctx.pinned(recBytes);
     if (!rec || !pin) return kFailed;
@@ -344,7 +505,7 @@ static u32 tbEncode(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed, 
     (void)hipGetLastError();
     {
       ProfScope ps(ctx, F::kEncodeScope);
-      f.launchEncode((u32)n, rq.maxZErr, (const u8*)rq.dData + (size_t)t0 * tileElems * tb, F::kMasked ? rq.dValidBytes + (size_t)t0 * tileElems : nullptr,
+      f.launchEncode((u32)n, rq.maxZErr, (const u8*)rq.dData + (size_t)t0 * tileBytes, nM ? rq.dValidBytes + (size_t)t0 * maskBytes : nullptr,
                      rq.dArena, end, rq.arenaCapacity, rq.slotBytes, (u64)t0, st);
     }
     if (hipGetLastError() != hipSuccess) { ctx.lastError = F::kLaunchError; return kFailed; }
@@ -354,21 +515,27 @@ static u32 tbEncode(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed, 
     redo.clear();
     for (int i = 0; i < n; i++)
     {
-      const TileBatchRec& r = tbRec(pin, F::kRecBytes, i);
-      if (r.flags)
+      // (a band stack: the tile begins where its first plane does, and is as long as its planes together)
+      const TbFold fold = tbFold(pin, F::kRecBytes, i, nB);
+      if (fold.flags)
       {
-        if (!slotted && (r.flags & kTbArenaFull)) return kBufferTooSmall;
-        if (redo.empty()) tbNote<F>(ctx, t0 + i, "encoded", r.flags);
+        if (!slotted && (fold.flags & kTbArenaFull)) return kBufferTooSmall;
+        if (redo.empty()) { if (nB > 1) tbNoteBand<F>(ctx, t0 + i, fold, "encoded"); else tbNote<F>(ctx, t0 + i, "encoded", fold.flags); }
         redo.push_back(t0 + i);    // (slotted: a tile that does not fit its slot says so when it is encoded by itself)
         continue;
       }
-      rq.hOffsets[t0 + i] = r.offset;
-      rq.hSizes[t0 + i] = r.blobSize;
+      const u64 offset = tbRec(pin, F::kRecBytes, i * nB).offset;
+      u32 blobSize = 0;
+      for (int k = 0; k < nB; k++) blobSize += tbRec(pin, F::kRecBytes, i * nB + k).blobSize;
+      rq.hOffsets[t0 + i] = offset;
+      rq.hSizes[t0 + i] = blobSize;
       // (the arena is in use up to the last byte of the batch's last blob: an arena of exactly that size is enough)
-      if (!slotted) end = std::max<u64>(end, r.offset + r.blobSize);
+      if (!slotted) end = std::max<u64>(end, offset + blobSize);
       ctx.pathCount[0]++; ctx.tileBatchCount[0]++;
     }
+    const std::string note = ctx.lastNote;
     for (int t : redo) { const u32 rc = encodeOne(t); if (rc != kOk) return rc; }    // (reuses the workspace: the batch is done with it)
+    if (nB > 1 && !redo.empty()) ctx.lastNote = note;    // (a band stack: the note that names tile and band outlives the single encoder's)
   }
   arenaUsed = slotted ? (u64)rq.nTiles * rq.slotBytes : end;
   return kOk;
@@ -378,7 +545,8 @@ template<class F>
 static u32 tbDecode(Context& ctx, const TilesDecodeRequest& rq, bool batchOk)
 {
   const int tb = dtSize(rq.dt);
-  const u64 tileElems = (u64)rq.nRows * (u64)rq.nCols;
+  const int nB = rq.nBands, nM = rq.nMasks >= 0 ? rq.nMasks : (F::kMasked ? 1 : 0);
+  const u64 tileElems = (u64)rq.nRows * (u64)rq.nCols, tileBytes = tileElems * (u64)tb * (u64)nB, maskBytes = tileElems * (u64)nM;
   hipStream_t st = ctx.activeStream();
   u32 firstError = kOk;
   // a tile by itself; one that fails is left zeroed, mask too, and the call goes on with the tiles behind it
@@ -386,29 +554,31 @@ static u32 tbDecode(Context& ctx, const TilesDecodeRequest& rq, bool batchOk)
   {
     DecodeRequest one;
     one.dBlob = rq.dArena + rq.hOffsets[t]; one.blobSize = rq.hSizes[t]; one.dt = rq.dt; one.nDepth = 1; one.nCols = rq.nCols;
-    one.nRows = rq.nRows; one.nBands = 1; one.nMasks = F::kMasked ? 1 : 0;
-    one.dValidBytes = F::kMasked ? rq.dValidBytes + (size_t)t * tileElems : nullptr;
-    one.dOut = (u8*)rq.dOut + (size_t)t * tileElems * tb;
+    one.nRows = rq.nRows; one.nBands = nB; one.nMasks = nM;
+    one.dValidBytes = nM ? rq.dValidBytes + (size_t)t * maskBytes : nullptr;
+    one.dOut = (u8*)rq.dOut + (size_t)t * tileBytes;
     const u32 rc = decodeDevice(ctx, one);
     ctx.tileBatchCount[3]++;
     if (rc != kOk)
     {
       hipStream_t s = ctx.activeStream();
-      hipMemsetAsync(one.dOut, 0, (size_t)tileElems * tb, s);
-      if (F::kMasked) hipMemsetAsync(one.dValidBytes, 0, (size_t)tileElems, s);
+      hipMemsetAsync(one.dOut, 0, (size_t)tileBytes, s);
+      if (nM) hipMemsetAsync(one.dValidBytes, 0, (size_t)maskBytes, s);
       hipStreamSynchronize(s);
       if (firstError == kOk) firstError = rc;
     }
   };
-  if (!batchOk)
+  auto oneByOne = [&]() -> u32
   {
     for (int t = 0; t < rq.nTiles; t++) decodeOne(t);
     return firstError;
-  }
+  };
+  if (!batchOk) return oneByOne();
 
-  F f(rq.dt, rq.nRows, rq.nCols);
+  F f(rq.dt, rq.nRows, rq.nCols, TbStack{ nB, nM });
   const size_t perTile = f.decodeBytesPerTile();
-  const int maxBatch = tbMaxBatch(rq.nTiles, perTile);
+  if (!tbTileFits(perTile, 0, nB)) return oneByOne();
+  const int maxBatch = tbMaxBatch(rq.nTiles, perTile, 0, nB);
   std::vector<int> redo;
   for (int t0 = 0; t0 < rq.nTiles; t0 += maxBatch)
   {
@@ -419,7 +589,7 @@ static u32 tbDecode(Context& ctx, const TilesDecodeRequest& rq, bool batchOk)
     u64* dOff = ctx.allocT<u64>((size_t)n + 1);
     u32* dSize = ctx.allocT<u32>((size_t)n + 1);
     // (pinned: the tables on their way up, then -- a region of its own -- the records' way back)
-    const size_t upBytes = ((size_t)n * 12 + 64 + 63) & ~(size_t)63, recBytes = (size_t)n * F::kRecBytes;
+    const size_t upBytes = ((size_t)n * 12 + 64 + 63) & ~(size_t)63, recBytes = (size_t)n * (size_t)nB * F::kRecBytes;
     u8* pinUp = (u8*)ctx.pinned(upBytes + recBytes);
     if (!rec || !dOff || !dSize || !pinUp) return kFailed;
     u8* pin = pinUp + upBytes;
@@ -431,7 +601,7 @@ static u32 tbDecode(Context& ctx, const TilesDecodeRequest& rq, bool batchOk)
     hipMemcpyAsync(dSize, hSize, (size_t)n * 4, hipMemcpyHostToDevice, st);
     {
       ProfScope ps(ctx, F::kDecodeScope);
-      f.launchDecode((u32)n, rq.dArena, dOff, dSize, (u8*)rq.dOut + (size_t)t0 * tileElems * tb, F::kMasked ? rq.dValidBytes + (size_t)t0 * tileElems : nullptr, st);
+      f.launchDecode((u32)n, rq.dArena, dOff, dSize, (u8*)rq.dOut + (size_t)t0 * tileBytes, nM ? rq.dValidBytes + (size_t)t0 * maskBytes : nullptr, st);
     }
     if (hipGetLastError() != hipSuccess) { ctx.lastError = F::kLaunchError; return kFailed; }
     hipMemcpyAsync(pin, rec, recBytes, hipMemcpyDeviceToHost, st);
@@ -440,12 +610,14 @@ static u32 tbDecode(Context& ctx, const TilesDecodeRequest& rq, bool batchOk)
     redo.clear();
     for (int i = 0; i < n; i++)
     {
-      const u32 flags = tbRec(pin, F::kRecBytes, i).flags;
-      if (!flags) { ctx.pathCount[2]++; ctx.tileBatchCount[2]++; continue; }
-      if (redo.empty()) tbNote<F>(ctx, t0 + i, "decoded", flags);
+      const TbFold fold = tbFold(pin, F::kRecBytes, i, nB);
+      if (!fold.flags) { ctx.pathCount[2]++; ctx.tileBatchCount[2]++; continue; }
+      if (redo.empty()) { if (nB > 1) tbNoteBand<F>(ctx, t0 + i, fold, "decoded"); else tbNote<F>(ctx, t0 + i, "decoded", fold.flags); }
       redo.push_back(t0 + i);
     }
+    const std::string note = ctx.lastNote;
     for (int t : redo) decodeOne(t);    // (reuses the workspace: the batch is done with it)
+    if (nB > 1 && !redo.empty()) ctx.lastNote = note;
   }
   return firstError;
 }
@@ -474,6 +646,44 @@ u32 decodeTilesDeviceMasked(Context& ctx, const TilesDecodeRequest& rq)
     return kWrongParam;
   if (tbbShapeOk(rq.dt, rq.nRows, rq.nCols)) return tbDecode<BytesMaskedBatch>(ctx, rq, true);
   return tbDecode<MaskedBatch>(ctx, rq, tmbShapeOk(rq.dt, rq.nRows, rq.nCols));
+}
+
+// ---- band stacks.  One band: the calls above.  The batch's own launches take the wide types (MaskedBandsBatch) and lossless 8-bit
+// stacks (BytesBandsBatch) with no mask or one mask a tile; a mask per band, 8-bit stacks from maxZErr 1 on, the error bounds and sizes
+// the masked family leaves alone go one by one, a whole stack per encodeDevice / decodeDevice call.
+u32 encodeTilesDeviceBands(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed)
+{
+  arenaUsed = 0;
+  if (!rq.dData || !rq.dArena || !rq.hOffsets || !rq.hSizes || rq.nTiles <= 0 || rq.nRows <= 0 || rq.nCols <= 0 || rq.dt < 0 || rq.dt > DT_Double
+    || rq.maxZErr < 0 || (rq.slotBytes & 15u) != 0 || rq.nBands <= 0 || (rq.nMasks != 0 && rq.nMasks != 1 && rq.nMasks != rq.nBands)
+    || (rq.nMasks == 0) != (rq.dValidBytes == nullptr))
+    return kWrongParam;
+  if (rq.nBands == 1)
+  {
+    TilesEncodeRequest one = rq;
+    one.nMasks = -1;
+    return encodeTilesDeviceMasked(ctx, one, arenaUsed);
+  }
+  if (rq.nMasks <= 1 && rq.maxZErr < 1 && tbbShapeOk(rq.dt, rq.nRows, rq.nCols)) return tbEncode<BytesBandsBatch>(ctx, rq, arenaUsed, true);
+  // (whatever is left of the 8-bit types -- maxZErr >= 1, a mask per band, oversized -- falls through with batchOk false: tmbShapeOk takes
+  // no 8-bit type, so MaskedBandsBatch is only the name under which every tile goes one by one; the same on the way back)
+  const bool batchOk = rq.nMasks <= 1 && tmbShapeOk(rq.dt, rq.nRows, rq.nCols) && rq.maxZErr != 777 && !(rq.dt >= DT_Float && rq.maxZErr == 0);
+  return tbEncode<MaskedBandsBatch>(ctx, rq, arenaUsed, batchOk);
+}
+
+u32 decodeTilesDeviceBands(Context& ctx, const TilesDecodeRequest& rq)
+{
+  if (!rq.dArena || !rq.hOffsets || !rq.hSizes || !rq.dOut || rq.nTiles <= 0 || rq.nRows <= 0 || rq.nCols <= 0 || rq.dt < 0 || rq.dt > DT_Double
+    || rq.nBands <= 0 || (rq.nMasks != 0 && rq.nMasks != 1 && rq.nMasks != rq.nBands) || (rq.nMasks == 0) != (rq.dValidBytes == nullptr))
+    return kWrongParam;
+  if (rq.nBands == 1)
+  {
+    TilesDecodeRequest one = rq;
+    one.nMasks = -1;
+    return decodeTilesDeviceMasked(ctx, one);
+  }
+  if (rq.nMasks <= 1 && tbbShapeOk(rq.dt, rq.nRows, rq.nCols)) return tbDecode<BytesBandsBatch>(ctx, rq, true);
+  return tbDecode<MaskedBandsBatch>(ctx, rq, rq.nMasks <= 1 && tmbShapeOk(rq.dt, rq.nRows, rq.nCols));
 }
 
 // (encodeTilesDevice / decodeTilesDevice have checked the arguments and the eligibility)

@@ -14,7 +14,9 @@ enum : u32
   kTbHeader = 1024u,      // not a header the batch takes
   kTbChecksum = 2048u,    // Fletcher32 differs
   kTbBlocks = 8192u,      // the walk met a block header that cannot be, or the blocks do not end where the blob does
-  kTbSibling = 16384u     // a block's decode failed (raised by the block kernel's waves)
+  kTbSibling = 16384u,    // a block's decode failed (raised by the block kernel's waves)
+  // band stacks
+  kTbBand = 131072u       // another band of the tile left the batch: the tile goes back whole
 };
 
 // the head of every tile's record (TmbTile, TbbTile): all the host driver reads of one

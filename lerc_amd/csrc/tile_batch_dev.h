@@ -126,6 +126,47 @@ __device__ __forceinline__ void tbArenaPlace(Rec* __restrict__ tiles, u32 nTiles
   }
 }
 
+// ---- band stacks: ONE workgroup folds the planes (tile * nBands + band) into tiles and places the tiles -- a tile's room is the sum
+// of its planes' blobs, packed at 16-byte aligned offsets from arenaBase on or in the tile's slot; a plane's offset is the running sum
+// inside its tile (any byte alignment).  A tile with a flagged plane, or one that does not fit, claims nothing: every plane of it is
+// flagged.  (s: 257 words of LDS)
+template<class Rec>
+__device__ __forceinline__ void tbPlaceBands(Rec* __restrict__ planes, u32 nTiles, u32 nBands, u64 arenaBase, u64 arenaCapacity, u64 slotBytes,
+                                             u64 firstTile, u64* s)
+{
+  const u32 per = (nTiles + 255u) / 256u, from = min(nTiles, threadIdx.x * per), to = min(nTiles, from + per);
+  auto flagAll = [&](u32 i, u32 own, u32 others)
+  {
+    for (u32 k = 0; k < nBands; k++) { TileBatchRec& r = planes[(u64)i * nBands + k].head; if (!r.flags) r.flags = k == 0 ? own : others; }
+  };
+  u64 sum = 0;
+  for (u32 i = from; i < to; i++)
+  {
+    u32 fl = 0;
+    u64 size = 0;
+    for (u32 k = 0; k < nBands; k++) { const TileBatchRec& r = planes[(u64)i * nBands + k].head; fl |= r.flags; size += r.blobSize; }
+    if (!fl && (size > 0xFFFFFFFFull || (slotBytes && size > slotBytes))) { flagAll(i, kTbCapacity, kTbBand); continue; }
+    if (fl) { flagAll(i, kTbBand, kTbBand); continue; }
+    if (!slotBytes) sum += (size + 15ull) & ~15ull;
+  }
+  s[threadIdx.x] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) { u64 run = 0; for (u32 i = 0; i < 256u; i++) { const u64 y = s[i]; s[i] = run; run += y; } s[256] = run; }
+  __syncthreads();
+  u64 run = arenaBase + s[threadIdx.x];
+  for (u32 i = from; i < to; i++)
+  {
+    if (planes[(u64)i * nBands].head.flags) continue;    // (folded above: flagged as a whole or not at all)
+    u64 size = 0;
+    for (u32 k = 0; k < nBands; k++) size += planes[(u64)i * nBands + k].head.blobSize;
+    const u64 base = slotBytes ? (firstTile + i) * slotBytes : run;
+    run += (size + 15ull) & ~15ull;
+    if (!slotBytes && base + size > arenaCapacity) { flagAll(i, kTbArenaFull, kTbArenaFull); continue; }
+    u64 at = base;
+    for (u32 k = 0; k < nBands; k++) { TileBatchRec& r = planes[(u64)i * nBands + k].head; r.offset = at; at += r.blobSize; }
+  }
+}
+
 // ---- the codec 6 header (Lerc2.cpp:724-786), 90 bytes
 static const u32 kHdr6 = 90;    // headerBytes(6), codec_common.cpp
 
@@ -165,6 +206,35 @@ __device__ __forceinline__ void tbWriteHeader6(u8* out, const TbHeader6& h)
   putBytes(out + 46, (u64)h.flagBytes, 4);
   const double dbl[5] = { h.maxZErr, h.zMin, h.zMax, 0.0, 0.0 };
   for (int i = 0; i < 5; i++) { u64 bits; memcpy(&bits, &dbl[i], 8); putBytes(out + 50 + 8 * i, bits, 8); }
+}
+
+// ---- band stacks, decode: a thread per tile walks the chain of band blobs -- band k + 1 begins where band k's header says band k
+// ends; every header names the stack's shape and type and the number of blobs behind it; the sizes add up to the tile's.  -> the
+// planes' places for the plane-parallel kernels; a chain that does not hold leaves sizes of 0, which the parse kernels refuse plane
+// by plane.  G: a family's geometry (TileGeom's nRows, nCols, dt)
+template<class G>
+__device__ __forceinline__ void tbBandChain(const G& g, u32 nTiles, u32 nBands, const u8* __restrict__ arena, const u64* __restrict__ offsets,
+                                            const u32* __restrict__ sizes, u64* __restrict__ planeOff, u32* __restrict__ planeSize)
+{
+  const u32 t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= nTiles) return;
+  const u64 base = offsets[t];
+  const u32 total = sizes[t];
+  u32 at = 0;
+  bool ok = true;
+  for (u32 k = 0; k < nBands && ok; k++)
+  {
+    if (total - at < kHdr6 + 4u) { ok = false; break; }
+    TbHeader6 h;
+    ok = tbReadHeader6(arena + base + at, h) && h.version == kCodecVersion && h.nRows == g.nRows && h.nCols == g.nCols && h.nDepth == 1 && h.dt == g.dt
+      && h.nBlobsMore == (int)(nBands - 1u - k) && h.blobSize >= (int)(kHdr6 + 4u) && (u32)h.blobSize <= total - at;
+    if (!ok) break;
+    planeOff[(u64)t * nBands + k] = base + at;
+    planeSize[(u64)t * nBands + k] = (u32)h.blobSize;
+    at += (u32)h.blobSize;
+  }
+  if (ok && at != total) ok = false;
+  if (!ok) for (u32 k = 0; k < nBands; k++) { planeOff[(u64)t * nBands + k] = base; planeSize[(u64)t * nBands + k] = 0u; }
 }
 
 // ---- a tile's mask, by the workgroup that owns the tile (masked batches of any pixel type)

@@ -85,4 +85,18 @@ struct TbbDecodeBuffers
 // masked: b.m.valid != nullptr
 void launchTbbDecode(const TbbGeom& g, const u8* dArena, const u64* dOffsets, const u32* dSizes, void* dTiles, const TbbDecodeBuffers& b, hipStream_t st);
 
+// ---- band stacks: a tile is nBands rasters [nBands][nRows][nCols] under ONE mask, its blob the bands' blobs byte-adjacent.  The
+// kernels' unit is the plane, tile * nBands + band: g.nTiles counts planes, and so do the records and every buffer above.  Always the
+// MASKED form: a call without masks hands all ones.
+// Encode: b.m.valid is never null, tile t's mask lies at b.m.valid + t * validStride (0: one mask for all).  Band 0 carries the mask
+// section, the bands behind it the 4-byte count 0; a tile with a plane that leaves the batch (a constant band, one sweep, 16 x 16
+// blocks, ...) leaves it whole (kTbBand on its other planes) and claims no room.  firstTile counts tiles.
+void launchTbbEncodeBands(const TbbGeom& g, u32 nBands, const BandParams& bp, const void* dTiles, u64 validStride, u8* dArena, u64 arenaBase,
+                          u64 arenaCapacity, u64 slotBytes, u64 firstTile, const TbbEncodeBuffers& b, hipStream_t st);
+// Decode: dOffsets / dSizes are per TILE; a thread per tile walks the chain of band headers into planeOff / planeSize (per plane; a
+// chain that does not hold leaves sizes of 0, which the parse refuses).  b.m.valid: [tiles][nRows][nCols], written from band 0, or
+// null (then a blob with an invalid pixel is refused).
+void launchTbbDecodeBands(const TbbGeom& g, u32 nBands, const u8* dArena, const u64* dOffsets, const u32* dSizes, u64* planeOff, u32* planeSize,
+                          void* dTiles, const TbbDecodeBuffers& b, hipStream_t st);
+
 }    // namespace lerc

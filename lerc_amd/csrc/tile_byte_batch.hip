@@ -36,6 +36,12 @@
 // valid count, k_tbb_blocks16 / k_tbb_decide16 settle the low-bit-rate retry, k_tbb_write puts the mask section in front and codes an
 // invalid pixel with length 0; k_tbbd_parse expands and checks the mask, k_tbbd_huff wants numValid code words, sends them to the
 // valid positions by rank and undoes the masked predictor row by row.  Tiles without a valid pixel stay inside.
+//
+// BANDS (a second template argument of k_tbb_stats, k_tbb_write and k_tbbd_parse, MASKED form only; launchTbbEncodeBands /
+// launchTbbDecodeBands): tiles that are band stacks, the unit a plane (tile * nBands + band).  A tile's planes share its mask; band 0
+// writes the mask section, the bands behind it the count 0; every header names the band blobs behind it.  k_tbb_place_bands gives a
+// tile the sum of its planes' sizes and each plane the running sum inside it -- a band begins at any byte --, and sends a tile with a
+// flagged plane back whole; k_tbbd_chain finds the planes of a tile's blob by the headers' sizes.
 #include <cstdio>
 #include <cstdlib>
 #include "kernels.h"
@@ -120,8 +126,10 @@ __device__ __forceinline__ u32 tbbmDelta(const u8* __restrict__ px, const TbbmMa
 // ================================================================================================
 // MASKED: in front of the histograms the masked batch's prelude (tile_batch_dev.h) -- byte mask -> bit mask, the count of valid pixels,
 // the mask's run-length stream by one lane -- and the histograms over valid pixels only
-template<class T, bool MASKED>
-__global__ void __launch_bounds__(256) k_tbb_stats(TbbGeom g, const u8* __restrict__ data, TbbEncodeBuffers b)
+// BANDS (MASKED only): t is a plane, tile * nBands + band (tile_byte_batch.h); the tile's mask lies at b.m.valid + tile * validStride,
+// and only band 0 makes the mask's run-length stream -- the bands behind it write the count 0
+template<class T, bool MASKED, bool BANDS = false>
+__global__ void __launch_bounds__(256) k_tbb_stats(TbbGeom g, const u8* __restrict__ data, TbbEncodeBuffers b, u32 nBands, u64 validStride)
 {
   __shared__ u32 s_h[512];
   __shared__ u32 s_mn[4], s_mx[4];
@@ -136,12 +144,13 @@ __global__ void __launch_bounds__(256) k_tbb_stats(TbbGeom g, const u8* __restri
     __shared__ u16 s_last[kTbbMaskWords];
     __shared__ u32 s_scan[256];
     __shared__ u64 s_red[4];
-    const u32 cnt = tbMaskToBits(b.m.valid + (u64)t * g.tileElems, nPix, s_bits, b.m.bits + (u64)t * b.m.bitStride, [](u32) {});
+    const u8* __restrict__ vb = BANDS ? b.m.valid + (u64)(t / nBands) * validStride : b.m.valid + (u64)t * g.tileElems;
+    const u32 cnt = tbMaskToBits(vb, nPix, s_bits, b.m.bits + (u64)t * b.m.bitStride, [](u32) {});
     numValid = (u32)blockSum((u64)cnt, s_red);    // (its barriers cover s_h and s_bits)
     if (threadIdx.x == 0)
     {
       TbbMaskRec mr = { numValid, 0u };
-      if (numValid > 0u && numValid < nPix)
+      if (numValid > 0u && numValid < nPix && (!BANDS || t % nBands == 0u))
       {
         mr.rleLen = tbMaskRle(s_bits, (nPix + 7u) >> 3, b.m.rle + (u64)t * b.m.rleStride, b.m.rleStride);
         if (!mr.rleLen) rleFlag = kTbbRle;
@@ -531,8 +540,10 @@ static const u32 kTbbStageWords = kTbbStep + 4u;    // 32 bits a code word at mo
 
 // MASKED: header and mask section as the masked batch writes them (tbWriteHeaderMask), for a tile without a valid pixel nothing else;
 // in the pixel stream an invalid pixel is a code of length 0 -- the step's scan is the compaction
-template<class T, bool MASKED>
-__global__ void __launch_bounds__(256) k_tbb_write(TbbGeom g, const u8* __restrict__ data, u8* __restrict__ arena, TbbEncodeBuffers b)
+// BANDS (MASKED only): the header says how many band blobs follow; the blob begins at any byte (every store here is a byte's, but
+// for the stream's words, which ask the address)
+template<class T, bool MASKED, bool BANDS = false>
+__global__ void __launch_bounds__(256) k_tbb_write(TbbGeom g, const u8* __restrict__ data, u8* __restrict__ arena, TbbEncodeBuffers b, u32 nBands)
 {
   __shared__ u8 s_hdr[kTbbDataBegin + 2];
   __shared__ u64 s_code[256];
@@ -550,8 +561,8 @@ __global__ void __launch_bounds__(256) k_tbb_write(TbbGeom g, const u8* __restri
     const TbbMaskRec mr = b.m.rec[t];
     const bool empty = ti.mode == kTbbModeEmpty;
     const int off = (g.dt == DT_Char) ? 128 : 0;
-    const TbHeader6 hd = { kCodecVersion, 0u, g.nRows, g.nCols, 1, (int)mr.numValid, 8, (int)ti.head.blobSize, g.dt, 0, 0u,
-                           0.5, empty ? 0.0 : (double)((int)ti.symMin - off), empty ? 0.0 : (double)((int)ti.symMax - off) };
+    const TbHeader6 hd = { kCodecVersion, 0u, g.nRows, g.nCols, 1, (int)mr.numValid, 8, (int)ti.head.blobSize, g.dt,
+                           BANDS ? (int)(nBands - 1u - t % nBands) : 0, 0u, 0.5, empty ? 0.0 : (double)((int)ti.symMin - off), empty ? 0.0 : (double)((int)ti.symMax - off) };
     s_code[threadIdx.x] = b.codes[(u64)t * 256u + threadIdx.x];
     tbWriteHeaderMask(blob, hd, b.m.rle + (u64)t * b.m.rleStride, mr.rleLen, s_hdr);    // (its barrier covers s_code)
     if (empty) return;
@@ -679,7 +690,7 @@ static void tbbEncodeT(const TbbGeom& g, const BandParams& bp, const void* dTile
 {
   const int nPos = g.nTV * g.nTH;
   const dim3 perTile(g.nTiles), blk(256), perBlock((nPos + 3) / 4, g.nTiles);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_stats<T, MASKED>), perTile, blk, 0, st, g, (const u8*)dTiles, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_stats<T, MASKED, false>), perTile, blk, 0, st, g, (const u8*)dTiles, b, 1u, (u64)0);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_blocks<T, false, MASKED>), perBlock, blk, 0, st, g, bp, (const T*)dTiles, (u8*)nullptr, b);
   hipLaunchKernelGGL(k_tbb_decide<MASKED>, perTile, blk, 0, st, g, slotBytes, firstTile, b);
   if constexpr (MASKED)
@@ -691,8 +702,41 @@ static void tbbEncodeT(const TbbGeom& g, const BandParams& bp, const void* dTile
   }
   if (!slotBytes) hipLaunchKernelGGL(k_tbb_arena, dim3(1), blk, 0, st, g.nTiles, arenaBase, arenaCapacity, b);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_blocks<T, true, MASKED>), perBlock, blk, 0, st, g, bp, (const T*)dTiles, dArena, b);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_write<T, MASKED>), perTile, blk, 0, st, g, (const u8*)dTiles, dArena, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_write<T, MASKED, false>), perTile, blk, 0, st, g, (const u8*)dTiles, dArena, b, 1u);
   hipLaunchKernelGGL(k_tbb_checksum, perTile, blk, 0, st, dArena, b);
+}
+
+// band stacks: ONE workgroup folds the planes into tiles and places the tiles (tbPlaceBands, tile_batch_dev.h)
+__global__ void __launch_bounds__(256) k_tbb_place_bands(u32 nTiles, u32 nBands, u64 arenaBase, u64 arenaCapacity, u64 slotBytes, u64 firstTile,
+                                                         TbbEncodeBuffers b)
+{
+  __shared__ u64 s[257];
+  tbPlaceBands(b.tiles, nTiles, nBands, arenaBase, arenaCapacity, slotBytes, firstTile, s);
+}
+
+// the masked launch set over the planes; the slot check and the placement are k_tbb_place_bands' for whole tiles
+template<class T>
+static void tbbEncodeBandsT(const TbbGeom& g, u32 nBands, const BandParams& bp, const void* dTiles, u64 validStride, u8* dArena, u64 arenaBase,
+                            u64 arenaCapacity, u64 slotBytes, u64 firstTile, const TbbEncodeBuffers& b, hipStream_t st)
+{
+  const int nPos = g.nTV * g.nTH, nPos16 = ((g.nRows + 15) / 16) * ((g.nCols + 15) / 16);
+  const dim3 perPlane(g.nTiles), blk(256), perBlock((nPos + 3) / 4, g.nTiles);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_stats<T, true, true>), perPlane, blk, 0, st, g, (const u8*)dTiles, b, nBands, validStride);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_blocks<T, false, true>), perBlock, blk, 0, st, g, bp, (const T*)dTiles, (u8*)nullptr, b);
+  hipLaunchKernelGGL(k_tbb_decide<true>, perPlane, blk, 0, st, g, (u64)0, (u64)0, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_blocks16<T>), dim3((nPos16 + 3) / 4, g.nTiles), blk, 0, st, g, bp, (const T*)dTiles, b);
+  hipLaunchKernelGGL(k_tbb_decide16, perPlane, blk, 0, st, g, b);
+  hipLaunchKernelGGL(k_tbb_place_bands, dim3(1), blk, 0, st, g.nTiles / nBands, nBands, arenaBase, arenaCapacity, slotBytes, firstTile, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_blocks<T, true, true>), perBlock, blk, 0, st, g, bp, (const T*)dTiles, dArena, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_write<T, true, true>), perPlane, blk, 0, st, g, (const u8*)dTiles, dArena, b, nBands);
+  hipLaunchKernelGGL(k_tbb_checksum, perPlane, blk, 0, st, dArena, b);
+}
+
+void launchTbbEncodeBands(const TbbGeom& g, u32 nBands, const BandParams& bp, const void* dTiles, u64 validStride, u8* dArena, u64 arenaBase,
+                          u64 arenaCapacity, u64 slotBytes, u64 firstTile, const TbbEncodeBuffers& b, hipStream_t st)
+{
+  if (g.dt == DT_Char) tbbEncodeBandsT<signed char>(g, nBands, bp, dTiles, validStride, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st);
+  else if (g.dt == DT_Byte) tbbEncodeBandsT<unsigned char>(g, nBands, bp, dTiles, validStride, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st);
 }
 
 void launchTbbEncode(const TbbGeom& g, const BandParams& bp, const void* dTiles, u8* dArena, u64 arenaBase, u64 arenaCapacity, u64 slotBytes,
@@ -778,9 +822,14 @@ __device__ bool tbbParseTable(const u8* __restrict__ p, u32 n, u8* __restrict__ 
 // MASKED: a mask section of any length in front of the ranges; the run-length stream expanded into LDS (tbMaskUnrle, as the masked
 // batch's parse does), the mask's own count held against the header's, the bit mask left in the workspace, the caller's valid
 // bytes written; tiling mode: the valid counts per block out of the bit mask
-template<class T, bool MASKED>
+// BANDS (MASKED only): t is a plane, tile * nBands + band, offsets / sizes are the planes' (k_tbbd_chain).  A band behind band 0
+// carries no mask section of its own: its count of valid pixels is band 0's, and between none and all it takes band 0's run-length
+// stream ("the mask stays in force").  A band with a mask section of its own, or a count that is not band 0's, is refused: the
+// single-blob decoder takes the whole stack.  The caller's valid bytes are written by band 0; without them (b.m.valid null) a blob
+// with an invalid pixel is refused.
+template<class T, bool MASKED, bool BANDS = false>
 __global__ void __launch_bounds__(256)
-k_tbbd_parse(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ offsets, const u32* __restrict__ sizes, TbbDecodeBuffers b)
+k_tbbd_parse(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ offsets, const u32* __restrict__ sizes, TbbDecodeBuffers b, u32 nBands)
 {
   __shared__ u64 s_red[4];
   __shared__ TbbTile s_ti;
@@ -790,6 +839,10 @@ k_tbbd_parse(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
   const u8* __restrict__ blob = arena + offsets[t];
   const u32 sizeGiven = sizes[t];
   const u32 nPix = (u32)g.tileElems;
+  const u32 band = BANDS ? t % nBands : 0u, plane0 = t - band;
+  // (band 0's blob: read by the bands behind it only where their own header, and so the chain, has held)
+  const u8* __restrict__ blob0 = BANDS ? arena + offsets[plane0] : blob;
+  const u32 size0 = BANDS ? sizes[plane0] : sizeGiven;
 
   if (threadIdx.x == 0)
   {
@@ -807,15 +860,20 @@ k_tbbd_parse(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
         ti.checksum = h.checksum;
         ti.head.blobSize = (u32)h.blobSize;
         if (h.version != kCodecVersion || h.nRows != g.nRows || h.nCols != g.nCols || h.nDepth != 1 || h.numValid < 0 || (u32)h.numValid > nPix
-          || h.microBlockSize != 8 || h.blobSize < (int)(kHdr6 + 4u) || (u32)h.blobSize > sizeGiven || h.dt != g.dt || h.nBlobsMore != 0
-          || (h.flagBytes & 0xFFu) != 0u)
+          || h.microBlockSize != 8 || h.blobSize < (int)(kHdr6 + 4u) || (u32)h.blobSize > sizeGiven || h.dt != g.dt
+          || h.nBlobsMore != (BANDS ? (int)(nBands - 1u - band) : 0) || (h.flagBytes & 0xFFu) != 0u)
           fl = kTbHeader;
+        if (BANDS && !fl)
+        {
+          if (!b.m.valid && (u32)h.numValid != nPix) fl = kTbHeader;
+          if (band > 0u && (size0 < kHdr6 + 4u || (u32)getBytes(blob0 + 26, 4) != (u32)h.numValid)) fl = kTbHeader;
+        }
         if (!fl)
         {
           mr.numValid = (u32)h.numValid;
           mr.rleLen = (u32)getBytes(blob + kHdr6, 4);
           const bool noStream = mr.numValid == nPix || mr.numValid == 0u;
-          if (noStream ? mr.rleLen != 0u : (mr.rleLen < 2u || mr.rleLen > ti.head.blobSize)) fl = kTbHeader;
+          if ((noStream || band > 0u) ? mr.rleLen != 0u : (mr.rleLen < 2u || mr.rleLen > ti.head.blobSize)) fl = kTbHeader;
           else if (mr.numValid == 0u)
           {
             // no valid pixel: nothing may follow the mask section's length (Lerc2.cpp:235-241); range and error bound are not asked
@@ -876,7 +934,15 @@ k_tbbd_parse(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
     dataBegin += mr.rleLen;
     for (u32 i = threadIdx.x; i < nBytes + 16u; i += 256u) s_bits[i] = (allValid && i < nBytes) ? (u8)0xFF : (u8)0;
     __syncthreads();
-    if (!allValid && !empty && threadIdx.x == 0 && !tbMaskUnrle(blob + kHdr6 + 4u, mr.rleLen, s_bits, nBytes)) s_ti.head.flags = kTbbMaskStream;
+    if (!allValid && !empty && threadIdx.x == 0)
+    {
+      if (band > 0u)
+      {
+        const u32 nm0 = (u32)getBytes(blob0 + kHdr6, 4);
+        if (nm0 < 2u || (u64)kHdr6 + 4u + nm0 > (u64)size0 || !tbMaskUnrle(blob0 + kHdr6 + 4u, nm0, s_bits, nBytes)) s_ti.head.flags = kTbbMaskStream;
+      }
+      else if (!tbMaskUnrle(blob + kHdr6 + 4u, mr.rleLen, s_bits, nBytes)) s_ti.head.flags = kTbbMaskStream;
+    }
     __syncthreads();
     // (a mask that names another number of valid pixels than the header does is the single-blob decoder's business: it asks the mask)
     const u32 own = tbMaskCount(s_bits, nPix, s_red);
@@ -887,8 +953,11 @@ k_tbbd_parse(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
     }
     u8* __restrict__ bitsOut = b.m.bits + (u64)t * b.m.bitStride;
     for (u32 i = threadIdx.x; i < nBytes; i += 256u) bitsOut[i] = s_bits[i];
-    u8* __restrict__ vOut = b.m.valid + (u64)t * g.tileElems;
-    for (u32 k = threadIdx.x; k < nPix; k += 256u) vOut[k] = (u8)((s_bits[k >> 3] >> (7u - (k & 7u))) & 1u);
+    if (!BANDS || (band == 0u && b.m.valid))
+    {
+      u8* __restrict__ vOut = b.m.valid + (u64)(BANDS ? t / nBands : t) * g.tileElems;
+      for (u32 k = threadIdx.x; k < nPix; k += 256u) vOut[k] = (u8)((s_bits[k >> 3] >> (7u - (k & 7u))) & 1u);
+    }
     if (threadIdx.x == 0) b.m.rec[t] = mr;
     if (s_ti.mode == (u32)IEM_Tiling)
     {
@@ -1206,9 +1275,37 @@ template<class T, bool MASKED>
 static void tbbDecodeT(const TbbGeom& g, const u8* dArena, const u64* dOffsets, const u32* dSizes, void* dTiles, const TbbDecodeBuffers& b, hipStream_t st)
 {
   const int nPos = g.nTV * g.nTH;
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_parse<T, MASKED>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, dSizes, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_parse<T, MASKED, false>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, dSizes, b, 1u);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_blocks<T, MASKED>), dim3((nPos + 3) / 4, g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, (T*)dTiles, b);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_huff<T, MASKED>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, (u8*)dTiles, b);
+}
+
+// band stacks: a thread per tile walks the chain of band blobs (tbBandChain, tile_batch_dev.h)
+__global__ void __launch_bounds__(256)
+k_tbbd_chain(TbbGeom g, u32 nTiles, u32 nBands, const u8* __restrict__ arena, const u64* __restrict__ offsets, const u32* __restrict__ sizes,
+             u64* __restrict__ planeOff, u32* __restrict__ planeSize)
+{
+  tbBandChain(g, nTiles, nBands, arena, offsets, sizes, planeOff, planeSize);
+}
+
+template<class T>
+static void tbbDecodeBandsT(const TbbGeom& g, u32 nBands, const u8* dArena, const u64* dOffsets, const u32* dSizes, u64* planeOff, u32* planeSize,
+                            void* dTiles, const TbbDecodeBuffers& b, hipStream_t st)
+{
+  const int nPos = g.nTV * g.nTH;
+  const u32 nTiles = g.nTiles / nBands;
+  hipLaunchKernelGGL(k_tbbd_chain, dim3((nTiles + 255u) / 256u), dim3(256), 0, st, g, nTiles, nBands, dArena, dOffsets, dSizes, planeOff, planeSize);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_parse<T, true, true>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, (const u64*)planeOff, (const u32*)planeSize, b,
+                     nBands);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_blocks<T, true>), dim3((nPos + 3) / 4, g.nTiles), dim3(256), 0, st, g, dArena, (const u64*)planeOff, (T*)dTiles, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_huff<T, true>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, (const u64*)planeOff, (u8*)dTiles, b);
+}
+
+void launchTbbDecodeBands(const TbbGeom& g, u32 nBands, const u8* dArena, const u64* dOffsets, const u32* dSizes, u64* planeOff, u32* planeSize,
+                          void* dTiles, const TbbDecodeBuffers& b, hipStream_t st)
+{
+  if (g.dt == DT_Char) tbbDecodeBandsT<signed char>(g, nBands, dArena, dOffsets, dSizes, planeOff, planeSize, dTiles, b, st);
+  else if (g.dt == DT_Byte) tbbDecodeBandsT<unsigned char>(g, nBands, dArena, dOffsets, dSizes, planeOff, planeSize, dTiles, b, st);
 }
 
 void launchTbbDecode(const TbbGeom& g, const u8* dArena, const u64* dOffsets, const u32* dSizes, void* dTiles, const TbbDecodeBuffers& b, hipStream_t st)

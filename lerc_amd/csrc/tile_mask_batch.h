@@ -40,7 +40,7 @@ struct TmbTile    // one per tile, device; copied home after the batch
   u32 kind;               // kTmbKind...
   u32 retry;              // encode: the low-bit-rate rule asks for the sizes of 16 x 16 blocks (k_tmb_decide)
   u32 mbSize;             // encode: the header's microBlockSize -- 16 once the retry has won, even if one sweep then beats the blocks
-  u32 rsv;
+  u32 nBlobsMore;         // encode: the header's count of band blobs that follow (0 unless the tile is a band of a stack)
 };
 
 static_assert(sizeof(TmbTile) % 8 == 0, "records lie back to back");
@@ -79,5 +79,18 @@ struct TmbDecodeBuffers
 };
 void launchTmbDecode(const TmbGeom& g, const u8* dArena, const u64* dOffsets, const u32* dSizes, void* dTiles, u8* dValidBytes,
                      const TmbDecodeBuffers& b, hipStream_t st);
+
+// ---- band stacks: a tile is nBands rasters [nBands][nRows][nCols] under ONE mask, its blob the bands' blobs byte-adjacent.  The
+// kernels' unit is the plane, tile * nBands + band: g.nTiles counts planes, and so do the records and every buffer above.
+// Encode: dValidBytes is never null (the caller hands all ones for a call without masks), tile t's mask lies at dValidBytes + t *
+// validStride (0: one mask for all).  Band 0 carries the mask section, the bands behind it the 4-byte count 0; a tile with a plane
+// that leaves the batch leaves it whole (kTbBand on its other planes) and claims no room.  firstTile counts tiles.
+void launchTmbEncodeBands(const TmbGeom& g, u32 nBands, const BandParams& bp, double maxZErr, u32 cand, const void* dTiles, const u8* dValidBytes,
+                          u64 validStride, u8* dArena, u64 arenaBase, u64 arenaCapacity, u64 slotBytes, u64 firstTile, const TmbEncodeBuffers& b, hipStream_t st);
+// Decode: dOffsets / dSizes are per TILE; a thread per tile walks the chain of band headers into planeOff / planeSize (per plane; a
+// chain that does not hold leaves sizes of 0, which the parse refuses).  dValidBytes: [tiles][nRows][nCols], written from band 0, or
+// null (then a blob with an invalid pixel is refused).
+void launchTmbDecodeBands(const TmbGeom& g, u32 nBands, const u8* dArena, const u64* dOffsets, const u32* dSizes, u64* planeOff, u32* planeSize,
+                          void* dTiles, u8* dValidBytes, const TmbDecodeBuffers& b, hipStream_t st);
 
 }    // namespace lerc

@@ -48,9 +48,12 @@ template<> struct TmbAcc<double> { typedef double type; static __device__ __forc
 // ================================================================================================
 // encode
 // ================================================================================================
-template<class T>
+// BANDS: t is a plane, tile * nBands + band (tile_mask_batch.h); the tile's mask lies at valid + tile * validStride, and only band 0
+// makes the mask's run-length stream -- the bands behind it write the count 0, "the mask of the band in front stays in force"
+template<class T, bool BANDS = false>
 __global__ void __launch_bounds__(256)
-k_tmb_prelude(TmbGeom g, double maxZErr, u32 cand, const T* __restrict__ data, const u8* __restrict__ valid, TmbEncodeBuffers b)
+k_tmb_prelude(TmbGeom g, double maxZErr, u32 cand, const T* __restrict__ data, const u8* __restrict__ valid, TmbEncodeBuffers b, u32 nBands,
+              u64 validStride)
 {
   typedef typename TmbAcc<T>::type Acc;
   constexpr bool isFlt = DtOf<T>::v >= DT_Float;
@@ -61,7 +64,8 @@ k_tmb_prelude(TmbGeom g, double maxZErr, u32 cand, const T* __restrict__ data, c
   const u32 t = blockIdx.x;
   const u32 nPix = (u32)g.tileElems, nBytes = (nPix + 7u) >> 3;
   const T* __restrict__ px = data + (u64)t * g.tileElems;
-  const u8* __restrict__ vb = valid + (u64)t * g.tileElems;
+  const u32 band = BANDS ? t % nBands : 0u;
+  const u8* __restrict__ vb = BANDS ? valid + (u64)(t / nBands) * validStride : valid + (u64)t * g.tileElems;
   u8* __restrict__ bitsOut = b.bits + (u64)t * g.bitStride;
   const int facCand[9] = { 1, 2, 10, 20, 100, 200, 1000, 2000, 10000 };
 
@@ -152,7 +156,7 @@ k_tmb_prelude(TmbGeom g, double maxZErr, u32 cand, const T* __restrict__ data, c
 
   // ---- the mask's run-length stream (tbMaskRle)
   u32 rleLen = 0;
-  if (fl == 0 && numValid > 0 && numValid < nPix)
+  if (fl == 0 && numValid > 0 && numValid < nPix && band == 0)
   {
     rleLen = tbMaskRle(s_bits, nBytes, b.rle + (u64)t * g.rleStride, g.rleStride);
     if (!rleLen) fl |= kTmbRle;
@@ -162,6 +166,7 @@ k_tmb_prelude(TmbGeom g, double maxZErr, u32 cand, const T* __restrict__ data, c
   // header and mask section; where pixels differ: ranges and the "one sweep" byte
   ti.dataBegin = kHdr6 + 4u + rleLen + (ti.kind == kTmbKindBlocks8 ? 2u * (u32)sizeof(T) + 1u : 0u);
   ti.mbSize = 8u;
+  if (BANDS) ti.nBlobsMore = nBands - 1u - band;
   ti.head.blobSize = ti.dataBegin;    // (all there is of an empty or a constant tile; the others: k_tmb_decide2)
   b.tiles[t] = ti;
 }
@@ -173,7 +178,7 @@ template<class T>
 __device__ __forceinline__ void tmbWriteFront(const TmbGeom& g, u32 t, const TmbTile& ti, const T* __restrict__ px, u8* __restrict__ blob, const TmbEncodeBuffers& b,
                                               u8* s_hdr, u32* s_w)
 {
-  const TbHeader6 h = { kCodecVersion, 0u, g.nRows, g.nCols, 1, (int)ti.numValid, (int)ti.mbSize, (int)ti.head.blobSize, g.dt, 0,
+  const TbHeader6 h = { kCodecVersion, 0u, g.nRows, g.nCols, 1, (int)ti.numValid, (int)ti.mbSize, (int)ti.head.blobSize, g.dt, (int)ti.nBlobsMore,
                         ti.isInt ? 0x100u : 0u, ti.maxZErr, ti.zMin, ti.zMax };
   tbWriteHeaderMask(blob, h, b.rle + (u64)t * g.rleStride, ti.rleLen, s_hdr);
   if (ti.kind == kTmbKindEmpty || ti.kind == kTmbKindConst) return;    // (Lerc2.cpp:235-241, :255: nothing behind the mask)
@@ -295,13 +300,55 @@ __global__ void __launch_bounds__(256) k_tmb_checksum(u8* __restrict__ arena, Tm
   tbWriteChecksum(arena, b.tiles[blockIdx.x].head, s_red);
 }
 
+// band stacks: ONE workgroup folds the planes into tiles and places the tiles (tbPlaceBands, tile_batch_dev.h)
+__global__ void __launch_bounds__(256) k_tmb_place_bands(u32 nTiles, u32 nBands, u64 arenaBase, u64 arenaCapacity, u64 slotBytes, u64 firstTile,
+                                                         TmbEncodeBuffers b)
+{
+  __shared__ u64 s[257];
+  tbPlaceBands(b.tiles, nTiles, nBands, arenaBase, arenaCapacity, slotBytes, firstTile, s);
+}
+
+template<class T>
+static void tmbEncodeBandsT(const TmbGeom& g, u32 nBands, const BandParams& bp, double maxZErr, u32 cand, const void* dTiles, const u8* dValidBytes,
+                            u64 validStride, u8* dArena, u64 arenaBase, u64 arenaCapacity, u64 slotBytes, u64 firstTile, const TmbEncodeBuffers& b,
+                            hipStream_t st)
+{
+  // (the single-band launch set over the planes; the slot check and the placement are k_tmb_place_bands' for whole tiles)
+  const int nPos = g.nTV * g.nTH, nPos16 = ((g.nRows + 15) / 16) * ((g.nCols + 15) / 16);
+  const dim3 perPlane(g.nTiles), blk(256);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_prelude<T, true>), perPlane, blk, 0, st, g, maxZErr, cand, (const T*)dTiles, dValidBytes, b, nBands, validStride);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_blocks<T, 8, false>), dim3((nPos + 3) / 4, g.nTiles), blk, 0, st, g, bp, (const T*)dTiles, (u8*)nullptr, b);
+  hipLaunchKernelGGL(k_tmb_decide, perPlane, blk, 0, st, g, (u32)sizeof(T), b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_blocks<T, 16, false>), dim3((nPos16 + 3) / 4, g.nTiles), blk, 0, st, g, bp, (const T*)dTiles, (u8*)nullptr, b);
+  hipLaunchKernelGGL(k_tmb_decide2, perPlane, blk, 0, st, g, (u32)sizeof(T), (u64)0, (u64)0, b);
+  hipLaunchKernelGGL(k_tmb_place_bands, dim3(1), blk, 0, st, g.nTiles / nBands, nBands, arenaBase, arenaCapacity, slotBytes, firstTile, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_blocks<T, 8, true>), dim3((nPos + 3) / 4 + 1, g.nTiles), blk, 0, st, g, bp, (const T*)dTiles, dArena, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_blocks<T, 16, true>), dim3((nPos16 + 3) / 4, g.nTiles), blk, 0, st, g, bp, (const T*)dTiles, dArena, b);
+  hipLaunchKernelGGL(k_tmb_checksum, perPlane, blk, 0, st, dArena, b);
+}
+
+void launchTmbEncodeBands(const TmbGeom& g, u32 nBands, const BandParams& bp, double maxZErr, u32 cand, const void* dTiles, const u8* dValidBytes,
+                          u64 validStride, u8* dArena, u64 arenaBase, u64 arenaCapacity, u64 slotBytes, u64 firstTile, const TmbEncodeBuffers& b, hipStream_t st)
+{
+  switch (g.dt)
+  {
+    case DT_Short:  tmbEncodeBandsT<short>(g, nBands, bp, maxZErr, cand, dTiles, dValidBytes, validStride, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st); break;
+    case DT_UShort: tmbEncodeBandsT<unsigned short>(g, nBands, bp, maxZErr, cand, dTiles, dValidBytes, validStride, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st); break;
+    case DT_Int:    tmbEncodeBandsT<int>(g, nBands, bp, maxZErr, cand, dTiles, dValidBytes, validStride, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st); break;
+    case DT_UInt:   tmbEncodeBandsT<unsigned int>(g, nBands, bp, maxZErr, cand, dTiles, dValidBytes, validStride, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st); break;
+    case DT_Float:  tmbEncodeBandsT<float>(g, nBands, bp, maxZErr, cand, dTiles, dValidBytes, validStride, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st); break;
+    case DT_Double: tmbEncodeBandsT<double>(g, nBands, bp, maxZErr, cand, dTiles, dValidBytes, validStride, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, b, st); break;
+    default: break;
+  }
+}
+
 template<class T>
 static void tmbEncodeT(const TmbGeom& g, const BandParams& bp, double maxZErr, u32 cand, const void* dTiles, const u8* dValidBytes, u8* dArena,
                        u64 arenaBase, u64 arenaCapacity, u64 slotBytes, u64 firstTile, const TmbEncodeBuffers& b, hipStream_t st)
 {
   const int nPos = g.nTV * g.nTH, nPos16 = ((g.nRows + 15) / 16) * ((g.nCols + 15) / 16);
   const dim3 perTile(g.nTiles), blk(256);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_prelude<T>), perTile, blk, 0, st, g, maxZErr, cand, (const T*)dTiles, dValidBytes, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_prelude<T, false>), perTile, blk, 0, st, g, maxZErr, cand, (const T*)dTiles, dValidBytes, b, 1u, (u64)0);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_blocks<T, 8, false>), dim3((nPos + 3) / 4, g.nTiles), blk, 0, st, g, bp, (const T*)dTiles, (u8*)nullptr, b);
   hipLaunchKernelGGL(k_tmb_decide, perTile, blk, 0, st, g, (u32)sizeof(T), b);
   // (over the whole batch, whether a tile is marked or not: the host knows nothing yet, and does not wait to learn it)
@@ -341,10 +388,22 @@ template<class T> __device__ __forceinline__ bool tmbIsValueOf(double z)
   return z >= lo && z <= hi && z == floor(z);
 }
 
-template<class T>
+// band stacks: a thread per tile walks the chain of band blobs (tbBandChain, tile_batch_dev.h)
+__global__ void __launch_bounds__(256)
+k_tmbd_chain(TmbGeom g, u32 nTiles, u32 nBands, const u8* __restrict__ arena, const u64* __restrict__ offsets, const u32* __restrict__ sizes,
+             u64* __restrict__ planeOff, u32* __restrict__ planeSize)
+{
+  tbBandChain(g, nTiles, nBands, arena, offsets, sizes, planeOff, planeSize);
+}
+
+// BANDS: t is a plane, tile * nBands + band, offsets / sizes are the planes' (k_tmbd_chain).  A band behind band 0 carries no mask
+// section of its own: its count of valid pixels is band 0's, and between none and all it takes band 0's run-length stream ("the mask
+// stays in force").  A band with a mask section of its own, or a count that is not band 0's, is refused: the single-blob decoder
+// takes the whole stack.  The caller's valid bytes are written by band 0; without them a blob with an invalid pixel is refused.
+template<class T, bool BANDS = false>
 __global__ void __launch_bounds__(256)
 k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ offsets, const u32* __restrict__ sizes, T* __restrict__ outAll,
-             u8* __restrict__ validOut, TmbDecodeBuffers b)
+             u8* __restrict__ validOut, TmbDecodeBuffers b, u32 nBands)
 {
   constexpr u32 TB = (u32)sizeof(T);
   __shared__ __align__(16) u8 s_bits[kTmbMaxMaskBytes + 16];
@@ -357,6 +416,10 @@ k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
   const u8* __restrict__ blob = arena + offsets[t];
   const u32 sizeGiven = sizes[t];
   const u32 nPix = (u32)g.tileElems, nBytes = (nPix + 7u) >> 3;
+  const u32 band = BANDS ? t % nBands : 0u, plane0 = t - band;
+  // (band 0's blob: read by the bands behind it only where their own header, and so the chain, has held)
+  const u8* __restrict__ blob0 = BANDS ? arena + offsets[plane0] : blob;
+  const u32 size0 = BANDS ? sizes[plane0] : sizeGiven;
 
   if (threadIdx.x == 0)
   {
@@ -373,15 +436,20 @@ k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
       ti.head.blobSize = (u32)h.blobSize;
       ti.maxZErr = h.maxZErr; ti.zMin = h.zMin; ti.zMax = h.zMax;
       if (h.version != kCodecVersion || h.nRows != g.nRows || h.nCols != g.nCols || h.nDepth != 1 || h.numValid < 0 || (u32)h.numValid > nPix
-        || (h.microBlockSize != 8 && h.microBlockSize != 16) || h.blobSize < (int)(kHdr6 + 4u) || (u32)h.blobSize > sizeGiven || h.dt != g.dt || h.nBlobsMore != 0
+        || (h.microBlockSize != 8 && h.microBlockSize != 16) || h.blobSize < (int)(kHdr6 + 4u) || (u32)h.blobSize > sizeGiven || h.dt != g.dt || h.nBlobsMore != (BANDS ? (int)(nBands - 1u - band) : 0)
         || (h.flagBytes & 0xFFu) != 0u)
         fl = kTbHeader;
+      if (BANDS && !fl)
+      {
+        if (!validOut && (u32)h.numValid != nPix) fl = kTbHeader;
+        if (band > 0 && (size0 < kHdr6 + 4u || (u32)getBytes(blob0 + 26, 4) != (u32)h.numValid)) fl = kTbHeader;
+      }
       const int mbSize = h.microBlockSize;
       if (!fl)
       {
         nm = (u32)getBytes(blob + kHdr6, 4);
         const bool noStream = ti.numValid == nPix || ti.numValid == 0u;
-        if (noStream ? nm != 0u : (nm < 2u || nm > ti.head.blobSize)) fl = kTbHeader;
+        if ((noStream || band > 0u) ? nm != 0u : (nm < 2u || nm > ti.head.blobSize)) fl = kTbHeader;
         else if (ti.numValid == 0u)
         {
           // no valid pixel: nothing may follow the mask section's length (Lerc2.cpp:235-241); range and error bound are not asked
@@ -439,10 +507,21 @@ k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
   __syncthreads();
   if (!allValid && kind != kTmbKindEmpty && threadIdx.x == 0)
   {
-    if (!tbMaskUnrle(blob + kHdr6 + 4u, nm, s_bits, nBytes)) s_flags = kTmbMaskStream;
+    if (band > 0u)
+    {
+      const u32 nm0 = (u32)getBytes(blob0 + kHdr6, 4);
+      if (nm0 < 2u || (u64)kHdr6 + 4u + nm0 > (u64)size0 || !tbMaskUnrle(blob0 + kHdr6 + 4u, nm0, s_bits, nBytes)) s_flags = kTmbMaskStream;
+    }
+    else if (!tbMaskUnrle(blob + kHdr6 + 4u, nm, s_bits, nBytes)) s_flags = kTmbMaskStream;
   }
   __syncthreads();
   if (s_flags) { if (threadIdx.x == 0) { s_ti.head.flags = s_flags; b.tiles[t] = s_ti; } return; }
+  // (a mask taken over from band 0 must hold this band's count, whatever the band's kind)
+  if (band > 0u && !allValid && kind != kTmbKindEmpty && tbMaskCount(s_bits, nPix, s_red) != s_ti.numValid)
+  {
+    if (threadIdx.x == 0) { s_ti.head.flags = kTbHeader; b.tiles[t] = s_ti; }
+    return;
+  }
 
   T* __restrict__ out = outAll + (u64)t * g.tileElems;
   if (kind == kTmbKindConst || kind == kTmbKindOneSweep)
@@ -470,8 +549,11 @@ k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
   // ---- the bit mask for the block kernel, the caller's valid bytes
   u8* __restrict__ bitsOut = b.bits + (u64)t * g.bitStride;
   for (u32 i = threadIdx.x; i < nBytes; i += 256u) bitsOut[i] = s_bits[i];
-  u8* __restrict__ vOut = validOut + (u64)t * g.tileElems;
-  for (u32 k = threadIdx.x; k < nPix; k += 256u) vOut[k] = (u8)((s_bits[k >> 3] >> (7u - (k & 7u))) & 1u);
+  if (!BANDS || (band == 0u && validOut))
+  {
+    u8* __restrict__ vOut = validOut + (u64)(BANDS ? t / nBands : t) * g.tileElems;
+    for (u32 k = threadIdx.x; k < nPix; k += 256u) vOut[k] = (u8)((s_bits[k >> 3] >> (7u - (k & 7u))) & 1u);
+  }
   if (kind != kTmbKindBlocks8 && kind != kTmbKindBlocks16)
   {
     if (threadIdx.x == 0) b.tiles[t] = s_ti;
@@ -522,9 +604,37 @@ static void tmbDecodeT(const TmbGeom& g, const u8* dArena, const u64* dOffsets, 
                        const TmbDecodeBuffers& b, hipStream_t st)
 {
   const int nPos = g.nTV * g.nTH, nPos16 = ((g.nRows + 15) / 16) * ((g.nCols + 15) / 16);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_parse<T>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, dSizes, (T*)dTiles, dValidBytes, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_parse<T, false>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, dSizes, (T*)dTiles, dValidBytes, b, 1u);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_blocks<T, 8>), dim3((nPos + 3) / 4, g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, (T*)dTiles, b);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_blocks<T, 16>), dim3((nPos16 + 3) / 4, g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, (T*)dTiles, b);
+}
+
+template<class T>
+static void tmbDecodeBandsT(const TmbGeom& g, u32 nBands, const u8* dArena, const u64* dOffsets, const u32* dSizes, u64* planeOff, u32* planeSize,
+                            void* dTiles, u8* dValidBytes, const TmbDecodeBuffers& b, hipStream_t st)
+{
+  const int nPos = g.nTV * g.nTH, nPos16 = ((g.nRows + 15) / 16) * ((g.nCols + 15) / 16);
+  const u32 nTiles = g.nTiles / nBands;
+  hipLaunchKernelGGL(k_tmbd_chain, dim3((nTiles + 255u) / 256u), dim3(256), 0, st, g, nTiles, nBands, dArena, dOffsets, dSizes, planeOff, planeSize);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_parse<T, true>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, (const u64*)planeOff, (const u32*)planeSize, (T*)dTiles,
+                     dValidBytes, b, nBands);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_blocks<T, 8>), dim3((nPos + 3) / 4, g.nTiles), dim3(256), 0, st, g, dArena, (const u64*)planeOff, (T*)dTiles, b);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_blocks<T, 16>), dim3((nPos16 + 3) / 4, g.nTiles), dim3(256), 0, st, g, dArena, (const u64*)planeOff, (T*)dTiles, b);
+}
+
+void launchTmbDecodeBands(const TmbGeom& g, u32 nBands, const u8* dArena, const u64* dOffsets, const u32* dSizes, u64* planeOff, u32* planeSize,
+                          void* dTiles, u8* dValidBytes, const TmbDecodeBuffers& b, hipStream_t st)
+{
+  switch (g.dt)
+  {
+    case DT_Short:  tmbDecodeBandsT<short>(g, nBands, dArena, dOffsets, dSizes, planeOff, planeSize, dTiles, dValidBytes, b, st); break;
+    case DT_UShort: tmbDecodeBandsT<unsigned short>(g, nBands, dArena, dOffsets, dSizes, planeOff, planeSize, dTiles, dValidBytes, b, st); break;
+    case DT_Int:    tmbDecodeBandsT<int>(g, nBands, dArena, dOffsets, dSizes, planeOff, planeSize, dTiles, dValidBytes, b, st); break;
+    case DT_UInt:   tmbDecodeBandsT<unsigned int>(g, nBands, dArena, dOffsets, dSizes, planeOff, planeSize, dTiles, dValidBytes, b, st); break;
+    case DT_Float:  tmbDecodeBandsT<float>(g, nBands, dArena, dOffsets, dSizes, planeOff, planeSize, dTiles, dValidBytes, b, st); break;
+    case DT_Double: tmbDecodeBandsT<double>(g, nBands, dArena, dOffsets, dSizes, planeOff, planeSize, dTiles, dValidBytes, b, st); break;
+    default: break;
+  }
 }
 
 void launchTmbDecode(const TmbGeom& g, const u8* dArena, const u64* dOffsets, const u32* dSizes, void* dTiles, u8* dValidBytes,
