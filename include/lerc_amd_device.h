@@ -58,7 +58,7 @@ LERC_AMD_API lerc_status lerc_amd_finish(lerc_amd_context* ctx, unsigned int tic
  * bytes long; offsets / sizes / arenaUsed are HOST arrays the caller provides.  BufferTooSmall(3) if the arena is
  * too small (lerc_computeCompressedSize bounds a tile; nRows * nCols * sizeof(T) + 128 per tile always suffices).
  * Decoding takes the same description back.  Blobs that need the general kernels are handled inside, one by one.
- * 8-bit tiles (int8 / uint8, maxZErr < 1, up to 131 072 pixels and 4 096 blocks: 256 x 256, 257 x 257) are a batch as well, one set of
+ * 8-bit tiles (int8 / uint8, maxZErr < 1, up to 264 192 pixels and 4 352 blocks of 8 x 8: 256 x 256, 257 x 257, 512 x 512, 513 x 513) are a batch as well, one set of
  * launches and one host wait per sub-batch: statistics, both Huffman code books, the choice between Huffman, delta Huffman and 8 x 8
  * tiling, table, pixel stream and checksum are made on the device, a workgroup per tile.  Handed back and encoded one by one inside the
  * call, with the same bytes: a constant tile, one sweep, the 16 x 16 retry of the low-bit-rate rule (lerc_amd_last_note names the reason).
@@ -85,7 +85,7 @@ LERC_AMD_API lerc_status lerc_amd_decode_tiles_device_slots(lerc_amd_context* ct
  * _slots).  slotBytes == 0: packed arena, offsets[t] 16-byte aligned; slotBytes != 0 (a multiple of 16): tile t at dArena + t * slotBytes,
  * offsets[t] is set to that (arenaCapacity >= nTiles * slotBytes).  Tile t's blob is byte for byte what lerc_encode(tile t, nMasks = 1,
  * mask t) makes; a tile without an invalid pixel gets no mask section.  The batch's own launches (one set per sub-batch, one host wait)
- * take float32, float64 and the 16- and 32-bit integer types, tiles of up to 131 072 pixels and 4 096 blocks (256 x 256, 257 x 257), and
+ * take float32, float64 and the 16- and 32-bit integer types, tiles of up to 264 192 pixels and 4 352 blocks of 8 x 8 (256 x 256, 257 x 257, 512 x 512, 513 x 513), and
  * write header, mask section (run-length coded on the device), ranges, block stream and checksum -- of tiles without a valid pixel
  * (header only), constant tiles (header and mask section), one-sweep tiles (the valid pixels raw) and tiles whose low-bit-rate retry
  * ends in 16 x 16 blocks as well.  8-bit tiles (int8 / uint8, maxZErr < 1) WITH a mask pointer are a batch too, the masked form of the
@@ -118,7 +118,7 @@ LERC_AMD_API lerc_status lerc_amd_decode_tiles_device_masked(lerc_amd_context* c
  * only.  With nBands == 1 these are the calls above.
  * The batch's own launches (one set per sub-batch, one host wait; the unit is the plane, tile * nBands + band, and a tile is the
  * batch's only if all its planes are) take the wide types -- float32, float64, the 16- and 32-bit integers -- with nMasks 0 or 1, up to
- * 131 072 pixels and 4 096 blocks a band: per band its own statistics, error bound (all-integer float values, TryRaiseMaxZError), kind
+ * 264 192 pixels and 4 352 blocks of 8 x 8 a band: per band its own statistics, error bound (all-integer float values, TryRaiseMaxZError), kind
  * (8 x 8 or 16 x 16 blocks, one sweep, constant, empty) and checksum; the mask's run-length stream once a tile, in band 0 -- the bands
  * behind it carry the header's count of valid pixels and an empty mask section.  With nMasks == 0 the planes run through the masked
  * family's kernels under a mask of all ones, as all-valid tiles inside a masked batch do; the fast one-launch tile encoder of
@@ -129,7 +129,7 @@ LERC_AMD_API lerc_status lerc_amd_decode_tiles_device_masked(lerc_amd_context* c
  * Handed back and encoded one by one inside the call, a whole stack per lerc_amd_encode_device call, same bytes and status
  * (lerc_amd_last_note names tile, band and reason): an 8-bit tile with a band of a kind the 8-bit batch hands back (constant, one
  * sweep, winning 16 x 16 blocks -- the tile goes back whole), 8-bit stacks at maxZErr >= 1, nMasks == nBands (masks per band need the masks-differ comparison and a second mask section), a tile with a NaN at a valid
- * pixel in any band (the mask then changes across the bands), maxZErr 777 or 0 on float values, oversized tiles, a blob that does not
+ * pixel in any band (the mask then changes across the bands), maxZErr 777 or 0 on float values, tiles beyond that size (lerc_amd_last_note then names the size), a blob that does not
  * fit its slot. */
 LERC_AMD_API lerc_status lerc_amd_encode_tiles_device_bands(lerc_amd_context* ctx, const void* dTiles, unsigned int dataType, int nCols, int nRows,
     int nBands, int nTiles, int nMasks, const unsigned char* dValidBytes, double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity,

@@ -38,8 +38,7 @@ struct TbStack { int nBands, nMasks; };
 // ================================================================================================
 static bool tmbShapeOk(int dt, int nRows, int nCols)
 {
-  const u64 nPix = (u64)nRows * (u64)nCols, nPos = (u64)((nRows + 7) / 8) * (u64)((nCols + 7) / 8);
-  return dt >= DT_Short && dt <= DT_Double && nPix <= (u64)kTmbMaxMaskBytes * 8u && nPos <= kTmbMaxBlocks;
+  return dt >= DT_Short && dt <= DT_Double && tbShapeFits(nRows, nCols);
 }
 
 struct MaskedBatch
@@ -191,8 +190,7 @@ struct MaskedBandsBatch : MaskedBatch
 // ================================================================================================
 static bool tbbShapeOk(int dt, int nRows, int nCols)
 {
-  const u64 nPix = (u64)nRows * (u64)nCols, nPos = (u64)((nRows + 7) / 8) * (u64)((nCols + 7) / 8);
-  return (dt == DT_Char || dt == DT_Byte) && nPix <= kTbbMaxPixels && nPos <= kTbbMaxBlocks;
+  return (dt == DT_Char || dt == DT_Byte) && tbShapeFits(nRows, nCols);
 }
 
 bool tilesBytesEncodeEligible(const TilesEncodeRequest& rq)
@@ -447,6 +445,16 @@ static void tbNoteBand(Context& ctx, int tile, const TbFold& f, const char* what
   ctx.lastNote = msg;
 }
 
+// every tile went one by one because of its size alone: said last, behind whatever the single encoder / decoder noted
+static void tbNoteSize(Context& ctx, int nRows, int nCols, const char* what)
+{
+  if (tbShapeFits(nRows, nCols)) return;
+  char msg[224];
+  snprintf(msg, sizeof(msg), "every tile of the batch is %s by itself: the size, %d x %d pixels, is beyond what the tile batches take (%u pixels and %u blocks of 8 x 8)",
+           what, nRows, nCols, kTbMaxPixels, kTbMaxBlocks);
+  ctx.lastNote = msg;
+}
+
 // batchOk == false: every tile one by one (a request the family's kernels do not take)
 template<class F>
 static u32 tbEncode(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed, bool batchOk)
@@ -484,7 +492,12 @@ static u32 tbEncode(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed, 
     arenaUsed = slotted ? (u64)rq.nTiles * rq.slotBytes : end;
     return kOk;
   };
-  if (!batchOk) return oneByOne();
+  if (!batchOk)
+  {
+    const u32 rc = oneByOne();
+    if (rc == kOk) tbNoteSize(ctx, rq.nRows, rq.nCols, "encoded");    // (a failure keeps what the single encoder said about it)
+    return rc;
+  }
 
   hipStream_t st = ctx.activeStream();
   F f(rq.dt, rq.nRows, rq.nCols, TbStack{ nB, nM });
@@ -573,7 +586,12 @@ static u32 tbDecode(Context& ctx, const TilesDecodeRequest& rq, bool batchOk)
     for (int t = 0; t < rq.nTiles; t++) decodeOne(t);
     return firstError;
   };
-  if (!batchOk) return oneByOne();
+  if (!batchOk)
+  {
+    const u32 rc = oneByOne();
+    if (rc == kOk) tbNoteSize(ctx, rq.nRows, rq.nCols, "decoded");
+    return rc;
+  }
 
   F f(rq.dt, rq.nRows, rq.nCols, TbStack{ nB, nM });
   const size_t perTile = f.decodeBytesPerTile();

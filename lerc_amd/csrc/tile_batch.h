@@ -35,6 +35,36 @@ struct TileGeom    // (TmbGeom, tile_mask_batch.h, has these fields too, with it
   u64 tileElems;
 };
 
+// ---- how large a tile (a plane of a band stack) the batches take: its bit mask and its per-block counts live in the LDS of the
+// kernels that own a tile.  513 x 513 is 263 169 pixels and 4 225 blocks of 8 x 8; both limits also admit long thin shapes.  Larger
+// tiles go one by one inside the call.
+static const u32 kTbMaxPixels = 264192;       // 516 x 512; 33 024 mask bytes
+static const u32 kTbMaxMaskBytes = kTbMaxPixels / 8;
+static const u32 kTbMaxBlocks = 4352;
+// the kernels with such arrays come in two forms, picked by the host from the shape (tbLargeForm): the small one holds what the batches
+// took before 512 x 512 tiles came in (256 x 256, 257 x 257: 8 257 mask bytes) and keeps its occupancy, the large one the limits above
+static const u32 kTbSmallMaskBytes = 16384;
+static const u32 kTbSmallBlocks = 4096;
+
+template<bool LARGE> struct TbForm
+{
+  static const u32 kMaskBytes = LARGE ? kTbMaxMaskBytes : kTbSmallMaskBytes;
+  static const u32 kBlocks = LARGE ? kTbMaxBlocks : kTbSmallBlocks;
+  static const u32 kMaskWords = kMaskBytes / 4u;    // words of 32 pixels
+};
+
+inline bool tbShapeFits(int nRows, int nCols)
+{
+  const u64 nPix = (u64)nRows * (u64)nCols, nPos = (u64)((nRows + 7) / 8) * (u64)((nCols + 7) / 8);
+  return nPix <= kTbMaxPixels && nPos <= kTbMaxBlocks;
+}
+
+template<class G>
+inline bool tbLargeForm(const G& g)
+{
+  return ((g.tileElems + 7u) >> 3) > kTbSmallMaskBytes || (u64)g.nTV * (u64)g.nTH > kTbSmallBlocks;
+}
+
 // the fields of BandParams that follow from a batch's geometry and a block size alone, the others zero
 template<class G>
 LERC_HD BandParams tbFillBandParams(const G& g, int mb)

@@ -54,11 +54,10 @@ struct TbbMaskBuffers
   u32 bitStride, rleStride, pos16Stride;
 };
 
-static const u32 kTbbMaxPixels = 131072;      // 257 x 257 is 66 049; a code longer than 32 bits needs more pixels than this
-static const u32 kTbbMaxBlocks = 4096;
+// (the size limits are the batches' common ones, tile_batch.h.  A Huffman code longer than 32 bits needs a histogram whose counts grow
+// like the Fibonacci numbers, 9 227 465 pixels at the least: far more than kTbMaxPixels, so tbbBuildBook's refusal is never met)
 static const u32 kTbbTableCap = 1280;         // 16 + 3 + 256 * 6 / 8 + 256 * 32 / 8 + 4, rounded up
 static const u32 kTbbDataBegin = 98;          // header 90, mask section 4, ranges 2, "not one sweep" 1, mode 1; masked: + TbbMaskRec::rleLen
-static const u32 kTbbMaxMaskBytes = kTbbMaxPixels / 8;
 static const u32 kTbbModeEmpty = 3;           // TbbTile::mode of a masked tile without a valid pixel: header and mask section are all of it
 
 struct TbbEncodeBuffers

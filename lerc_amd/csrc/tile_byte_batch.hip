@@ -67,11 +67,11 @@ __device__ __forceinline__ u32 tbbDelta(const u8* __restrict__ px, u32 k, u32 nC
 // that is valid (never across a row's start), else the pixel above if that is valid, else the last valid pixel in scan order,
 // however far back (0 in front of the first).  "The last valid pixel below k" is asked of the bit mask: inside k's word of 32
 // pixels a bit scan, else the last non-empty word below it -- a table made once per tile.
-static const u32 kTbbMaskWords = kTbbMaxPixels / 32u;
-
 struct TbbmMask
 {
-  const u8* bits;         // the tile's bit mask in LDS (BitMask's layout: most significant bit first), 16 zero bytes behind it
+  // the tile's bit mask (BitMask's layout: most significant bit first) in LDS, 16 zero bytes behind it -- or, k_tbb_write's large form,
+  // where it lies in the workspace, its last word of 32 pixels padded with zero bytes (k_tbb_stats)
+  const u8* bits;
   const u16* last;        // last[w]: 1 + the last word below w with a valid pixel in it, 0: none
   __device__ __forceinline__ u32 word(u32 w) const
   {
@@ -128,7 +128,8 @@ __device__ __forceinline__ u32 tbbmDelta(const u8* __restrict__ px, const TbbmMa
 // the mask's run-length stream by one lane -- and the histograms over valid pixels only
 // BANDS (MASKED only): t is a plane, tile * nBands + band (tile_byte_batch.h); the tile's mask lies at b.m.valid + tile * validStride,
 // and only band 0 makes the mask's run-length stream -- the bands behind it write the count 0
-template<class T, bool MASKED, bool BANDS = false>
+// LARGE (MASKED only): the form for tiles beyond the small form's mask bytes (tile_batch.h: TbForm), picked by the host from the shape
+template<class T, bool MASKED, bool BANDS = false, bool LARGE = false>
 __global__ void __launch_bounds__(256) k_tbb_stats(TbbGeom g, const u8* __restrict__ data, TbbEncodeBuffers b, u32 nBands, u64 validStride)
 {
   __shared__ u32 s_h[512];
@@ -140,12 +141,14 @@ __global__ void __launch_bounds__(256) k_tbb_stats(TbbGeom g, const u8* __restri
   u32 numValid = nPix, rleFlag = 0;
   if constexpr (MASKED)
   {
-    __shared__ __align__(16) u8 s_bits[kTbbMaxMaskBytes + 16];
-    __shared__ u16 s_last[kTbbMaskWords];
+    __shared__ __align__(16) u8 s_bits[TbForm<LARGE>::kMaskBytes + 16];
+    __shared__ u16 s_last[TbForm<LARGE>::kMaskWords];
     __shared__ u32 s_scan[256];
     __shared__ u64 s_red[4];
     const u8* __restrict__ vb = BANDS ? b.m.valid + (u64)(t / nBands) * validStride : b.m.valid + (u64)t * g.tileElems;
     const u32 cnt = tbMaskToBits(vb, nPix, s_bits, b.m.bits + (u64)t * b.m.bitStride, [](u32) {});
+    // (k_tbb_write's large form reads the mask as words of 32 pixels where it lies: the last word's bytes behind the mask are zero)
+    if (LARGE && threadIdx.x < 4u) b.m.bits[(u64)t * b.m.bitStride + ((nPix + 7u) >> 3) + threadIdx.x] = 0;
     numValid = (u32)blockSum((u64)cnt, s_red);    // (its barriers cover s_h and s_bits)
     if (threadIdx.x == 0)
     {
@@ -542,7 +545,9 @@ static const u32 kTbbStageWords = kTbbStep + 4u;    // 32 bits a code word at mo
 // in the pixel stream an invalid pixel is a code of length 0 -- the step's scan is the compaction
 // BANDS (MASKED only): the header says how many band blobs follow; the blob begins at any byte (every store here is a byte's, but
 // for the stream's words, which ask the address)
-template<class T, bool MASKED, bool BANDS = false>
+// LARGE (MASKED only): the bit mask is read where k_tbb_stats left it in the workspace, not copied into LDS -- with a copy of 33 KB
+// the kernel would hold more than 64 KB; only the table of last words is made in LDS
+template<class T, bool MASKED, bool BANDS = false, bool LARGE = false>
 __global__ void __launch_bounds__(256) k_tbb_write(TbbGeom g, const u8* __restrict__ data, u8* __restrict__ arena, TbbEncodeBuffers b, u32 nBands)
 {
   __shared__ u8 s_hdr[kTbbDataBegin + 2];
@@ -607,15 +612,20 @@ __global__ void __launch_bounds__(256) k_tbb_write(TbbGeom g, const u8* __restri
   TbbmMask m = { nullptr, nullptr };
   if constexpr (MASKED)
   {
-    __shared__ __align__(16) u8 s_bits[kTbbMaxMaskBytes + 16];
-    __shared__ u16 s_last[kTbbMaskWords];
+    __shared__ u16 s_last[TbForm<LARGE>::kMaskWords];
     __shared__ u32 s_scan[256];
     const u32 nBytes = (nPix + 7u) >> 3;
     const u8* __restrict__ bits = b.m.bits + (u64)t * b.m.bitStride;
-    for (u32 i = threadIdx.x; i < nBytes + 16u; i += 256u) s_bits[i] = i < nBytes ? bits[i] : (u8)0;
-    __syncthreads();
-    if (delta) tbbmLastWords(s_bits, nPix, s_last, s_scan);
-    m.bits = s_bits; m.last = s_last;
+    if constexpr (LARGE) m.bits = bits;
+    else
+    {
+      __shared__ __align__(16) u8 s_bits[kTbSmallMaskBytes + 16];
+      for (u32 i = threadIdx.x; i < nBytes + 16u; i += 256u) s_bits[i] = i < nBytes ? bits[i] : (u8)0;
+      __syncthreads();
+      m.bits = s_bits;
+    }
+    if (delta) tbbmLastWords(m.bits, nPix, s_last, s_scan);
+    m.last = s_last;
   }
   u32 carryBits = 0, carryWord = 0, wordBase = 0;
   for (u32 k0 = 0; k0 < nPix; k0 += kTbbStep)
@@ -690,7 +700,9 @@ static void tbbEncodeT(const TbbGeom& g, const BandParams& bp, const void* dTile
 {
   const int nPos = g.nTV * g.nTH;
   const dim3 perTile(g.nTiles), blk(256), perBlock((nPos + 3) / 4, g.nTiles);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_stats<T, MASKED, false>), perTile, blk, 0, st, g, (const u8*)dTiles, b, 1u, (u64)0);
+  const bool large = MASKED && tbLargeForm(g);    // (the forms without a mask hold no array that grows with the tile)
+  if (large) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_stats<T, MASKED, false, MASKED>), perTile, blk, 0, st, g, (const u8*)dTiles, b, 1u, (u64)0); }
+  else { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_stats<T, MASKED, false, false>), perTile, blk, 0, st, g, (const u8*)dTiles, b, 1u, (u64)0); }
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_blocks<T, false, MASKED>), perBlock, blk, 0, st, g, bp, (const T*)dTiles, (u8*)nullptr, b);
   hipLaunchKernelGGL(k_tbb_decide<MASKED>, perTile, blk, 0, st, g, slotBytes, firstTile, b);
   if constexpr (MASKED)
@@ -702,7 +714,8 @@ static void tbbEncodeT(const TbbGeom& g, const BandParams& bp, const void* dTile
   }
   if (!slotBytes) hipLaunchKernelGGL(k_tbb_arena, dim3(1), blk, 0, st, g.nTiles, arenaBase, arenaCapacity, b);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_blocks<T, true, MASKED>), perBlock, blk, 0, st, g, bp, (const T*)dTiles, dArena, b);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_write<T, MASKED, false>), perTile, blk, 0, st, g, (const u8*)dTiles, dArena, b, 1u);
+  if (large) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_write<T, MASKED, false, MASKED>), perTile, blk, 0, st, g, (const u8*)dTiles, dArena, b, 1u); }
+  else { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_write<T, MASKED, false, false>), perTile, blk, 0, st, g, (const u8*)dTiles, dArena, b, 1u); }
   hipLaunchKernelGGL(k_tbb_checksum, perTile, blk, 0, st, dArena, b);
 }
 
@@ -721,14 +734,17 @@ static void tbbEncodeBandsT(const TbbGeom& g, u32 nBands, const BandParams& bp, 
 {
   const int nPos = g.nTV * g.nTH, nPos16 = ((g.nRows + 15) / 16) * ((g.nCols + 15) / 16);
   const dim3 perPlane(g.nTiles), blk(256), perBlock((nPos + 3) / 4, g.nTiles);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_stats<T, true, true>), perPlane, blk, 0, st, g, (const u8*)dTiles, b, nBands, validStride);
+  const bool large = tbLargeForm(g);
+  if (large) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_stats<T, true, true, true>), perPlane, blk, 0, st, g, (const u8*)dTiles, b, nBands, validStride); }
+  else { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_stats<T, true, true, false>), perPlane, blk, 0, st, g, (const u8*)dTiles, b, nBands, validStride); }
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_blocks<T, false, true>), perBlock, blk, 0, st, g, bp, (const T*)dTiles, (u8*)nullptr, b);
   hipLaunchKernelGGL(k_tbb_decide<true>, perPlane, blk, 0, st, g, (u64)0, (u64)0, b);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_blocks16<T>), dim3((nPos16 + 3) / 4, g.nTiles), blk, 0, st, g, bp, (const T*)dTiles, b);
   hipLaunchKernelGGL(k_tbb_decide16, perPlane, blk, 0, st, g, b);
   hipLaunchKernelGGL(k_tbb_place_bands, dim3(1), blk, 0, st, g.nTiles / nBands, nBands, arenaBase, arenaCapacity, slotBytes, firstTile, b);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_blocks<T, true, true>), perBlock, blk, 0, st, g, bp, (const T*)dTiles, dArena, b);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_write<T, true, true>), perPlane, blk, 0, st, g, (const u8*)dTiles, dArena, b, nBands);
+  if (large) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_write<T, true, true, true>), perPlane, blk, 0, st, g, (const u8*)dTiles, dArena, b, nBands); }
+  else { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbb_write<T, true, true, false>), perPlane, blk, 0, st, g, (const u8*)dTiles, dArena, b, nBands); }
   hipLaunchKernelGGL(k_tbb_checksum, perPlane, blk, 0, st, dArena, b);
 }
 
@@ -827,13 +843,14 @@ __device__ bool tbbParseTable(const u8* __restrict__ p, u32 n, u8* __restrict__ 
 // stream ("the mask stays in force").  A band with a mask section of its own, or a count that is not band 0's, is refused: the
 // single-blob decoder takes the whole stack.  The caller's valid bytes are written by band 0; without them (b.m.valid null) a blob
 // with an invalid pixel is refused.
-template<class T, bool MASKED, bool BANDS = false>
+// LARGE (MASKED only): the form for tiles beyond the small form's mask bytes or blocks (tile_batch.h: TbForm)
+template<class T, bool MASKED, bool BANDS = false, bool LARGE = false>
 __global__ void __launch_bounds__(256)
 k_tbbd_parse(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ offsets, const u32* __restrict__ sizes, TbbDecodeBuffers b, u32 nBands)
 {
   __shared__ u64 s_red[4];
   __shared__ TbbTile s_ti;
-  __shared__ u16 s_nv[MASKED ? kTbbMaxBlocks : 1];
+  __shared__ u16 s_nv[MASKED ? TbForm<LARGE>::kBlocks : 1];
   __shared__ TbbMaskRec s_mr;
   const u32 t = blockIdx.x;
   const u8* __restrict__ blob = arena + offsets[t];
@@ -927,7 +944,7 @@ k_tbbd_parse(TbbGeom g, const u8* __restrict__ arena, const u64* __restrict__ of
   if constexpr (MASKED)
   {
     // ---- the mask: all ones, all zeros, or the run-length stream expanded (what it does not fill stays zero)
-    __shared__ __align__(16) u8 s_bits[kTbbMaxMaskBytes + 16];
+    __shared__ __align__(16) u8 s_bits[TbForm<LARGE>::kMaskBytes + 16];
     const TbbMaskRec mr = s_mr;
     const u32 nBytes = (nPix + 7u) >> 3;
     const bool allValid = mr.numValid == nPix, empty = mr.numValid == 0u;
@@ -1275,7 +1292,8 @@ template<class T, bool MASKED>
 static void tbbDecodeT(const TbbGeom& g, const u8* dArena, const u64* dOffsets, const u32* dSizes, void* dTiles, const TbbDecodeBuffers& b, hipStream_t st)
 {
   const int nPos = g.nTV * g.nTH;
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_parse<T, MASKED, false>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, dSizes, b, 1u);
+  if (MASKED && tbLargeForm(g)) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_parse<T, MASKED, false, MASKED>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, dSizes, b, 1u); }
+  else { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_parse<T, MASKED, false, false>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, dSizes, b, 1u); }
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_blocks<T, MASKED>), dim3((nPos + 3) / 4, g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, (T*)dTiles, b);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_huff<T, MASKED>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, (u8*)dTiles, b);
 }
@@ -1295,8 +1313,8 @@ static void tbbDecodeBandsT(const TbbGeom& g, u32 nBands, const u8* dArena, cons
   const int nPos = g.nTV * g.nTH;
   const u32 nTiles = g.nTiles / nBands;
   hipLaunchKernelGGL(k_tbbd_chain, dim3((nTiles + 255u) / 256u), dim3(256), 0, st, g, nTiles, nBands, dArena, dOffsets, dSizes, planeOff, planeSize);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_parse<T, true, true>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, (const u64*)planeOff, (const u32*)planeSize, b,
-                     nBands);
+  if (tbLargeForm(g)) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_parse<T, true, true, true>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, (const u64*)planeOff, (const u32*)planeSize, b, nBands); }
+  else { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_parse<T, true, true, false>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, (const u64*)planeOff, (const u32*)planeSize, b, nBands); }
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_blocks<T, true>), dim3((nPos + 3) / 4, g.nTiles), dim3(256), 0, st, g, dArena, (const u64*)planeOff, (T*)dTiles, b);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tbbd_huff<T, true>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, (const u64*)planeOff, (u8*)dTiles, b);
 }

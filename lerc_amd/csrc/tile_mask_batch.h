@@ -56,9 +56,6 @@ struct TmbGeom    // TileGeom's fields and this family's strides
   u64 tileElems;
 };
 
-static const u32 kTmbMaxMaskBytes = 16384;    // a tile's bit mask in LDS: 128 K pixels (257 x 257 is 8 257 bytes)
-static const u32 kTmbMaxBlocks = 4096;
-
 struct TmbEncodeBuffers
 {
   TmbTile* tiles;

@@ -50,14 +50,15 @@ template<> struct TmbAcc<double> { typedef double type; static __device__ __forc
 // ================================================================================================
 // BANDS: t is a plane, tile * nBands + band (tile_mask_batch.h); the tile's mask lies at valid + tile * validStride, and only band 0
 // makes the mask's run-length stream -- the bands behind it write the count 0, "the mask of the band in front stays in force"
-template<class T, bool BANDS = false>
+// LARGE: the form for tiles beyond the small form's mask bytes or blocks (tile_batch.h: TbForm), picked by the host from the shape
+template<class T, bool BANDS = false, bool LARGE = false>
 __global__ void __launch_bounds__(256)
 k_tmb_prelude(TmbGeom g, double maxZErr, u32 cand, const T* __restrict__ data, const u8* __restrict__ valid, TmbEncodeBuffers b, u32 nBands,
               u64 validStride)
 {
   typedef typename TmbAcc<T>::type Acc;
   constexpr bool isFlt = DtOf<T>::v >= DT_Float;
-  __shared__ __align__(16) u8 s_bits[kTmbMaxMaskBytes + 16];
+  __shared__ __align__(16) u8 s_bits[TbForm<LARGE>::kMaskBytes + 16];
   __shared__ u64 s_red[4];
   __shared__ Acc s_mn[4], s_mx[4];
   __shared__ u64 s_raise[4][9];
@@ -316,7 +317,8 @@ static void tmbEncodeBandsT(const TmbGeom& g, u32 nBands, const BandParams& bp, 
   // (the single-band launch set over the planes; the slot check and the placement are k_tmb_place_bands' for whole tiles)
   const int nPos = g.nTV * g.nTH, nPos16 = ((g.nRows + 15) / 16) * ((g.nCols + 15) / 16);
   const dim3 perPlane(g.nTiles), blk(256);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_prelude<T, true>), perPlane, blk, 0, st, g, maxZErr, cand, (const T*)dTiles, dValidBytes, b, nBands, validStride);
+  if (tbLargeForm(g)) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_prelude<T, true, true>), perPlane, blk, 0, st, g, maxZErr, cand, (const T*)dTiles, dValidBytes, b, nBands, validStride); }
+  else { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_prelude<T, true, false>), perPlane, blk, 0, st, g, maxZErr, cand, (const T*)dTiles, dValidBytes, b, nBands, validStride); }
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_blocks<T, 8, false>), dim3((nPos + 3) / 4, g.nTiles), blk, 0, st, g, bp, (const T*)dTiles, (u8*)nullptr, b);
   hipLaunchKernelGGL(k_tmb_decide, perPlane, blk, 0, st, g, (u32)sizeof(T), b);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_blocks<T, 16, false>), dim3((nPos16 + 3) / 4, g.nTiles), blk, 0, st, g, bp, (const T*)dTiles, (u8*)nullptr, b);
@@ -348,7 +350,8 @@ static void tmbEncodeT(const TmbGeom& g, const BandParams& bp, double maxZErr, u
 {
   const int nPos = g.nTV * g.nTH, nPos16 = ((g.nRows + 15) / 16) * ((g.nCols + 15) / 16);
   const dim3 perTile(g.nTiles), blk(256);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_prelude<T, false>), perTile, blk, 0, st, g, maxZErr, cand, (const T*)dTiles, dValidBytes, b, 1u, (u64)0);
+  if (tbLargeForm(g)) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_prelude<T, false, true>), perTile, blk, 0, st, g, maxZErr, cand, (const T*)dTiles, dValidBytes, b, 1u, (u64)0); }
+  else { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_prelude<T, false, false>), perTile, blk, 0, st, g, maxZErr, cand, (const T*)dTiles, dValidBytes, b, 1u, (u64)0); }
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmb_blocks<T, 8, false>), dim3((nPos + 3) / 4, g.nTiles), blk, 0, st, g, bp, (const T*)dTiles, (u8*)nullptr, b);
   hipLaunchKernelGGL(k_tmb_decide, perTile, blk, 0, st, g, (u32)sizeof(T), b);
   // (over the whole batch, whether a tile is marked or not: the host knows nothing yet, and does not wait to learn it)
@@ -400,14 +403,14 @@ k_tmbd_chain(TmbGeom g, u32 nTiles, u32 nBands, const u8* __restrict__ arena, co
 // section of its own: its count of valid pixels is band 0's, and between none and all it takes band 0's run-length stream ("the mask
 // stays in force").  A band with a mask section of its own, or a count that is not band 0's, is refused: the single-blob decoder
 // takes the whole stack.  The caller's valid bytes are written by band 0; without them a blob with an invalid pixel is refused.
-template<class T, bool BANDS = false>
+template<class T, bool BANDS = false, bool LARGE = false>
 __global__ void __launch_bounds__(256)
 k_tmbd_parse(TmbGeom g, const u8* __restrict__ arena, const u64* __restrict__ offsets, const u32* __restrict__ sizes, T* __restrict__ outAll,
              u8* __restrict__ validOut, TmbDecodeBuffers b, u32 nBands)
 {
   constexpr u32 TB = (u32)sizeof(T);
-  __shared__ __align__(16) u8 s_bits[kTmbMaxMaskBytes + 16];
-  __shared__ u16 s_nv[kTmbMaxBlocks];
+  __shared__ __align__(16) u8 s_bits[TbForm<LARGE>::kMaskBytes + 16];
+  __shared__ u16 s_nv[TbForm<LARGE>::kBlocks];
   __shared__ u64 s_red[4];
   __shared__ u32 s_w[4];
   __shared__ TmbTile s_ti;
@@ -604,7 +607,8 @@ static void tmbDecodeT(const TmbGeom& g, const u8* dArena, const u64* dOffsets, 
                        const TmbDecodeBuffers& b, hipStream_t st)
 {
   const int nPos = g.nTV * g.nTH, nPos16 = ((g.nRows + 15) / 16) * ((g.nCols + 15) / 16);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_parse<T, false>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, dSizes, (T*)dTiles, dValidBytes, b, 1u);
+  if (tbLargeForm(g)) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_parse<T, false, true>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, dSizes, (T*)dTiles, dValidBytes, b, 1u); }
+  else { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_parse<T, false, false>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, dSizes, (T*)dTiles, dValidBytes, b, 1u); }
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_blocks<T, 8>), dim3((nPos + 3) / 4, g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, (T*)dTiles, b);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_blocks<T, 16>), dim3((nPos16 + 3) / 4, g.nTiles), dim3(256), 0, st, g, dArena, dOffsets, (T*)dTiles, b);
 }
@@ -616,8 +620,10 @@ static void tmbDecodeBandsT(const TmbGeom& g, u32 nBands, const u8* dArena, cons
   const int nPos = g.nTV * g.nTH, nPos16 = ((g.nRows + 15) / 16) * ((g.nCols + 15) / 16);
   const u32 nTiles = g.nTiles / nBands;
   hipLaunchKernelGGL(k_tmbd_chain, dim3((nTiles + 255u) / 256u), dim3(256), 0, st, g, nTiles, nBands, dArena, dOffsets, dSizes, planeOff, planeSize);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_parse<T, true>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, (const u64*)planeOff, (const u32*)planeSize, (T*)dTiles,
-                     dValidBytes, b, nBands);
+  if (tbLargeForm(g)) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_parse<T, true, true>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, (const u64*)planeOff, (const u32*)planeSize, (T*)dTiles,
+                                         dValidBytes, b, nBands); }
+  else { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_parse<T, true, false>), dim3(g.nTiles), dim3(256), 0, st, g, dArena, (const u64*)planeOff, (const u32*)planeSize, (T*)dTiles,
+                          dValidBytes, b, nBands); }
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_blocks<T, 8>), dim3((nPos + 3) / 4, g.nTiles), dim3(256), 0, st, g, dArena, (const u64*)planeOff, (T*)dTiles, b);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tmbd_blocks<T, 16>), dim3((nPos16 + 3) / 4, g.nTiles), dim3(256), 0, st, g, dArena, (const u64*)planeOff, (T*)dTiles, b);
 }
