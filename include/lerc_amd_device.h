@@ -150,6 +150,41 @@ LERC_AMD_API lerc_status lerc_amd_decode_tiles_device_bands(lerc_amd_context* ct
  * one behind the batch, out[2] / out[3] the same for decodes. */
 LERC_AMD_API void lerc_amd_tile_batch_counters(lerc_amd_context* ctx, unsigned long long out[4]);
 
+/* Raster mosaics: a raster that lies in device memory as it is -- nBands planes of nRows rows, rowPitch ELEMENTS from row to row
+ * (>= nCols) and bandPitch elements from band to band (>= (nRows - 1) * rowPitch + nCols; ignored with one band), a view into a larger
+ * allocation included -- is cut into a grid of tiles of tileRows x tileCols and every tile coded, in ONE call.  The grid:
+ * nTY = ceil(nRows / tileRows) by nTX = ceil(nCols / tileCols) tiles, tile (ty, tx) has index t = ty * nTX + tx and covers rows
+ * [ty * tileRows, min(nRows, (ty + 1) * tileRows)) and the columns likewise: the last row and column of tiles are smaller where the
+ * raster is no multiple of the tile.  offsets / sizes: HOST arrays of nTY * nTX entries.  nMasks is 0 (dValidBytes NULL) or 1: one
+ * byte mask [nRows][nCols] for the raster, maskRowPitch bytes from row to row, shared by the bands; WrongParam(2) for any other nMasks
+ * (a mask per band is not taken here), for a pitch below the width, sizes that are not positive, slotBytes that is no multiple of 16.
+ * Tile t's blob is byte for byte what lerc_encode makes of that rectangle (nDepth 1, nBands, nMasks, the rectangle's part of the mask,
+ * maxZErr) -- what lerc_amd_encode_tiles_device_bands, _masked or the unmasked tile call makes of the same tile.  slotBytes == 0,
+ * packed: every blob begins 16-byte aligned at dArena + offsets[t]; the order in the arena is the call's own.  slotBytes != 0 (a
+ * multiple of 16, arenaCapacity >= nTiles * slotBytes): every blob has a room of slotBytes that begins at a multiple of slotBytes,
+ * offsets[t] says which -- rooms are handed out per shape class, so room k is not necessarily tile k.  arenaUsed and the status codes
+ * as in the tile calls above.
+ * Inside, the grid's tiles of one shape -- at most four classes: interior, right column, bottom row, corner -- are gathered, a chunk of
+ * at most 256 MiB at a time, into a staging buffer the context owns (one launch a chunk, one more for the mask), and the chunk is
+ * handed to the tile calls above: their size limits, hand-backs, lerc_amd_last_note and lerc_amd_tile_batch_counters hold as they
+ * stand.  With one band, tiles as wide as the raster (tileCols >= nCols) and no padding (rowPitch == nCols; maskRowPitch == nCols)
+ * the tiles lie as a mosaic already and are coded where they lie.  The raster is only read. */
+LERC_AMD_API lerc_status lerc_amd_encode_raster_tiles_device(lerc_amd_context* ctx, const void* dRaster, unsigned int dataType, int nCols,
+    int nRows, int nBands, unsigned long long rowPitch, unsigned long long bandPitch, int tileCols, int tileRows, int nMasks,
+    const unsigned char* dValidBytes, unsigned long long maskRowPitch, double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity,
+    unsigned long long slotBytes, unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed);
+/* The way back, same description: pixels and valid bytes of every rectangle are exactly what lerc_amd_decode_tiles_device_bands writes
+ * for that blob (one band and no mask pointer: what lerc_amd_decode_tiles_device writes).  A blob that fails leaves its rectangle
+ * zeroed, all bands and the mask's rectangle; the other tiles are decoded all the same, and the call returns the first such status.
+ * Bytes of the raster and of the mask outside [0, nCols) of a row -- the pitch's padding, whatever lies beside a view -- are never
+ * written and never read. */
+LERC_AMD_API lerc_status lerc_amd_decode_raster_tiles_device(lerc_amd_context* ctx, const unsigned char* dArena, const unsigned long long* offsets,
+    const unsigned int* sizes, unsigned int dataType, int nCols, int nRows, int nBands, unsigned long long rowPitch, unsigned long long bandPitch,
+    int tileCols, int tileRows, void* dRaster, int nMasks, unsigned char* dValidBytes, unsigned long long maskRowPitch);
+/* Diagnostics of the two calls above: tiles out[0] cut through the staging buffer, out[1] encoded where they lie, out[2] pasted from
+ * the staging buffer, out[3] decoded where they lie. */
+LERC_AMD_API void lerc_amd_raster_tiles_counters(lerc_amd_context* ctx, unsigned long long out[4]);
+
 /* Per-kernel timing with HIP events on the context's stream (used by bench.py for the roofline of the
  * dominant kernel).  lerc_amd_profile_read writes lines "kernel_group total_ms launches" into buf. */
 LERC_AMD_API void lerc_amd_profile_enable(lerc_amd_context* ctx, int on);

@@ -80,6 +80,17 @@ def load_library():
                                                            ct.c_void_p, ct.c_void_p]
         lib.lerc_amd_decode_tiles_device_bands.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_int,
                                                            ct.c_uint, ct.c_void_p, ct.c_int, ct.c_void_p]
+    # (the raster tile calls: the same rule)
+    have_raster = not os.environ.get("LERC_AMD_LIBRARY") or hasattr(lib, "lerc_amd_encode_raster_tiles_device")
+    if have_raster:
+        lib.lerc_amd_encode_raster_tiles_device.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int, ct.c_int, ct.c_int, ct.c_ulonglong,
+                                                            ct.c_ulonglong, ct.c_int, ct.c_int, ct.c_int, ct.c_void_p, ct.c_ulonglong, ct.c_double,
+                                                            ct.c_void_p, ct.c_ulonglong, ct.c_ulonglong, ct.c_void_p, ct.c_void_p, ct.c_void_p]
+        lib.lerc_amd_decode_raster_tiles_device.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int, ct.c_int, ct.c_int,
+                                                            ct.c_ulonglong, ct.c_ulonglong, ct.c_int, ct.c_int, ct.c_void_p, ct.c_int, ct.c_void_p,
+                                                            ct.c_ulonglong]
+        lib.lerc_amd_raster_tiles_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_ulonglong)]
+        lib.lerc_amd_raster_tiles_counters.restype = None
     lib.lerc_amd_tile_batch_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_ulonglong)]
     lib.lerc_amd_tile_batch_counters.restype = None
     lib.lerc_amd_encode_device_async.argtypes = [ct.c_void_p] + enc + [ct.c_void_p, ct.c_uint, u32p]
@@ -90,7 +101,8 @@ def load_library():
               "lerc_amd_encode_device", "lerc_amd_decode_device", "lerc_amd_encode_tiles_device", "lerc_amd_decode_tiles_device",
               "lerc_amd_encode_device_async", "lerc_amd_decode_device_async", "lerc_amd_finish", "lerc_amd_encode_tiles_device_slots",
               "lerc_amd_decode_tiles_device_slots", "lerc_amd_encode_tiles_device_masked", "lerc_amd_decode_tiles_device_masked") + \
-            (("lerc_amd_encode_tiles_device_bands", "lerc_amd_decode_tiles_device_bands") if have_bands else ()):
+            (("lerc_amd_encode_tiles_device_bands", "lerc_amd_decode_tiles_device_bands") if have_bands else ()) + \
+            (("lerc_amd_encode_raster_tiles_device", "lerc_amd_decode_raster_tiles_device") if have_raster else ()):
         getattr(lib, n).restype = ct.c_uint
     _LIB = lib
     return lib
@@ -280,6 +292,39 @@ class DeviceCodec:
         return self.lib.lerc_amd_decode_tiles_device_bands(self.h, d_arena, offsets.ctypes.data, sizes.ctypes.data, n_tiles, n_cols, n_rows,
                                                            n_bands, dt_code, d_tiles, n_masks, d_valid or None)
 
+    def raster_tiles_counters(self):
+        """tiles of the raster tile calls of this context: [cut through the staging buffer, encoded where they lie, pasted from the staging
+        buffer, decoded where they lie]"""
+        out = (ct.c_ulonglong * 4)()
+        self.lib.lerc_amd_raster_tiles_counters(self.h, out)
+        return list(out)
+
+    def encode_raster_tiles(self, d_raster, dt_code, n_cols, n_rows, n_bands, row_pitch, band_pitch, tile, d_valid, mask_row_pitch, max_z_err,
+                            d_arena, arena_cap, slot_bytes=0):
+        """a pitched raster, raw device addresses, pitches in elements; tile: (tileRows, tileCols); d_valid 0 / None: no mask
+        -> (status, offsets uint64[nTiles], sizes uint32[nTiles], arena bytes used), tiles in the order of raster_tile_grid"""
+        n_tiles = len(raster_tile_grid(n_rows, n_cols, tile))
+        offsets = np.zeros(n_tiles, np.uint64)
+        sizes = np.zeros(n_tiles, np.uint32)
+        used = ct.c_ulonglong(0)
+        rc = self.lib.lerc_amd_encode_raster_tiles_device(self.h, d_raster, dt_code, n_cols, n_rows, n_bands, int(row_pitch), int(band_pitch),
+                                                          int(tile[1]), int(tile[0]), 1 if d_valid else 0, d_valid or None, int(mask_row_pitch),
+                                                          float(max_z_err), d_arena, int(arena_cap), int(slot_bytes), offsets.ctypes.data,
+                                                          sizes.ctypes.data, ct.byref(used))
+        return rc, offsets, sizes, int(used.value)
+
+    def decode_raster_tiles(self, d_arena, offsets, sizes, dt_code, n_cols, n_rows, n_bands, row_pitch, band_pitch, tile, d_raster, d_valid,
+                            mask_row_pitch):
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        sizes = np.ascontiguousarray(sizes, np.uint32)
+        assert len(offsets) == len(sizes) == len(raster_tile_grid(n_rows, n_cols, tile))
+        return self.lib.lerc_amd_decode_raster_tiles_device(self.h, d_arena, offsets.ctypes.data, sizes.ctypes.data, dt_code, n_cols, n_rows, n_bands,
+                                                            int(row_pitch), int(band_pitch), int(tile[1]), int(tile[0]), d_raster,
+                                                            1 if d_valid else 0, d_valid or None, int(mask_row_pitch))
+
+    def raster_tile_grid(self, n_rows, n_cols, tile):
+        return raster_tile_grid(n_rows, n_cols, tile)
+
     def last_note(self):
         """why the last call that left the streaming kernels (or went down a streaming tier) did so; "" if none did"""
         self.lib.lerc_amd_last_note.argtypes = [ct.c_void_p]
@@ -445,3 +490,49 @@ def decode_tiles_device_bands(codec, arena, offsets, sizes, out, valid_out):
     n_masks, d_valid = _band_masks(valid_out, n_tiles, n_bands, n_rows, n_cols)
     return codec.decode_tiles_bands(arena.data_ptr(), offsets, sizes, n_tiles, n_cols, n_rows, n_bands, _torch_dt_code(out), out.data_ptr(),
                                     n_masks, d_valid)
+
+
+def raster_tile_grid(n_rows, n_cols, tile):
+    """the tiles a raster of n_rows x n_cols is cut into, tile = (tileRows, tileCols): [(row0, row1, col0, col1)] in tile order, row by
+    row of the grid -- the order of the raster tile calls' offsets and sizes; the last row and column of tiles are smaller where the
+    raster is no multiple of the tile"""
+    tile_rows, tile_cols = int(tile[0]), int(tile[1])
+    assert n_rows > 0 and n_cols > 0 and tile_rows > 0 and tile_cols > 0
+    return [(r0, min(n_rows, r0 + tile_rows), c0, min(n_cols, c0 + tile_cols))
+            for r0 in range(0, n_rows, tile_rows) for c0 in range(0, n_cols, tile_cols)]
+
+
+def _raster_view(raster, valid):
+    """-> (nBands, nRows, nCols, rowPitch, bandPitch, mask address, mask row pitch) of a raster tensor [R, C] or [B, R, C] whose rows are
+    dense (stride(-1) == 1) -- a view into a larger tensor is fine: the pitches are its strides"""
+    assert raster.dim() in (2, 3) and raster.stride(-1) == 1, "raster: [R, C] or [B, R, C] with dense rows"
+    n_rows, n_cols = int(raster.shape[-2]), int(raster.shape[-1])
+    n_bands = int(raster.shape[0]) if raster.dim() == 3 else 1
+    row_pitch = int(raster.stride(-2)) if n_rows > 1 else n_cols
+    band_pitch = int(raster.stride(0)) if (raster.dim() == 3 and n_bands > 1) else 0
+    assert row_pitch >= n_cols and (n_bands == 1 or band_pitch >= (n_rows - 1) * row_pitch + n_cols), "raster: rows and bands must not overlap"
+    if valid is None:
+        return n_bands, n_rows, n_cols, row_pitch, band_pitch, 0, 0
+    assert valid.element_size() == 1 and tuple(valid.shape) == (n_rows, n_cols) and valid.stride(-1) == 1, "valid: uint8 [R, C] with dense rows"
+    mask_pitch = int(valid.stride(0)) if n_rows > 1 else n_cols
+    assert mask_pitch >= n_cols
+    return n_bands, n_rows, n_cols, row_pitch, band_pitch, valid.data_ptr(), mask_pitch
+
+
+def encode_raster_tiles_device(codec, raster, valid, max_z_err, tile, arena, slot_bytes=0):
+    """raster: CUDA(HIP) tensor [R, C] or [B, R, C], a view allowed as long as stride(-1) == 1; valid: uint8 tensor [R, C] (0 = invalid, one
+    mask for all bands) or None; tile: (tileRows, tileCols); arena: uint8 CUDA tensor.  The raster is cut into the grid of
+    raster_tile_grid and every tile becomes one blob, exactly what encode() makes of that rectangle (all bands, its part of the mask);
+    slot_bytes != 0 (a multiple of 16): every blob in a room of its own, offsets says which.
+    -> (status, offsets uint64[nTiles], sizes uint32[nTiles], arena bytes used)"""
+    n_bands, n_rows, n_cols, row_pitch, band_pitch, d_valid, mask_pitch = _raster_view(raster, valid)
+    return codec.encode_raster_tiles(raster.data_ptr(), _torch_dt_code(raster), n_cols, n_rows, n_bands, row_pitch, band_pitch, tile, d_valid,
+                                     mask_pitch, max_z_err, arena.data_ptr(), arena.numel(), slot_bytes)
+
+
+def decode_raster_tiles_device(codec, arena, offsets, sizes, out, valid_out, tile):
+    """the way back: out a tensor as `raster` above, valid_out as `valid` (written 1 / 0) or None.  A tile whose blob fails leaves its
+    rectangle zeroed, all bands and mask; elements outside the rows of `out` (a view's surroundings) are not touched."""
+    n_bands, n_rows, n_cols, row_pitch, band_pitch, d_valid, mask_pitch = _raster_view(out, valid_out)
+    return codec.decode_raster_tiles(arena.data_ptr(), offsets, sizes, _torch_dt_code(out), n_cols, n_rows, n_bands, row_pitch, band_pitch, tile,
+                                     out.data_ptr(), d_valid, mask_pitch)

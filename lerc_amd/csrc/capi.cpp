@@ -738,6 +738,50 @@ void lerc_amd_tile_batch_counters(lerc_amd_context* h, unsigned long long out[4]
   for (int i = 0; i < 4; i++) out[i] = h ? h->ctx.tileBatchCount[i] : 0;
 }
 
+// ---- a pitched raster cut into a grid of tiles (codec_raster_tiles.cpp)
+static bool rasterTileDimsOk(int nCols, int nRows, int tileCols, int tileRows, unsigned int dataType)
+{
+  return dimsOk(1, std::min(nCols, tileCols), std::min(nRows, tileRows), (size_t)dtSize((int)dataType));
+}
+
+lerc_status lerc_amd_encode_raster_tiles_device(lerc_amd_context* h, const void* dRaster, unsigned int dataType, int nCols, int nRows, int nBands,
+  unsigned long long rowPitch, unsigned long long bandPitch, int tileCols, int tileRows, int nMasks, const unsigned char* dValidBytes,
+  unsigned long long maskRowPitch, double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity, unsigned long long slotBytes,
+  unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed)
+{
+  if (arenaUsed) *arenaUsed = 0;
+  if (!h || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || tileCols <= 0 || tileRows <= 0) return kWrongParam;
+  if (!rasterTileDimsOk(nCols, nRows, tileCols, tileRows, dataType)) return kDimsTooLarge;
+  RasterTilesRequest rq;
+  rq.dRaster = const_cast<void*>(dRaster); rq.dValidBytes = const_cast<unsigned char*>(dValidBytes); rq.dt = (int)dataType;
+  rq.nCols = nCols; rq.nRows = nRows; rq.nBands = nBands; rq.nMasks = nMasks; rq.tileCols = tileCols; rq.tileRows = tileRows;
+  rq.rowPitch = rowPitch; rq.bandPitch = bandPitch; rq.maskRowPitch = maskRowPitch;
+  rq.dArena = dArena; rq.hOffsets = offsets; rq.hSizes = sizes; rq.maxZErr = maxZErr; rq.arenaCapacity = arenaCapacity; rq.slotBytes = slotBytes;
+  u64 used = 0;
+  const u32 rc = encodeRasterTilesDevice(h->ctx, rq, used);
+  if (arenaUsed) *arenaUsed = used;
+  return rc;
+}
+
+lerc_status lerc_amd_decode_raster_tiles_device(lerc_amd_context* h, const unsigned char* dArena, const unsigned long long* offsets,
+  const unsigned int* sizes, unsigned int dataType, int nCols, int nRows, int nBands, unsigned long long rowPitch, unsigned long long bandPitch,
+  int tileCols, int tileRows, void* dRaster, int nMasks, unsigned char* dValidBytes, unsigned long long maskRowPitch)
+{
+  if (!h || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || tileCols <= 0 || tileRows <= 0) return kWrongParam;
+  if (!rasterTileDimsOk(nCols, nRows, tileCols, tileRows, dataType)) return kDimsTooLarge;
+  RasterTilesRequest rq;
+  rq.dRaster = dRaster; rq.dValidBytes = dValidBytes; rq.dt = (int)dataType;
+  rq.nCols = nCols; rq.nRows = nRows; rq.nBands = nBands; rq.nMasks = nMasks; rq.tileCols = tileCols; rq.tileRows = tileRows;
+  rq.rowPitch = rowPitch; rq.bandPitch = bandPitch; rq.maskRowPitch = maskRowPitch;
+  rq.dArena = const_cast<unsigned char*>(dArena); rq.hOffsets = const_cast<unsigned long long*>(offsets); rq.hSizes = const_cast<unsigned int*>(sizes);
+  return decodeRasterTilesDevice(h->ctx, rq);
+}
+
+void lerc_amd_raster_tiles_counters(lerc_amd_context* h, unsigned long long out[4])
+{
+  for (int i = 0; i < 4; i++) out[i] = h ? h->ctx.rasterTilesCount[i] : 0;
+}
+
 void lerc_amd_profile_enable(lerc_amd_context* h, int on) { if (h) h->ctx.profEnable(on != 0); }
 
 int lerc_amd_profile_read(lerc_amd_context* h, char* buf, int cap, int reset)

@@ -137,6 +137,9 @@ public:
   void wipePersistentState();
   // a value no earlier call of this context has used and that no fill pattern looks like: kernels raise flags by
   // writing it into cells that are never cleared (tile_fast.h)
+  // the raster tile calls' staging buffer (codec_raster_tiles.cpp): outside the bump workspace, which the tile batches reset per
+  // sub-batch; grows on demand (contents are not kept), freed with the context
+  u8* rasterStage(size_t bytes);
   u32 nextEpoch() { m_epoch += 0x9E3779B9u; if ((m_epoch & 0xFFFFu) == (m_epoch >> 16) || m_epoch == 0u) m_epoch += 0x9E3779B9u; return m_epoch; }
 
   std::string lastError;
@@ -145,6 +148,7 @@ public:
   // which kernels served the calls so far: [0] encode streaming, [1] encode general, [2] decode streaming, [3] decode general
   unsigned long long pathCount[4] = { 0, 0, 0, 0 };
   unsigned long long tileBatchCount[4] = { 0, 0, 0, 0 };    // tiles of batch calls (lerc_amd_tile_batch_counters): [0] encoded by the batch's own launches, [1] encoded one by one behind it, [2] / [3] the same for decodes
+  unsigned long long rasterTilesCount[4] = { 0, 0, 0, 0 };  // tiles of the raster tile calls (lerc_amd_raster_tiles_counters): [0] cut through the staging buffer, [1] encoded where they lie, [2] pasted from the staging buffer, [3] decoded where they lie
   bool lastDecodeStreamed = false;
   DecodeTiers tiers;                   // which streaming decoder a band starts with, and the counters of what became of it
   bool scanOffsetsBan = false;         // this call: a masked band's scan for block offsets has failed, the general discovery takes the bands
@@ -176,6 +180,8 @@ private:
   hipStream_t m_stream = nullptr, m_userStream = nullptr;
   bool m_userSet = false;
   u8* m_slab = nullptr;
+  u8* m_rasterStage = nullptr;
+  size_t m_rasterStageCap = 0;
   size_t m_cap = 0, m_used = 0;
   void* m_pinned = nullptr;
   size_t m_pinnedCap = 0;
@@ -306,6 +312,24 @@ bool tilesBytesEncodeEligible(const TilesEncodeRequest& rq);
 bool tilesBytesDecodeEligible(const TilesDecodeRequest& rq);
 u32 encodeTilesBytes(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed);
 u32 decodeTilesBytes(Context& ctx, const TilesDecodeRequest& rq);
+
+// ---- a pitched device raster cut into a grid of tiles, every tile a blob (codec_raster_tiles.cpp, raster_tiles.hip): per shape class
+// of the grid (interior, right column, bottom row, corner) the tiles are staged as [n][nBands][r][c] and handed to the calls above
+struct RasterTilesRequest
+{
+  void* dRaster = nullptr;            // device: nBands planes of nRows rows, pitched (encode: read only)
+  u8* dValidBytes = nullptr;          // device: one byte mask [nRows][maskRowPitch] for the raster (nMasks == 1), or nullptr
+  int dt = 0, nCols = 0, nRows = 0, nBands = 1, nMasks = 0, tileCols = 0, tileRows = 0;
+  u64 rowPitch = 0, bandPitch = 0, maskRowPitch = 0;    // in elements
+  u8* dArena = nullptr;               // device (decode: read only)
+  u64* hOffsets = nullptr;            // host [nTY * nTX], tile (ty, tx) at ty * nTX + tx
+  u32* hSizes = nullptr;
+  // encode only
+  double maxZErr = 0;
+  u64 arenaCapacity = 0, slotBytes = 0;
+};
+u32 encodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq, u64& arenaUsed);
+u32 decodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq);
 
 // header-only queries (host)
 struct BlobInfo

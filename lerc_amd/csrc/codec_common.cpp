@@ -365,6 +365,7 @@ Context::Context()
 Context::~Context()
 {
   if (m_slab) hipFree(m_slab);
+  if (m_rasterStage) hipFree(m_rasterStage);
   if (m_pinned) hipHostFree(m_pinned);
   if (m_pinnedAux) hipHostFree(m_pinnedAux);
   if (m_asyncPinned) hipHostFree(m_asyncPinned);
@@ -458,6 +459,15 @@ void* Context::pinnedAux(size_t bytes)
   if (hipHostMalloc(&m_pinnedAux, bytes + 4096, hipHostMallocDefault) != hipSuccess) return nullptr;
   m_pinnedAuxCap = bytes + 4096;
   return m_pinnedAux;
+}
+
+u8* Context::rasterStage(size_t bytes)
+{
+  if (bytes <= m_rasterStageCap) return m_rasterStage;
+  if (m_rasterStage) { hipStreamSynchronize(activeStream()); hipFree(m_rasterStage); m_rasterStage = nullptr; m_rasterStageCap = 0; }
+  if (hipMalloc((void**)&m_rasterStage, bytes + 256) != hipSuccess) { lastError = "lerc_amd: hipMalloc failed (raster tile staging)"; return nullptr; }
+  m_rasterStageCap = bytes + 256;
+  return m_rasterStage;
 }
 
 hipStream_t Context::forkSide()

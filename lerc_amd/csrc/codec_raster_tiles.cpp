@@ -1,0 +1,253 @@
+// codec_raster_tiles.cpp -- a pitched device raster in, a grid of tile blobs out, and back (lerc_amd_encode_raster_tiles_device /
+// lerc_amd_decode_raster_tiles_device).  The reference has no counterpart: a tiled-LERC writer (MRF, a tile cache) cuts the raster on
+// the host and calls lerc_encode per tile.
+//
+// A grid has at most four shape classes -- interior, right column, bottom row, corner --, and a class is a mosaic of one shape, which
+// is what the tile batch calls take.  Per class, in chunks that fit the staging buffer: k_rt_cut gathers the chunk's rectangles into
+// [n][nBands][r][c] (the mask's into [n][r][c]), the chunk goes to encodeTilesDevice (one band, no mask: the one-launch tile encoder),
+// encodeTilesDeviceMasked (one band, a mask) or encodeTilesDeviceBands with the arena pointed at the bytes still free (the class's run
+// of rooms, if slotted), and its offsets and sizes are scattered into the caller's arrays by tile index.  The way back gathers the
+// tables, decodes into the staging buffer and pastes.  Size limits, hand-backs, notes, lerc_amd_tile_batch_counters and the status of a
+// failing tile are those calls' own.  Tiles that lie as [n][r][c] already (one band, a tile as wide as the raster, no padding) are handed
+// over where they lie.
+#include "codec.h"
+#include "raster_tiles.h"
+
+#include <algorithm>
+#include <cstdlib>
+
+namespace lerc {
+
+// the staging buffer's cap (like kTbWorkspace of the tile batches): a class larger than that goes in several chunks
+static const size_t kRtStageBytes = (size_t)256 << 20;
+
+namespace {
+
+struct RtClass { u32 ty0, tx0, nTY, nTX, r, c; u64 tiles() const { return (u64)nTY * nTX; } };
+
+struct RtGrid
+{
+  u32 nTY = 0, nTX = 0;
+  std::vector<RtClass> classes;
+  bool inPlace = false;
+  u64 nTiles() const { return (u64)nTY * nTX; }
+};
+
+bool rtArgsOk(const RasterTilesRequest& rq, bool encode)
+{
+  if (!rq.dRaster || !rq.dArena || !rq.hOffsets || !rq.hSizes || rq.dt < 0 || rq.dt > DT_Double || rq.nCols <= 0 || rq.nRows <= 0 || rq.nBands <= 0
+    || rq.tileCols <= 0 || rq.tileRows <= 0 || (rq.nMasks != 0 && rq.nMasks != 1) || (rq.nMasks == 0) != (rq.dValidBytes == nullptr))
+    return false;
+  if (rq.rowPitch < (u64)rq.nCols || (rq.nMasks && rq.maskRowPitch < (u64)rq.nCols)) return false;
+  if (rq.nBands > 1 && rq.bandPitch < (u64)(rq.nRows - 1) * rq.rowPitch + (u64)rq.nCols) return false;
+  if (((uintptr_t)rq.dRaster & (uintptr_t)(dtSize(rq.dt) - 1)) != 0) return false;    // (elements lie on their own boundaries)
+  if (encode && (rq.maxZErr < 0 || (rq.slotBytes & 15u) != 0)) return false;
+  return true;
+}
+
+RtGrid rtGrid(const RasterTilesRequest& rq)
+{
+  RtGrid g;
+  const u32 tr = (u32)rq.tileRows, tc = (u32)rq.tileCols, nR = (u32)rq.nRows, nC = (u32)rq.nCols;
+  const u32 fullY = nR / tr, fullX = nC / tc, remR = nR % tr, remC = nC % tc;
+  g.nTY = fullY + (remR ? 1 : 0); g.nTX = fullX + (remC ? 1 : 0);
+  if (fullY && fullX) g.classes.push_back({ 0, 0, fullY, fullX, tr, tc });
+  if (fullY && remC) g.classes.push_back({ 0, fullX, fullY, 1, tr, remC });
+  if (remR && fullX) g.classes.push_back({ fullY, 0, 1, fullX, remR, tc });
+  if (remR && remC) g.classes.push_back({ fullY, fullX, 1, 1, remR, remC });
+  g.inPlace = rq.nBands == 1 && tc >= nC && rq.rowPitch == (u64)nC && (!rq.nMasks || rq.maskRowPitch == (u64)nC);
+  return g;
+}
+
+struct RtStagePlan { size_t dataPerTile, maskPerTile; u32 maxChunk; };
+
+// tiles a chunk: what fits the cap (one at least); LERC_AMD_TEST_RASTER_CHUNK=n (tests only, read per call) makes it n
+RtStagePlan rtPlan(const RasterTilesRequest& rq, const RtClass& k)
+{
+  RtStagePlan p;
+  const size_t pix = (size_t)k.r * k.c;
+  p.dataPerTile = pix * (size_t)rq.nBands * (size_t)dtSize(rq.dt);
+  p.maskPerTile = rq.nMasks ? pix : 0;
+  size_t most = std::max<size_t>(1, kRtStageBytes / (p.dataPerTile + p.maskPerTile));
+  const char* e = getenv("LERC_AMD_TEST_RASTER_CHUNK");
+  const long knob = e ? strtol(e, nullptr, 0) : 0;
+  if (knob >= 1) most = std::min<size_t>(most, (size_t)knob);
+  p.maxChunk = (u32)std::min<u64>(std::min<u64>(k.tiles(), most), 0x7FFFFFFFu);
+  return p;
+}
+
+size_t rtMaskAt(const RtStagePlan& p, u32 n) { return ((size_t)n * p.dataPerTile + 255) & ~(size_t)255; }
+
+// the staging buffer for the largest chunk of the call, allocated once (growing it later would wait for the stream)
+u8* rtStageFor(Context& ctx, const RasterTilesRequest& rq, const RtGrid& g)
+{
+  size_t need = 0;
+  for (const RtClass& k : g.classes)
+  {
+    const RtStagePlan p = rtPlan(rq, k);
+    need = std::max(need, rtMaskAt(p, p.maxChunk) + (size_t)p.maxChunk * p.maskPerTile);
+  }
+  return ctx.rasterStage(need);
+}
+
+RtChunk rtChunk(const RasterTilesRequest& rq, const RtClass& k, u32 k0, u32 n, bool mask)
+{
+  RtChunk ch;
+  ch.rowPitch = mask ? rq.maskRowPitch : rq.rowPitch; ch.bandPitch = mask ? 0 : rq.bandPitch;
+  ch.tileRows = (u32)rq.tileRows; ch.tileCols = (u32)rq.tileCols; ch.r = k.r; ch.c = k.c;
+  ch.ty0 = k.ty0; ch.tx0 = k.tx0; ch.classW = k.nTX; ch.k0 = k0; ch.n = n; ch.nBands = mask ? 1u : (u32)rq.nBands;
+  return ch;
+}
+
+size_t rtTileIndex(const RtGrid& g, const RtClass& k, u32 i) { return (size_t)(k.ty0 + i / k.nTX) * g.nTX + (k.tx0 + i % k.nTX); }
+
+}    // namespace
+
+u32 encodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq, u64& arenaUsed)
+{
+  arenaUsed = 0;
+  if (!rtArgsOk(rq, true)) return kWrongParam;
+  const RtGrid g = rtGrid(rq);
+  if (g.nTiles() > 0x7FFFFFFFull) return kDimsTooLarge;
+  const bool slotted = rq.slotBytes != 0;
+  if (slotted && rq.arenaCapacity < g.nTiles() * rq.slotBytes) return kBufferTooSmall;
+  const u32 eb = (u32)dtSize(rq.dt);
+  hipStream_t st = ctx.activeStream();
+  u8* stage = g.inPlace ? nullptr : rtStageFor(ctx, rq, g);
+  if (!g.inPlace && !stage) return kFailed;
+
+  u64 base = 0, room = 0;    // packed: arena bytes in use; slotted: rooms handed out
+  std::vector<u64> offs;
+  std::vector<u32> sizes;
+  for (const RtClass& k : g.classes)
+  {
+    const RtStagePlan p = rtPlan(rq, k);
+    const u32 nClass = (u32)k.tiles(), step = g.inPlace ? nClass : p.maxChunk;
+    for (u32 k0 = 0; k0 < nClass; k0 += step)
+    {
+      const u32 n = std::min(step, nClass - k0);
+      TilesEncodeRequest sub;
+      if (g.inPlace)
+      {
+        // (tiles as wide as the raster: the class is a run of rows, [n][r][c] as it lies)
+        const u64 first = (u64)k.ty0 * (u64)rq.tileRows * (u64)rq.nCols;
+        sub.dData = (const u8*)rq.dRaster + first * eb;
+        sub.dValidBytes = rq.nMasks ? rq.dValidBytes + first : nullptr;
+        ctx.rasterTilesCount[1] += n;
+      }
+      else
+      {
+        (void)hipGetLastError();
+        launchRasterCut(rq.dRaster, stage, rtChunk(rq, k, k0, n, false), eb, st);
+        if (rq.nMasks) launchRasterCut(rq.dValidBytes, stage + rtMaskAt(p, n), rtChunk(rq, k, k0, n, true), 1, st);
+        if (hipGetLastError() != hipSuccess) { ctx.lastError = "lerc_amd: the raster cut kernel could not be launched"; return kFailed; }
+        sub.dData = stage;
+        sub.dValidBytes = rq.nMasks ? stage + rtMaskAt(p, n) : nullptr;
+        ctx.rasterTilesCount[0] += n;
+      }
+      offs.assign(n, 0); sizes.assign(n, 0);
+      sub.dt = rq.dt; sub.nCols = (int)k.c; sub.nRows = (int)k.r; sub.nTiles = (int)n; sub.maxZErr = rq.maxZErr;
+      sub.hOffsets = offs.data(); sub.hSizes = sizes.data(); sub.slotBytes = rq.slotBytes;
+      if (slotted) { base = room * rq.slotBytes; sub.arenaCapacity = (u64)n * rq.slotBytes; }
+      else
+      {
+        base = (base + 15) & ~15ull;
+        if (base >= rq.arenaCapacity) return kBufferTooSmall;
+        sub.arenaCapacity = rq.arenaCapacity - base;
+      }
+      sub.dArena = rq.dArena + base;
+      u64 used = 0;
+      u32 rc;
+      if (rq.nBands == 1) rc = rq.nMasks ? encodeTilesDeviceMasked(ctx, sub, used) : encodeTilesDevice(ctx, sub, used);
+      else { sub.nBands = rq.nBands; sub.nMasks = rq.nMasks; rc = encodeTilesDeviceBands(ctx, sub, used); }
+      if (rc != kOk) return rc;
+      for (u32 i = 0; i < n; i++)
+      {
+        const size_t t = rtTileIndex(g, k, k0 + i);
+        rq.hOffsets[t] = base + (slotted ? (u64)i * rq.slotBytes : offs[i]);
+        rq.hSizes[t] = sizes[i];
+      }
+      if (slotted) room += n; else base += used;
+    }
+  }
+  arenaUsed = slotted ? g.nTiles() * rq.slotBytes : base;
+  return kOk;
+}
+
+u32 decodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq)
+{
+  if (!rtArgsOk(rq, false)) return kWrongParam;
+  const RtGrid g = rtGrid(rq);
+  if (g.nTiles() > 0x7FFFFFFFull) return kDimsTooLarge;
+  const u32 eb = (u32)dtSize(rq.dt);
+  u8* stage = g.inPlace ? nullptr : rtStageFor(ctx, rq, g);
+  if (!g.inPlace && !stage) return kFailed;
+
+  u32 firstError = kOk;
+  std::vector<u64> offs;
+  std::vector<u32> sizes;
+  for (const RtClass& k : g.classes)
+  {
+    const RtStagePlan p = rtPlan(rq, k);
+    const u32 nClass = (u32)k.tiles(), step = g.inPlace ? nClass : p.maxChunk;
+    for (u32 k0 = 0; k0 < nClass; k0 += step)
+    {
+      const u32 n = std::min(step, nClass - k0);
+      offs.resize(n); sizes.resize(n);
+      for (u32 i = 0; i < n; i++) { const size_t t = rtTileIndex(g, k, k0 + i); offs[i] = rq.hOffsets[t]; sizes[i] = rq.hSizes[t]; }
+      TilesDecodeRequest sub;
+      sub.dArena = rq.dArena; sub.hOffsets = offs.data(); sub.hSizes = sizes.data();
+      sub.dt = rq.dt; sub.nCols = (int)k.c; sub.nRows = (int)k.r; sub.nTiles = (int)n;
+      if (g.inPlace)
+      {
+        const u64 first = (u64)k.ty0 * (u64)rq.tileRows * (u64)rq.nCols;
+        sub.dOut = (u8*)rq.dRaster + first * eb;
+        sub.dValidBytes = rq.nMasks ? rq.dValidBytes + first : nullptr;
+        ctx.rasterTilesCount[3] += n;
+      }
+      else
+      {
+        sub.dOut = stage;
+        sub.dValidBytes = rq.nMasks ? stage + rtMaskAt(p, n) : nullptr;
+        ctx.rasterTilesCount[2] += n;
+      }
+      u32 rc;
+      if (rq.nBands > 1) { sub.nBands = rq.nBands; sub.nMasks = rq.nMasks; rc = decodeTilesDeviceBands(ctx, sub); }
+      else if (rq.nMasks) rc = decodeTilesDeviceMasked(ctx, sub);
+      else
+      {
+        rc = decodeTilesDevice(ctx, sub);
+        if (rc != kOk)
+        {
+          // (the plain call stops at the tile that fails: here every tile is decoded all the same, so the chunk goes once more, tile
+          // by tile, and a tile that fails is left zeroed)
+          rc = kOk;
+          const size_t tileBytes = (size_t)k.r * k.c * eb;
+          for (u32 i = 0; i < n; i++)
+          {
+            TilesDecodeRequest one = sub;
+            one.hOffsets = offs.data() + i; one.hSizes = sizes.data() + i; one.nTiles = 1;
+            one.dOut = (u8*)sub.dOut + (size_t)i * tileBytes;
+            const u32 rc1 = decodeTilesDevice(ctx, one);
+            if (rc1 == kOk) continue;
+            hipMemsetAsync(one.dOut, 0, tileBytes, ctx.activeStream());
+            if (rc == kOk) rc = rc1;
+          }
+        }
+      }
+      if (rc != kOk && firstError == kOk) firstError = rc;
+      if (!g.inPlace)
+      {
+        hipStream_t st = ctx.activeStream();
+        (void)hipGetLastError();
+        launchRasterPaste(stage, rq.dRaster, rtChunk(rq, k, k0, n, false), eb, st);
+        if (rq.nMasks) launchRasterPaste(stage + rtMaskAt(p, n), rq.dValidBytes, rtChunk(rq, k, k0, n, true), 1, st);
+        if (hipGetLastError() != hipSuccess) { ctx.lastError = "lerc_amd: the raster paste kernel could not be launched"; return kFailed; }
+      }
+    }
+  }
+  if (!ctx.sync()) return kFailed;    // (the pastes: the raster is the caller's when the call returns)
+  return firstError;
+}
+
+}    // namespace lerc

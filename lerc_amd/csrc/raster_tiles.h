@@ -1,0 +1,34 @@
+// raster_tiles.h -- a pitched device raster cut into tiles and pasted back (raster_tiles.hip, codec_raster_tiles.cpp): the staging
+// pass in front of / behind the tile batch calls, which take tiles of one shape laid out as [n][nBands][r][c].
+#pragma once
+#include "lerc_common.h"
+
+namespace lerc {
+
+// One shape class of a tile grid (interior, right column, bottom row, corner): a rectangle of the grid whose tiles all are r x c.
+// Its tiles are numbered row by row inside the class; a launch moves tiles [k0, k0 + n) of it.
+struct RtChunk
+{
+  u64 rowPitch, bandPitch;    // of the raster, in elements (the mask: its own row pitch, nBands 1)
+  u32 tileRows, tileCols;     // the grid's steps
+  u32 r, c;                   // the class's tile shape (r <= tileRows, c <= tileCols)
+  u32 ty0, tx0, classW;       // the class's first tile row / column in the grid, and how many tiles wide it is
+  u32 k0, n;                  // the chunk: tiles of the class
+  u32 nBands;
+};
+
+// the rows of a plane a workgroup takes (at least: a workgroup of short rows takes as many as it has lanes for), and how many lanes run along one row (a power of two, 8 .. 64: a lane moves 16 bytes a step)
+static const u32 kRtStripRows = 16;
+inline u32 rtLanesPerRowLog2(u32 c, u32 elemBytes)
+{
+  const u64 vecs = ((u64)c * elemBytes + 15) / 16 + 1;    // (+ 1: a row that begins inside a vector)
+  u32 lg = 3;
+  while (lg < 6 && (1ull << lg) < vecs) lg++;
+  return lg;
+}
+
+// staging <- raster (cut) and raster <- staging (paste); elemBytes 1, 2, 4 or 8; both pointers aligned to the element.  One launch.
+void launchRasterCut(const void* dRaster, void* dStage, const RtChunk& ch, u32 elemBytes, hipStream_t st);
+void launchRasterPaste(const void* dStage, void* dRaster, const RtChunk& ch, u32 elemBytes, hipStream_t st);
+
+}    // namespace lerc

@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""Times the raster tile calls (lerc_amd_encode_raster_tiles_device / lerc_amd_decode_raster_tiles_device) against the tile calls
+they are built on, to learn what the staging pass -- k_rt_cut in front of the encode, k_rt_paste behind the decode -- costs.  One
+MI355X, everything device resident, float32 (synth.c2_float32) at MaxZError 0.01, tiles of 256 x 256, packed arenas, two rasters:
+
+  8192 x 8192    1024 tiles, one shape class
+  8190 x 8190    961 interior tiles and three edge classes (254 columns, 254 rows, the corner)
+
+Three things are timed on each:
+
+  (a) the raster calls on the raster as it lies
+  (b) lerc_amd_encode_tiles_device / lerc_amd_decode_tiles_device on the same tiles cut beforehand (the ragged raster: its
+      interior class only -- the edge classes are (a)'s alone, so (a) - (b) is an upper bound there)
+  (c) a plain device-to-device copy of the raster's bytes: what a pass that reads and writes them costs when nothing is strided
+
+(a) - (b) is the staging's cost.  Target: (a) - (b) <= 2 x (c) on the 8192^2 raster -- rows of 1 KiB instead of one long run, a launch
+per chunk, the records' round trip per class; beyond that the cut kernel is not streaming.
+
+Every call is queued on torch's current stream and timed with events around it; warm-up, then the median and the interquartile range
+of REPS (21) repetitions.  Prints the numbers (they are recorded in DESIGN.md 8.3); exit status 1 if the target is missed.  Run it under a time limit of its own:
+  timeout -k 10 600 python tools/time_raster_tiles.py
+"""
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+REPS = int(os.environ.get("REPS", "21"))
+TILE = 256
+E = 0.01
+
+
+def main():
+    import numpy as np
+    import torch
+    from lerc_amd import api, synth
+    assert torch.cuda.is_available(), "needs a GPU"
+
+    def timed(fn, reps=REPS, warm=3):
+        for _ in range(warm):
+            fn()
+        ms = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            ms.append(a.elapsed_time(b))
+        q = statistics.quantiles(ms, n=4)
+        return statistics.median(ms), q[2] - q[0]
+
+    codec = api.DeviceCodec(torch.cuda.current_stream().cuda_stream)
+    print("raster tile calls against the tile calls -- %s; float32 at %.2f, tiles of %d x %d; median [interquartile range] of %d, ms"
+          % (torch.cuda.get_device_name(0), E, TILE, TILE, REPS))
+    ok = True
+    for size in (8192, 8190):
+        raster = synth.c2_float32(size, size, device="cuda:0")
+        grid = api.raster_tile_grid(size, size, (TILE, TILE))
+        n = len(grid)
+        arena = torch.zeros(n * (TILE * TILE * 4 + TILE * TILE // 4 + 1024 + 16), dtype=torch.uint8, device="cuda")
+        back = torch.zeros_like(raster)
+        state = {}
+
+        def enc_a():
+            rc, offs, sizes, used = api.encode_raster_tiles_device(codec, raster, None, E, (TILE, TILE), arena)
+            assert rc == 0, (rc, codec.last_error())
+            state["a"] = (offs, sizes)
+
+        def dec_a():
+            assert api.decode_raster_tiles_device(codec, arena, state["a"][0], state["a"][1], back, None, (TILE, TILE)) == 0
+
+        r0, b0 = codec.raster_tiles_counters(), codec.tile_batch_counters()
+        enc_a()
+        dec_a()
+        torch.cuda.synchronize()
+        r1, b1 = codec.raster_tiles_counters(), codec.tile_batch_counters()
+        err = float((back.double() - raster.double()).abs().max())
+        assert err <= E + 1e-4, err
+        a_enc, a_dec = timed(enc_a), timed(dec_a)
+
+        full = size // TILE
+        tiles = raster[:full * TILE, :full * TILE].reshape(full, TILE, full, TILE).permute(0, 2, 1, 3).contiguous().reshape(full * full, TILE, TILE)
+        tiles_back = torch.zeros_like(tiles)
+
+        def enc_b():
+            rc, offs, sizes, used = api.encode_tiles_device(codec, tiles, E, arena)
+            assert rc == 0, (rc, codec.last_error())
+            state["b"] = (offs, sizes)
+
+        def dec_b():
+            assert api.decode_tiles_device(codec, arena, state["b"][0], state["b"][1], tiles_back) == 0
+
+        enc_b()
+        dec_b()
+        b_enc, b_dec = timed(enc_b), timed(dec_b)
+
+        def copy_c():
+            back.copy_(raster)
+
+        c = timed(copy_c)
+        print("%d x %d: %d tiles (%d interior); raster call counters [cut, in place, pasted, in place] %s, tile batch counters %s; max error %.6f"
+              % (size, size, n, full * full, [int(y - x) for x, y in zip(r0, r1)], [int(y - x) for x, y in zip(b0, b1)], err))
+        print("  (a) raster calls            encode %8.3f [%6.3f]   decode %8.3f [%6.3f]" % (a_enc + a_dec))
+        print("  (b) tile calls, tiles cut   encode %8.3f [%6.3f]   decode %8.3f [%6.3f]" % (b_enc + b_dec))
+        print("  (c) device-to-device copy of %.0f MiB   %8.3f [%6.3f]   (%.0f GB/s read + written)"
+              % (raster.numel() * 4 / 2 ** 20, c[0], c[1], 2 * raster.numel() * 4 / c[0] / 1e6))
+        for what, a, b in (("encode", a_enc[0], b_enc[0]), ("decode", a_dec[0], b_dec[0])):
+            met = a - b <= 2 * c[0]
+            print("  %s: (a) - (b) = %7.3f ms = %.2f x (c)%s" % (what, a - b, (a - b) / c[0],
+                                                               "   target 2 x (c): %s" % ("met" if met else "NOT met") if size == 8192 else ""))
+            if size == 8192:
+                ok = ok and met
+        del raster, arena, back, tiles, tiles_back
+        torch.cuda.empty_cache()
+    codec.close()
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
