@@ -2,7 +2,8 @@
 // workgroup of 256 threads that owns one tile needs: sums, Fletcher32 over a finished blob, an exclusive scan in place, the codec 6
 // header to and from bytes, the blobs' places in a packed arena, the walk over a tile's block headers, and a tile's mask (byte mask to
 // bit mask, its run-length stream each way, counts, ranks, header and mask section written).  And what a wave that owns one
-// block needs: the block encoder's and the block decoder's body.  Every piece of LDS is handed in by the kernel that owns it.
+// block needs: the block encoder's body, a composition of the stages the general kernel uses (tile_encode_dev.h), and the
+// block decoder's body.  Every piece of LDS is handed in by the kernel that owns it.
 #pragma once
 #include "lerc_common.h"
 #include "wave_utils.h"
@@ -424,8 +425,8 @@ __device__ __forceinline__ u32 tbWalkBlocks(const u8* __restrict__ blob, u32 beg
   return fl;
 }
 
-// ---- the block encoder's wave body: k_encode_tiles (tile_encode.hip) for one value a pixel and a tile of a batch.  The wave owns block
-// pos of the tile px (p: the tile's nRows, nCols, nTH, block size, error bound); lane l holds elements l, l + 64, ... of the block.
+// ---- the block encoder's wave body for one value a pixel and a tile of a batch: the stages of tile_encode_dev.h.  The wave owns block
+// pos of the tile px (p: the tile's nRows, nCols, nTH, block size, error bound).
 // MASKED: maskBits says which pixels are valid unless p.allValid, and the error bound may be any; else every pixel is valid and the
 // tile lossless (p.maxZErr 0.5, p.intLossless).  WRITE: the block's bytes go to data + table[pos] (data: where the tile's block stream
 // begins); else its size goes to table[pos].  LDS of the wave: valBuf E * 64 values; WRITE: obuf (1 + E * 64 * sizeof(T) + 3) / 4 + 4
@@ -434,102 +435,23 @@ template<class T, int E, bool MASKED, bool WRITE>
 __device__ __forceinline__ void tbEncodeBlock(const BandParams& p, int pos, const T* __restrict__ px, const u8* __restrict__ maskBits,
                                               u32* __restrict__ table, u8* __restrict__ data, T* valBuf, u32* obuf, u32* lutBuf)
 {
-  constexpr int MB = E == 1 ? 8 : 16;
   const int lane = laneId();
-  const int it = pos / p.nTH, jt = pos - it * p.nTH;
-  const int i0 = it * MB, j0 = jt * MB;
-  const int tileH = min(MB, p.nRows - i0), tileW = min(MB, p.nCols - j0);
-  const int nElem = tileH * tileW;
-  const bool allValid = !MASKED || p.allValid;
-
-  int rank[E];
-  i64 pix[E];
-  T v[E];
-  u32 q[E];
-  int n = MASKED ? 0 : nElem;
-#pragma unroll
-  for (int k = 0; k < E; k++)
+  const BlockLanes<E> L = blockLanes<E, MASKED>(p, pos, maskBits);
+  if (MASKED && L.n == 0)
   {
-    const int e = k * 64 + lane;
-    const bool inb = e < nElem;
-    const int r = inb ? e / tileW : 0, c = inb ? e - r * tileW : 0;
-    pix[k] = (i64)(i0 + r) * p.nCols + (j0 + c);
-    if (MASKED)
-    {
-      const bool valid = inb && (p.allValid || maskBit(maskBits, pix[k]));
-      const u64 bal = __ballot(valid);
-      rank[k] = valid ? n + __popcll(bal & laneMaskLt()) : -1;
-      n += __popcll(bal);
-    }
-    else rank[k] = inb ? e : -1;
-  }
-
-  if (MASKED && n == 0)    // empty position: one "all zero" byte (Lerc2.cpp:1534-1538, :1960-1966)
-  {
-    if (WRITE) { if (lane == 0) data[table[pos]] = (u8)(((u32)(((j0 >> 3) & 15) << 2) & 0x38u) | 2u); }
+    if (WRITE) { if (lane == 0) data[table[pos]] = emptyBlockByte(p, L.j0); }
     else if (lane == 0) table[pos] = 1u;
     return;
   }
-#pragma unroll
-  for (int k = 0; k < E; k++)
-  {
-    v[k] = T(0);
-    if (rank[k] >= 0) { v[k] = px[pix[k]]; valBuf[rank[k]] = v[k]; }
-  }
-  waveSync();
+  T v[E];
+  gatherSlice<T, E>(L, px, 1, 0, valBuf, v);
+  const SliceCode<T, E> s = analyseSlice<T, E>(p, L.n, v, L.rank, valBuf, p.dt, !MASKED || p.allValid, !MASKED || p.maxZErr > 0, !MASKED || p.intLossless);
+  if (!WRITE) { if (lane == 0) table[pos] = (u32)s.plan.nBytes; return; }
 
-  // --- statistics (GetValidDataAndStats)
-  T mn = valBuf[0], mx = valBuf[0];
-#pragma unroll
-  for (int k = 0; k < E; k++)
-    if (rank[k] >= 0) { mn = (v[k] < mn) ? v[k] : mn; mx = (v[k] > mx) ? v[k] : mx; }
-  mn = waveMinT(mn);
-  mx = waveMaxT(mx);
-  int same = 0;
-#pragma unroll
-  for (int k = 0; k < E; k++)
-  {
-    bool s = false;
-    if (rank[k] > 0) s = (v[k] == valBuf[rank[k] - 1]);
-    else if (rank[k] == 0) s = allValid ? (v[k] == T(0)) : false;    // prevVal starts at 0 (all-valid branch only)
-    same += __popcll(__ballot(s));
-  }
-  const bool tryLut = (n > 4) && ((double)mx > (double)mn + 3 * p.maxZErr) && (2 * same > n);
-
-  double mv = 0;
-  bool quantOk = false;
-  if (!MASKED || p.maxZErr > 0)    // (not MASKED: 0.5)
-  {
-    mv = ((double)mx - (double)mn) * p.scale;
-    quantOk = !(mv > (double)p.maxQ || (u32)(mv + 0.5) == 0);
-  }
-  u32 qMax = 0;
-#pragma unroll
-  for (int k = 0; k < E; k++) q[k] = 0;
-  if (quantOk)
-  {
-#pragma unroll
-    for (int k = 0; k < E; k++)
-      if (rank[k] >= 0)
-      {
-        q[k] = (!MASKED || p.intLossless) ? quantLossless<T>(v[k], mn) : (u32)(((double)v[k] - (double)mn) * p.scale + 0.5);
-        qMax = q[k] > qMax ? q[k] : qMax;
-      }
-    qMax = waveMax(qMax);
-  }
-  u32 nDistinct = 0;
-  if (tryLut && quantOk)
-  {
-    u32 idxTmp[E];
-    nDistinct = extractDistinct<E>(q, rank, nullptr, idxTmp);
-  }
-  const Plan plan = planBlock<T>(p, n, mn, mx, p.dt, tryLut, mv, qMax, nDistinct);
-  if (!WRITE) { if (lane == 0) table[pos] = (u32)plan.nBytes; return; }
-
-  composeBlock<T, E>(obuf, lutBuf, p, plan, n, j0, false, mn, v, q, rank, qMax);
+  composeBlock<T, E>(obuf, lutBuf, p, s.plan, L.n, L.j0, false, s.zMin, v, s.q, L.rank, s.qMax);
   const u8* ob8 = reinterpret_cast<const u8*>(obuf);
   u8* __restrict__ dst = data + table[pos];
-  for (int i = lane; i < plan.nBytes; i += 64) dst[i] = ob8[i];
+  for (int i = lane; i < s.plan.nBytes; i += 64) dst[i] = ob8[i];
 }
 
 // ---- the block decoder's wave body: k_decode_tiles (tile_decode.hip) for one value a pixel and a tile of a batch.  The wave owns block

@@ -11,15 +11,19 @@
 //   * workgroup = 4 waves, wave w handles block position 4 * blockIdx.x + w, all depth slices in turn
 //   * lane l holds elements l, l + 64, ... of the block in row-major order; valid elements are
 //     compacted with __ballot / __popcll so that "rank" equals the reference's dataBuf index
+//     (blockLanes, tile_encode_dev.h)
 //   * min / max / same-as-previous counts are wave reductions; the bit width comes from the clz of
-//     the quantised maximum; packing ORs each element's bits into an LDS image of the block
-//     (ds_or_b32, at most two per element), which is then copied to the blob with coalesced stores
+//     the quantised maximum (analyseSlice, once for a slice's values and once for their differences
+//     to the previous slice); packing ORs each element's bits into an LDS image of the block
+//     (composeBlock: ds_or_b32, at most two per element), which is then copied to the blob with
+//     coalesced stores
 //   * all control flow around cross-lane operations is wave-uniform
 //
 // FP parity: the quantiser is evaluated in double precision in the reference's
 // expression order; this file must be compiled with -ffp-contract=off.
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 #include "kernels.h"
 #include "wave_utils.h"
@@ -43,29 +47,9 @@ k_encode_tiles(const T* __restrict__ data, const u8* __restrict__ maskBits, Band
   const int w = waveId(), lane = laneId();
   const int pos = (int)blockIdx.x * 4 + w;
   if (pos >= p.nTV * p.nTH) return;    // whole wave leaves together
-  const int it = pos / p.nTH, jt = pos - it * p.nTH;
-  const int i0 = it * MB, j0 = jt * MB;
-  const int tileH = min(MB, p.nRows - i0), tileW = min(MB, p.nCols - j0);
-  const int nElem = tileH * tileW;
   const int nD = p.nDepth;
-  const u64 lt = laneMaskLt();
-
-  // --- which elements are valid, and their rank in the reference's row-major gather order
-  int rank[E];
-  i64 pix[E];
-  int n = 0;
-#pragma unroll
-  for (int k = 0; k < E; k++)
-  {
-    const int e = k * 64 + lane;
-    const bool inb = e < nElem;
-    const int r = inb ? e / tileW : 0, c = inb ? e - r * tileW : 0;
-    pix[k] = (i64)(i0 + r) * p.nCols + (j0 + c);
-    const bool valid = inb && (p.allValid || maskBit(maskBits, pix[k]));
-    const u64 bal = __ballot(valid);
-    rank[k] = valid ? n + __popcll(bal & lt) : -1;
-    n += __popcll(bal);
-  }
+  const BlockLanes<E> L = blockLanes<E, true>(p, pos, maskBits);
+  const int n = L.n;
 
   u32 total = 0;
   u32 outOff = 0;
@@ -78,146 +62,55 @@ k_encode_tiles(const T* __restrict__ data, const u8* __restrict__ maskBits, Band
     T* valBuf = s_val[cur][w];
     const T* prevBuf = s_val[cur ^ 1][w];
 
-    if (n == 0)    // empty position: one "all zero" byte per slice (Lerc2.cpp:1534-1538, :1960-1966)
+    if (n == 0)    // empty position: one "all zero" byte per slice
     {
-      if (WRITE && lane == 0)
-      {
-        u32 flag = (u32)(((j0 >> 3) & 15) << 2);
-        if (p.version >= 5) flag &= 0x38u;
-        out[outOff] = (u8)(flag | 2u);
-      }
+      if (WRITE && lane == 0) out[outOff] = emptyBlockByte(p, L.j0);
       outOff += 1; total += 1;
       continue;
     }
 
-    // --- gather this slice
     T v[E];
-#pragma unroll
-    for (int k = 0; k < E; k++)
-    {
-      v[k] = T(0);
-      if (rank[k] >= 0) { v[k] = data[pix[k] * nD + iD]; valBuf[rank[k]] = v[k]; }
-    }
-    waveSync();
+    gatherSlice<T, E>(L, data, nD, iD, valBuf, v);
+    const SliceCode<T, E> sv = analyseSlice<T, E>(p, n, v, L.rank, valBuf, p.dt, p.allValid != 0, p.maxZErr > 0, p.intLossless != 0);
 
-    // --- statistics (GetValidDataAndStats)
-    T mn = valBuf[0], mx = valBuf[0];
-#pragma unroll
-    for (int k = 0; k < E; k++)
-      if (rank[k] >= 0) { mn = (v[k] < mn) ? v[k] : mn; mx = (v[k] > mx) ? v[k] : mx; }
-    mn = waveMinT(mn);
-    mx = waveMaxT(mx);
-    int same = 0;
-#pragma unroll
-    for (int k = 0; k < E; k++)
-    {
-      bool s = false;
-      if (rank[k] > 0) s = (v[k] == valBuf[rank[k] - 1]);
-      else if (rank[k] == 0) s = p.allValid ? (v[k] == T(0)) : false;    // prevVal starts at 0 (all-valid branch only)
-      same += __popcll(__ballot(s));
-    }
-    const bool tryLut = (n > 4) && ((double)mx > (double)mn + 3 * p.maxZErr) && (2 * same > n);
-
-    double mv = 0;
-    bool quantOk = false;
-    if (p.maxZErr > 0)
-    {
-      mv = ((double)mx - (double)mn) * p.scale;
-      quantOk = !(mv > (double)p.maxQ || (u32)(mv + 0.5) == 0);
-    }
-    u32 q[E];
-    u32 qMax = 0;
-#pragma unroll
-    for (int k = 0; k < E; k++) q[k] = 0;
-    if (quantOk)
-    {
-      const double z0 = (double)mn;
-#pragma unroll
-      for (int k = 0; k < E; k++)
-        if (rank[k] >= 0)
-        {
-          q[k] = p.intLossless ? quantLossless<T>(v[k], mn) : (u32)(((double)v[k] - z0) * p.scale + 0.5);
-          qMax = q[k] > qMax ? q[k] : qMax;
-        }
-      qMax = waveMax(qMax);
-    }
-    u32 nDistinct = 0;
-    if (tryLut && quantOk)
-    {
-      u32 idxTmp[E];
-      nDistinct = extractDistinct<E>(q, rank, nullptr, idxTmp);
-    }
-    const Plan plan = planBlock<T>(p, n, mn, mx, p.dt, tryLut, mv, qMax, nDistinct);
-
-    // --- optional: difference to the previous depth slice (integer lossless only)
+    // --- optional: difference to the previous depth slice (integer lossless only: p.tryDiff says so, maxZErr is 0.5; the kernels
+    // of the float types carry none of it)
     bool useDiff = false;
-    Plan planD = plan;
-    int d[E], mnD = 0;
-    u32 qD[E], qMaxD = 0;
+    int d[E];
+    SliceCode<int, E> sd = {};
 #pragma unroll
-    for (int k = 0; k < E; k++) { d[k] = 0; qD[k] = 0; }
-    if (p.tryDiff && iD > 0)
+    for (int k = 0; k < E; k++) d[k] = 0;
+    if (std::is_integral<T>::value && p.tryDiff && iD > 0)
     {
       bool ovf = false;
 #pragma unroll
       for (int k = 0; k < E; k++)
-        if (rank[k] >= 0)
+        if (L.rank[k] >= 0)
         {
-          const T pv = prevBuf[rank[k]];
+          const T pv = prevBuf[L.rank[k]];
           if (!p.checkOverflow) d[k] = (int)((i64)(int)v[k] - (i64)(int)pv);
           else
           {
             const double z = (double)v[k] - (double)pv;
             if (z < -2147483648.0 || z > 2147483647.0) ovf = true; else d[k] = (int)z;
           }
-          s_diff[w][rank[k]] = d[k];
+          s_diff[w][L.rank[k]] = d[k];
         }
       waveSync();
       if (!__any(ovf))
       {
-        int lo = s_diff[w][0], hi = lo;
-#pragma unroll
-        for (int k = 0; k < E; k++)
-          if (rank[k] >= 0) { lo = d[k] < lo ? d[k] : lo; hi = d[k] > hi ? d[k] : hi; }
-        lo = waveMin(lo); hi = waveMax(hi);
-        mnD = lo;
-        int sameD = 0;
-#pragma unroll
-        for (int k = 0; k < E; k++)
-        {
-          bool s = false;
-          if (rank[k] > 0) s = (d[k] == s_diff[w][rank[k] - 1]);
-          else if (rank[k] == 0) s = (d[k] == 0);    // ComputeDiffSliceInt: prevVal(0) also for masked blocks
-          sameD += __popcll(__ballot(s));
-        }
-        const bool tryLutD = (n > 4) && ((double)hi > (double)lo + 3 * p.maxZErr) && (2 * sameD > n);
-        const double mvD = ((double)hi - (double)lo) * p.scale;
-        const bool quantOkD = !(mvD > (double)p.maxQ || (u32)(mvD + 0.5) == 0);
-        if (quantOkD)
-        {
-#pragma unroll
-          for (int k = 0; k < E; k++)
-            if (rank[k] >= 0) { qD[k] = (u32)((i64)d[k] - (i64)lo); qMaxD = qD[k] > qMaxD ? qD[k] : qMaxD; }
-          qMaxD = waveMax(qMaxD);
-        }
-        u32 nDistinctD = 0;
-        if (tryLutD && quantOkD)
-        {
-          u32 idxTmp[E];
-          nDistinctD = extractDistinct<E>(qD, rank, nullptr, idxTmp);
-        }
-        planD = planBlock<int>(p, n, lo, hi, DT_Int, tryLutD, mvD, qMaxD, nDistinctD);
-        useDiff = plan.nBytes > planD.nBytes;
+        sd = analyseSlice<int, E>(p, n, d, L.rank, s_diff[w], DT_Int, true, true, true);
+        useDiff = sv.plan.nBytes > sd.plan.nBytes;
       }
       waveSync();
     }
 
-    const int nBytes = useDiff ? planD.nBytes : plan.nBytes;
+    const int nBytes = useDiff ? sd.plan.nBytes : sv.plan.nBytes;
 
     if (WRITE)
     {
-      if (!useDiff) composeBlock<T, E>(obuf, s_lut[w], p, plan, n, j0, false, mn, v, q, rank, qMax);
-      else composeBlock<int, E>(obuf, s_lut[w], p, planD, n, j0, true, mnD, d, qD, rank, qMaxD);
+      if (!useDiff) composeBlock<T, E>(obuf, s_lut[w], p, sv.plan, n, L.j0, false, sv.zMin, v, sv.q, L.rank, sv.qMax);
+      else composeBlock<int, E>(obuf, s_lut[w], p, sd.plan, n, L.j0, true, sd.zMin, d, sd.q, L.rank, sd.qMax);
       const u8* ob8 = reinterpret_cast<const u8*>(obuf);
       for (int b = lane; b < nBytes; b += 64) out[outOff + b] = ob8[b];
       waveSync();

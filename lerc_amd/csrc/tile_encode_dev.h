@@ -1,4 +1,6 @@
-// tile_encode_dev.h -- device functions of the general block encoder (tile_encode.hip) that other kernels share: the byte image of one block.
+// tile_encode_dev.h -- the stages of a block encoder's wave body, composed by the general kernel (tile_encode.hip: all depth slices,
+// slice differences) and by the tile batches (tile_batch_dev.h: one value a pixel): the lanes of a block
+// (blockLanes), a slice's values (gatherSlice), its statistics, quantised values and plan (analyseSlice), its byte image (composeBlock).
 #pragma once
 #include "wave_utils.h"
 #include "block_plan.h"
@@ -41,7 +43,158 @@ __device__ __forceinline__ u32 extractDistinct(const u32 (&q)[E], const int (&ra
 }
 
 
-// Builds the byte image of one block in LDS (obuf, zeroed here) -- Lerc2::WriteTile.
+// ---- stage 1, the lanes of a block: the wave owns block position pos of a band cut into mb x mb blocks; lane l holds elements
+// l, l + 64, ... of the block in row-major order.  The encoders' only place for a block's geometry and its elements' ranks.
+struct BlockGeom { int i0, j0, tileW, nElem; };
+
+__device__ __forceinline__ BlockGeom blockGeom(const BandParams& p, int pos, int mb)
+{
+  const int it = pos / p.nTH, jt = pos - it * p.nTH;
+  BlockGeom g;
+  g.i0 = it * mb; g.j0 = jt * mb;
+  g.tileW = min(mb, p.nCols - g.j0);
+  g.nElem = min(mb, p.nRows - g.i0) * g.tileW;
+  return g;
+}
+
+// element k * 64 + lane: its pixel (the block's first where the element lies outside the block, e >= nElem) and its rank among the
+// block's valid pixels, which is the reference's dataBuf index (-1: not valid); n counts the valid pixels of the steps so far.
+// MASKED: valid pixels are compacted with __ballot / __popcll (every lane of the wave calls this); else every pixel of the block is
+// valid, rank = element, and n is not touched.
+template<bool MASKED>
+__device__ __forceinline__ void blockLaneStep(const BandParams& p, const BlockGeom& g, int k, const u8* __restrict__ maskBits, int& n, i64& pix, int& rank)
+{
+  const int e = k * 64 + laneId();
+  const bool inb = e < g.nElem;
+  const int r = inb ? e / g.tileW : 0, c = inb ? e - r * g.tileW : 0;
+  pix = (i64)(g.i0 + r) * p.nCols + (g.j0 + c);
+  if (MASKED)
+  {
+    const bool valid = inb && (p.allValid || maskBit(maskBits, pix));
+    const u64 bal = __ballot(valid);
+    rank = valid ? n + __popcll(bal & laneMaskLt()) : -1;
+    n += __popcll(bal);
+  }
+  else rank = inb ? e : -1;
+}
+
+template<int E>
+struct BlockLanes
+{
+  int rank[E];
+  i64 pix[E];
+  int n, j0, nElem;    // valid pixels, first column, elements of the block
+};
+
+template<int E, bool MASKED>
+__device__ __forceinline__ BlockLanes<E> blockLanes(const BandParams& p, int pos, const u8* __restrict__ maskBits)
+{
+  const BlockGeom g = blockGeom(p, pos, E == 1 ? 8 : 16);
+  BlockLanes<E> L;
+  L.j0 = g.j0; L.nElem = g.nElem;
+  L.n = MASKED ? 0 : g.nElem;
+#pragma unroll
+  for (int k = 0; k < E; k++) blockLaneStep<MASKED>(p, g, k, maskBits, L.n, L.pix[k], L.rank[k]);
+  return L;
+}
+
+// the one byte of a position without valid pixels, "all zero" (Lerc2.cpp:1534-1538, :1960-1966)
+__device__ __forceinline__ u8 emptyBlockByte(const BandParams& p, int j0)
+{
+  u32 flag = (u32)(((j0 >> 3) & 15) << 2);
+  if (p.version >= 5) flag &= 0x38u;
+  return (u8)(flag | 2u);
+}
+
+// ---- stage 2, a slice's values: slice iD of nD of the block's valid pixels into the lanes' registers and, by rank, into the wave's
+// valBuf (the reference's dataBuf)
+template<class T, int E>
+__device__ __forceinline__ void gatherSlice(const BlockLanes<E>& L, const T* __restrict__ data, int nD, int iD, T* valBuf, T (&v)[E])
+{
+#pragma unroll
+  for (int k = 0; k < E; k++)
+  {
+    v[k] = T(0);
+    if (L.rank[k] >= 0) { v[k] = data[L.pix[k] * nD + iD]; valBuf[L.rank[k]] = v[k]; }
+  }
+  waveSync();
+}
+
+// ---- stage 3, slice analysis: range, "same as the previous element" count, quantised values and the plan of a block's n > 0 values
+// v (also in valBuf by rank) of type Z -- a slice's values (GetValidDataAndStats, Lerc2.cpp:1717-1799) or their int differences to
+// the previous depth slice (ComputeDiffSliceInt, :1803-1874).  What the two differ in is said by the caller:
+//   dtZ        the values' data type for the plan: the band's, or DT_Int for differences
+//   prevIsZero whether the element of rank 0 is compared with a "previous value" of 0: GetValidDataAndStats starts prevVal at 0 on
+//              its all-valid branch only (:1735, against :1762-1775, where the first valid pixel counts as not the same);
+//              ComputeDiffSliceInt starts it at 0 on both branches (:1822)
+//   quantise   whether the block is quantised at all: maxZErr > 0 (NeedToQuantize, Lerc2.h:345-357); differences are tried for integer
+//              lossless bands only, where maxZErr is 0.5
+//   lossless   the quantiser is the integer subtraction (Quantize, Lerc2.h:359-376: maxZErr == 0.5 and an integer type); for differences
+//              quantLossless<int> is the reference's (unsigned int)((int64)d - (int64)zMin) literally
+template<class Z, int E>
+struct SliceCode
+{
+  Z zMin;
+  u32 q[E], qMax;
+  Plan plan;
+};
+
+template<class Z, int E>
+__device__ __forceinline__ SliceCode<Z, E> analyseSlice(const BandParams& p, int n, const Z (&v)[E], const int (&rank)[E], const Z* valBuf,
+                                                        int dtZ, bool prevIsZero, bool quantise, bool lossless)
+{
+  SliceCode<Z, E> s;
+  Z mn = valBuf[0], mx = valBuf[0];
+#pragma unroll
+  for (int k = 0; k < E; k++)
+    if (rank[k] >= 0) { mn = (v[k] < mn) ? v[k] : mn; mx = (v[k] > mx) ? v[k] : mx; }
+  mn = waveMinT(mn);
+  mx = waveMaxT(mx);
+  int same = 0;
+#pragma unroll
+  for (int k = 0; k < E; k++)
+  {
+    bool eq = false;
+    if (rank[k] > 0) eq = (v[k] == valBuf[rank[k] - 1]);
+    else if (rank[k] == 0) eq = prevIsZero && (v[k] == Z(0));
+    same += __popcll(__ballot(eq));
+  }
+  const bool tryLut = (n > 4) && ((double)mx > (double)mn + 3 * p.maxZErr) && (2 * same > n);
+
+  double mv = 0;
+  bool quantOk = false;
+  if (quantise)
+  {
+    mv = ((double)mx - (double)mn) * p.scale;
+    quantOk = !(mv > (double)p.maxQ || (u32)(mv + 0.5) == 0);
+  }
+  s.qMax = 0;
+#pragma unroll
+  for (int k = 0; k < E; k++) s.q[k] = 0;
+  if (quantOk)
+  {
+    const double z0 = (double)mn;
+#pragma unroll
+    for (int k = 0; k < E; k++)
+      if (rank[k] >= 0)
+      {
+        s.q[k] = lossless ? quantLossless<Z>(v[k], mn) : (u32)(((double)v[k] - z0) * p.scale + 0.5);
+        s.qMax = s.q[k] > s.qMax ? s.q[k] : s.qMax;
+      }
+    s.qMax = waveMax(s.qMax);
+  }
+  u32 nDistinct = 0;
+  if (tryLut && quantOk)
+  {
+    u32 idxTmp[E];
+    nDistinct = extractDistinct<E>(s.q, rank, nullptr, idxTmp);
+  }
+  s.zMin = mn;
+  s.plan = planBlock<Z>(p, n, mn, mx, dtZ, tryLut, mv, s.qMax, nDistinct);
+  return s;
+}
+
+// ---- stage 4, the byte image of one block in LDS (obuf, zeroed here) -- Lerc2::WriteTile.
 template<class Z, int E>
 __device__ __forceinline__ void composeBlock(u32* obuf, u32* lutBuf, const BandParams& p, const Plan& pl, int n, int j0,
                                              bool diff, Z zMin, const Z (&val)[E], const u32 (&q)[E],

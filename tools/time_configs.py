@@ -1,6 +1,8 @@
 """Tuning aid: the other BASELINE configurations, device resident, wall time per call and time per kernel:
 C3 16384^2 uint16 lossless, C4 4096^2 x 3 uint8 lossless (8-bit Huffman mode), C2 raster at maxZErr 0 (lossless float).
-    gpurun -- 'python tools/time_configs.py [c3 c4 c2lossless]'"""
+"depth3": a 4096^2 x 3 int16 lossless raster, the one case that reaches the general kernels' slice differences (k_encode_tiles) and
+k_decode_tiles: its profile scopes are tile_sizes, tile_write and tile_decode.
+    python tools/time_configs.py [c3 c4 c2lossless general depth3]"""
 import ctypes as ct
 import os
 import sys
@@ -69,6 +71,10 @@ def main():
         m = (((i // 97) + (j // 131)) % 10 != 0).to(torch.uint8).contiguous()
         run("C2 raster with a 10 % mask (general path)", x, 0.01, 1, mask=m)
         run("8000 x 8000 float32 (general path)", x[:8000, :8000].contiguous(), 0.01, 1)
+    if "depth3" in which:    # slice 1 = slice 0 + 7 (the difference wins), slice 2 independent (it loses)
+        a = synth.c3_uint16(4096, 4096).to(torch.int32)
+        b = synth.c3_uint16(4096, 4096, seed=77).to(torch.int32)
+        run("4096^2 x3 int16 lossless (slice differences)", torch.stack([a, a + 7, b], dim=-1).to(torch.int16).contiguous(), 0, 3)
     if "c2lossless" in which:
         run("C2 8192^2 float32 maxZErr 0", synth.c2_float32(), 0, 1)
 
