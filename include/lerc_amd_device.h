@@ -181,7 +181,32 @@ LERC_AMD_API lerc_status lerc_amd_encode_raster_tiles_device(lerc_amd_context* c
 LERC_AMD_API lerc_status lerc_amd_decode_raster_tiles_device(lerc_amd_context* ctx, const unsigned char* dArena, const unsigned long long* offsets,
     const unsigned int* sizes, unsigned int dataType, int nCols, int nRows, int nBands, unsigned long long rowPitch, unsigned long long bandPitch,
     int tileCols, int tileRows, void* dRaster, int nMasks, unsigned char* dValidBytes, unsigned long long maskRowPitch);
-/* Diagnostics of the two calls above: tiles out[0] cut through the staging buffer, out[1] encoded where they lie, out[2] pasted from
+/* The two calls above with one more stride: element (band b, row i, column j) lies at dRaster + b * bandPitch + i * rowPitch +
+ * j * pixelPitch, all pitches in ELEMENTS, all address arithmetic 64-bit.  Grid, tile order, offsets / sizes / arenaUsed, slots, status
+ * codes, hand-backs, lerc_amd_last_note, both counter calls and every blob are those of the calls above: tile t's blob is what
+ * lerc_encode makes of that rectangle as a band stack (nDepth 1, nBands, nMasks), whatever the layout it was read from.  The mask stays
+ * one [nRows][nCols] byte plane with maskRowPitch.  The layouts taken, WrongParam(2) for every other description:
+ *  - pixelPitch == 1, band-sequential (rowPitch >= nCols, bandPitch >= (nRows - 1) * rowPitch + nCols): the call IS the call above, same
+ *    checks, same path (coded where it lies included), same counters.
+ *  - pixelPitch == 1, line-interleaved (BIL): nBands > 1, bandPitch >= nCols, rowPitch >= (nBands - 1) * bandPitch + nCols.
+ *  - pixelPitch >= 2, pixel-interleaved (RGB / RGBA frames, [H, W, C] tensors, GDAL's INTERLEAVE=PIXEL): nBands == 1 (one channel of
+ *    an interleaved image, dRaster pointing at it; bandPitch ignored), or bandPitch == 1 and nBands <= pixelPitch;
+ *    rowPitch >= (nCols - 1) * pixelPitch + nBands.  pixelPitch > nBands is a raster with channels that are not coded (RGB out of RGBA, a
+ *    slice of a channel axis): the elements between a pixel's last band and the next pixel, like the row padding and whatever lies
+ *    beside a view, are never written by the decode and their values never used by either call (the encode fetches a row from band 0
+ *    of its first pixel to the last band of its last pixel in whole 16-byte vectors, nothing in front or behind).
+ * A pixel-interleaved raster always goes through the staging buffer (out[0] / out[2] of lerc_amd_raster_tiles_counters); the
+ * transposition is done by the kernels that fill and empty it (k_rt_cut_px / k_rt_paste_px), so the caller needs no planar copy.
+ * A pixelPitch of more than 8 elements is taken by a plain form of those kernels (a lane an element): same results, slower. */
+LERC_AMD_API lerc_status lerc_amd_encode_raster_tiles_device_strided(lerc_amd_context* ctx, const void* dRaster, unsigned int dataType, int nCols,
+    int nRows, int nBands, unsigned long long pixelPitch, unsigned long long rowPitch, unsigned long long bandPitch, int tileCols, int tileRows,
+    int nMasks, const unsigned char* dValidBytes, unsigned long long maskRowPitch, double maxZErr, unsigned char* dArena,
+    unsigned long long arenaCapacity, unsigned long long slotBytes, unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed);
+LERC_AMD_API lerc_status lerc_amd_decode_raster_tiles_device_strided(lerc_amd_context* ctx, const unsigned char* dArena,
+    const unsigned long long* offsets, const unsigned int* sizes, unsigned int dataType, int nCols, int nRows, int nBands,
+    unsigned long long pixelPitch, unsigned long long rowPitch, unsigned long long bandPitch, int tileCols, int tileRows, void* dRaster, int nMasks,
+    unsigned char* dValidBytes, unsigned long long maskRowPitch);
+/* Diagnostics of the four calls above: tiles out[0] cut through the staging buffer, out[1] encoded where they lie, out[2] pasted from
  * the staging buffer, out[3] decoded where they lie. */
 LERC_AMD_API void lerc_amd_raster_tiles_counters(lerc_amd_context* ctx, unsigned long long out[4]);
 

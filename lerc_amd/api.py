@@ -91,6 +91,16 @@ def load_library():
                                                             ct.c_ulonglong]
         lib.lerc_amd_raster_tiles_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_ulonglong)]
         lib.lerc_amd_raster_tiles_counters.restype = None
+    # (the strided raster tile calls: the same rule)
+    have_strided = not os.environ.get("LERC_AMD_LIBRARY") or hasattr(lib, "lerc_amd_encode_raster_tiles_device_strided")
+    if have_strided:
+        lib.lerc_amd_encode_raster_tiles_device_strided.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int, ct.c_int, ct.c_int,
+                                                                    ct.c_ulonglong, ct.c_ulonglong, ct.c_ulonglong, ct.c_int, ct.c_int, ct.c_int,
+                                                                    ct.c_void_p, ct.c_ulonglong, ct.c_double, ct.c_void_p, ct.c_ulonglong,
+                                                                    ct.c_ulonglong, ct.c_void_p, ct.c_void_p, ct.c_void_p]
+        lib.lerc_amd_decode_raster_tiles_device_strided.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int,
+                                                                    ct.c_int, ct.c_int, ct.c_ulonglong, ct.c_ulonglong, ct.c_ulonglong, ct.c_int,
+                                                                    ct.c_int, ct.c_void_p, ct.c_int, ct.c_void_p, ct.c_ulonglong]
     lib.lerc_amd_tile_batch_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_ulonglong)]
     lib.lerc_amd_tile_batch_counters.restype = None
     lib.lerc_amd_encode_device_async.argtypes = [ct.c_void_p] + enc + [ct.c_void_p, ct.c_uint, u32p]
@@ -102,7 +112,8 @@ def load_library():
               "lerc_amd_encode_device_async", "lerc_amd_decode_device_async", "lerc_amd_finish", "lerc_amd_encode_tiles_device_slots",
               "lerc_amd_decode_tiles_device_slots", "lerc_amd_encode_tiles_device_masked", "lerc_amd_decode_tiles_device_masked") + \
             (("lerc_amd_encode_tiles_device_bands", "lerc_amd_decode_tiles_device_bands") if have_bands else ()) + \
-            (("lerc_amd_encode_raster_tiles_device", "lerc_amd_decode_raster_tiles_device") if have_raster else ()):
+            (("lerc_amd_encode_raster_tiles_device", "lerc_amd_decode_raster_tiles_device") if have_raster else ()) + \
+            (("lerc_amd_encode_raster_tiles_device_strided", "lerc_amd_decode_raster_tiles_device_strided") if have_strided else ()):
         getattr(lib, n).restype = ct.c_uint
     _LIB = lib
     return lib
@@ -322,6 +333,30 @@ class DeviceCodec:
                                                             int(row_pitch), int(band_pitch), int(tile[1]), int(tile[0]), d_raster,
                                                             1 if d_valid else 0, d_valid or None, int(mask_row_pitch))
 
+    def encode_raster_tiles_strided(self, d_raster, dt_code, n_cols, n_rows, n_bands, pixel_pitch, row_pitch, band_pitch, tile, d_valid,
+                                    mask_row_pitch, max_z_err, d_arena, arena_cap, slot_bytes=0):
+        """encode_raster_tiles with a pixel pitch: element (b, i, j) at b * band_pitch + i * row_pitch + j * pixel_pitch -- pixel-interleaved
+        (pixel_pitch >= 2, band_pitch 1) and line-interleaved rasters; the library's check decides (status 2)"""
+        n_tiles = len(raster_tile_grid(n_rows, n_cols, tile))
+        offsets = np.zeros(n_tiles, np.uint64)
+        sizes = np.zeros(n_tiles, np.uint32)
+        used = ct.c_ulonglong(0)
+        rc = self.lib.lerc_amd_encode_raster_tiles_device_strided(self.h, d_raster, dt_code, n_cols, n_rows, n_bands, int(pixel_pitch),
+                                                                  int(row_pitch), int(band_pitch), int(tile[1]), int(tile[0]), 1 if d_valid else 0,
+                                                                  d_valid or None, int(mask_row_pitch), float(max_z_err), d_arena, int(arena_cap),
+                                                                  int(slot_bytes), offsets.ctypes.data, sizes.ctypes.data, ct.byref(used))
+        return rc, offsets, sizes, int(used.value)
+
+    def decode_raster_tiles_strided(self, d_arena, offsets, sizes, dt_code, n_cols, n_rows, n_bands, pixel_pitch, row_pitch, band_pitch, tile,
+                                    d_raster, d_valid, mask_row_pitch):
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        sizes = np.ascontiguousarray(sizes, np.uint32)
+        assert len(offsets) == len(sizes) == len(raster_tile_grid(n_rows, n_cols, tile))
+        return self.lib.lerc_amd_decode_raster_tiles_device_strided(self.h, d_arena, offsets.ctypes.data, sizes.ctypes.data, dt_code, n_cols, n_rows,
+                                                                    n_bands, int(pixel_pitch), int(row_pitch), int(band_pitch), int(tile[1]),
+                                                                    int(tile[0]), d_raster, 1 if d_valid else 0, d_valid or None,
+                                                                    int(mask_row_pitch))
+
     def raster_tile_grid(self, n_rows, n_cols, tile):
         return raster_tile_grid(n_rows, n_cols, tile)
 
@@ -503,36 +538,51 @@ def raster_tile_grid(n_rows, n_cols, tile):
 
 
 def _raster_view(raster, valid):
-    """-> (nBands, nRows, nCols, rowPitch, bandPitch, mask address, mask row pitch) of a raster tensor [R, C] or [B, R, C] whose rows are
-    dense (stride(-1) == 1) -- a view into a larger tensor is fine: the pitches are its strides"""
-    assert raster.dim() in (2, 3) and raster.stride(-1) == 1, "raster: [R, C] or [B, R, C] with dense rows"
+    """-> (nBands, nRows, nCols, pixelPitch, rowPitch, bandPitch, mask address, mask row pitch) of a raster tensor [R, C] or [B, R, C] with
+    ANY strides -- a view into a larger tensor, a permuted [H, W, C] tensor, a slice of its channel axis: the pitches are its strides.
+    Dense rows (stride(-1) == 1) are checked here, as ever; for any other layout the library's own check decides (status 2)."""
+    assert raster.dim() in (2, 3), "raster: [R, C] or [B, R, C]"
     n_rows, n_cols = int(raster.shape[-2]), int(raster.shape[-1])
     n_bands = int(raster.shape[0]) if raster.dim() == 3 else 1
-    row_pitch = int(raster.stride(-2)) if n_rows > 1 else n_cols
+    pixel_pitch = int(raster.stride(-1)) if n_cols > 1 else 1
     band_pitch = int(raster.stride(0)) if (raster.dim() == 3 and n_bands > 1) else 0
-    assert row_pitch >= n_cols and (n_bands == 1 or band_pitch >= (n_rows - 1) * row_pitch + n_cols), "raster: rows and bands must not overlap"
+    if pixel_pitch == 1:
+        row_pitch = int(raster.stride(-2)) if n_rows > 1 else n_cols
+        assert row_pitch >= n_cols and (n_bands == 1 or band_pitch >= (n_rows - 1) * row_pitch + n_cols), "raster: rows and bands must not overlap"
+    else:
+        row_pitch = int(raster.stride(-2)) if n_rows > 1 else (n_cols - 1) * pixel_pitch + n_bands
     if valid is None:
-        return n_bands, n_rows, n_cols, row_pitch, band_pitch, 0, 0
+        return n_bands, n_rows, n_cols, pixel_pitch, row_pitch, band_pitch, 0, 0
     assert valid.element_size() == 1 and tuple(valid.shape) == (n_rows, n_cols) and valid.stride(-1) == 1, "valid: uint8 [R, C] with dense rows"
     mask_pitch = int(valid.stride(0)) if n_rows > 1 else n_cols
     assert mask_pitch >= n_cols
-    return n_bands, n_rows, n_cols, row_pitch, band_pitch, valid.data_ptr(), mask_pitch
+    return n_bands, n_rows, n_cols, pixel_pitch, row_pitch, band_pitch, valid.data_ptr(), mask_pitch
 
 
 def encode_raster_tiles_device(codec, raster, valid, max_z_err, tile, arena, slot_bytes=0):
-    """raster: CUDA(HIP) tensor [R, C] or [B, R, C], a view allowed as long as stride(-1) == 1; valid: uint8 tensor [R, C] (0 = invalid, one
-    mask for all bands) or None; tile: (tileRows, tileCols); arena: uint8 CUDA tensor.  The raster is cut into the grid of
+    """raster: CUDA(HIP) tensor [R, C] or [B, R, C], a view with any strides: band-sequential (stride(-1) == 1) goes to the raster tile
+    call as ever; anything else -- hwc.permute(2, 0, 1), rgba[..., :3].permute(2, 0, 1), one channel of an interleaved image -- goes to
+    the strided call with pixelPitch = stride(-1), bandPitch = stride(0), without a copy; a layout the library does not take comes back
+    as status 2.  valid: uint8 tensor [R, C] with dense rows (0 = invalid, one mask for all bands) or None; tile: (tileRows, tileCols);
+    arena: uint8 CUDA tensor.  The raster is cut into the grid of
     raster_tile_grid and every tile becomes one blob, exactly what encode() makes of that rectangle (all bands, its part of the mask);
     slot_bytes != 0 (a multiple of 16): every blob in a room of its own, offsets says which.
     -> (status, offsets uint64[nTiles], sizes uint32[nTiles], arena bytes used)"""
-    n_bands, n_rows, n_cols, row_pitch, band_pitch, d_valid, mask_pitch = _raster_view(raster, valid)
-    return codec.encode_raster_tiles(raster.data_ptr(), _torch_dt_code(raster), n_cols, n_rows, n_bands, row_pitch, band_pitch, tile, d_valid,
-                                     mask_pitch, max_z_err, arena.data_ptr(), arena.numel(), slot_bytes)
+    n_bands, n_rows, n_cols, pixel_pitch, row_pitch, band_pitch, d_valid, mask_pitch = _raster_view(raster, valid)
+    if pixel_pitch == 1:
+        return codec.encode_raster_tiles(raster.data_ptr(), _torch_dt_code(raster), n_cols, n_rows, n_bands, row_pitch, band_pitch, tile, d_valid,
+                                         mask_pitch, max_z_err, arena.data_ptr(), arena.numel(), slot_bytes)
+    return codec.encode_raster_tiles_strided(raster.data_ptr(), _torch_dt_code(raster), n_cols, n_rows, n_bands, pixel_pitch, row_pitch, band_pitch,
+                                             tile, d_valid, mask_pitch, max_z_err, arena.data_ptr(), arena.numel(), slot_bytes)
 
 
 def decode_raster_tiles_device(codec, arena, offsets, sizes, out, valid_out, tile):
-    """the way back: out a tensor as `raster` above, valid_out as `valid` (written 1 / 0) or None.  A tile whose blob fails leaves its
+    """the way back: out a tensor as `raster` above (any strides: a pixel-interleaved view is written in place, its uncoded channels and
+    everything beside it untouched), valid_out as `valid` (written 1 / 0) or None.  A tile whose blob fails leaves its
     rectangle zeroed, all bands and mask; elements outside the rows of `out` (a view's surroundings) are not touched."""
-    n_bands, n_rows, n_cols, row_pitch, band_pitch, d_valid, mask_pitch = _raster_view(out, valid_out)
-    return codec.decode_raster_tiles(arena.data_ptr(), offsets, sizes, _torch_dt_code(out), n_cols, n_rows, n_bands, row_pitch, band_pitch, tile,
-                                     out.data_ptr(), d_valid, mask_pitch)
+    n_bands, n_rows, n_cols, pixel_pitch, row_pitch, band_pitch, d_valid, mask_pitch = _raster_view(out, valid_out)
+    if pixel_pitch == 1:
+        return codec.decode_raster_tiles(arena.data_ptr(), offsets, sizes, _torch_dt_code(out), n_cols, n_rows, n_bands, row_pitch, band_pitch, tile,
+                                         out.data_ptr(), d_valid, mask_pitch)
+    return codec.decode_raster_tiles_strided(arena.data_ptr(), offsets, sizes, _torch_dt_code(out), n_cols, n_rows, n_bands, pixel_pitch, row_pitch,
+                                             band_pitch, tile, out.data_ptr(), d_valid, mask_pitch)

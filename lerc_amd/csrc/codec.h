@@ -321,6 +321,8 @@ struct RasterTilesRequest
   u8* dValidBytes = nullptr;          // device: one byte mask [nRows][maskRowPitch] for the raster (nMasks == 1), or nullptr
   int dt = 0, nCols = 0, nRows = 0, nBands = 1, nMasks = 0, tileCols = 0, tileRows = 0;
   u64 rowPitch = 0, bandPitch = 0, maskRowPitch = 0;    // in elements
+  u64 pixelPitch = 1;                 // elements from column to column: 1 planes (band-sequential, or line-interleaved), >= 2 pixel-interleaved (bandPitch 1)
+  bool anyLayout = false;             // the _strided entry points: line- and pixel-interleaved descriptions are admitted
   u8* dArena = nullptr;               // device (decode: read only)
   u64* hOffsets = nullptr;            // host [nTY * nTX], tile (ty, tx) at ty * nTX + tx
   u32* hSizes = nullptr;

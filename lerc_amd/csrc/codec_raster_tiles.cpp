@@ -9,7 +9,9 @@
 // of rooms, if slotted), and its offsets and sizes are scattered into the caller's arrays by tile index.  The way back gathers the
 // tables, decodes into the staging buffer and pastes.  Size limits, hand-backs, notes, lerc_amd_tile_batch_counters and the status of a
 // failing tile are those calls' own.  Tiles that lie as [n][r][c] already (one band, a tile as wide as the raster, no padding) are handed
-// over where they lie.
+// over where they lie.  A pixel-interleaved raster (pixelPitch >= 2, the _strided calls) differs in the kernels that cut and paste its
+// data, k_rt_cut_px / k_rt_paste_px (raster_tiles_px.hip), and in nothing else: same staging buffer, same chunks, same counters; it is
+// never coded where it lies.
 #include "codec.h"
 #include "raster_tiles.h"
 
@@ -33,13 +35,31 @@ struct RtGrid
   u64 nTiles() const { return (u64)nTY * nTX; }
 };
 
+// The layouts taken.  pixelPitch 1: band-sequential (rows inside a band), and for the _strided calls line-interleaved as well (bands
+// inside a row) -- rtRasterAt is linear in its pitches, so k_rt_cut / k_rt_paste serve both.  pixelPitch >= 2 (the _strided calls
+// only): pixel-interleaved, one band or bands one element apart that fit into a pixel; a row holds its last pixel's last band.
+bool rtLayoutOk(const RasterTilesRequest& rq)
+{
+  const u64 nCols = (u64)rq.nCols, nRows = (u64)rq.nRows, nBands = (u64)rq.nBands;
+  if (rq.pixelPitch == 1)
+  {
+    if (rq.rowPitch >= nCols && (nBands == 1 || rq.bandPitch >= (nRows - 1) * rq.rowPitch + nCols)) return true;
+    // (line-interleaved: rowPitch >= (nBands - 1) * bandPitch + nCols, without the product)
+    return rq.anyLayout && nBands > 1 && rq.bandPitch >= nCols && rq.rowPitch >= nCols && (rq.rowPitch - nCols) / (nBands - 1) >= rq.bandPitch;
+  }
+  if (!rq.anyLayout || rq.pixelPitch == 0) return false;
+  if (nBands > 1 && (rq.bandPitch != 1 || nBands > rq.pixelPitch)) return false;
+  // (rowPitch >= (nCols - 1) * pixelPitch + nBands, without the product)
+  return rq.rowPitch >= nBands && (nCols == 1 || (rq.rowPitch - nBands) / (nCols - 1) >= rq.pixelPitch);
+}
+
 bool rtArgsOk(const RasterTilesRequest& rq, bool encode)
 {
   if (!rq.dRaster || !rq.dArena || !rq.hOffsets || !rq.hSizes || rq.dt < 0 || rq.dt > DT_Double || rq.nCols <= 0 || rq.nRows <= 0 || rq.nBands <= 0
     || rq.tileCols <= 0 || rq.tileRows <= 0 || (rq.nMasks != 0 && rq.nMasks != 1) || (rq.nMasks == 0) != (rq.dValidBytes == nullptr))
     return false;
-  if (rq.rowPitch < (u64)rq.nCols || (rq.nMasks && rq.maskRowPitch < (u64)rq.nCols)) return false;
-  if (rq.nBands > 1 && rq.bandPitch < (u64)(rq.nRows - 1) * rq.rowPitch + (u64)rq.nCols) return false;
+  if (rq.nMasks && rq.maskRowPitch < (u64)rq.nCols) return false;
+  if (!rtLayoutOk(rq)) return false;
   if (((uintptr_t)rq.dRaster & (uintptr_t)(dtSize(rq.dt) - 1)) != 0) return false;    // (elements lie on their own boundaries)
   if (encode && (rq.maxZErr < 0 || (rq.slotBytes & 15u) != 0)) return false;
   return true;
@@ -55,7 +75,7 @@ RtGrid rtGrid(const RasterTilesRequest& rq)
   if (fullY && remC) g.classes.push_back({ 0, fullX, fullY, 1, tr, remC });
   if (remR && fullX) g.classes.push_back({ fullY, 0, 1, fullX, remR, tc });
   if (remR && remC) g.classes.push_back({ fullY, fullX, 1, 1, remR, remC });
-  g.inPlace = rq.nBands == 1 && tc >= nC && rq.rowPitch == (u64)nC && (!rq.nMasks || rq.maskRowPitch == (u64)nC);
+  g.inPlace = rq.pixelPitch == 1 && rq.nBands == 1 && tc >= nC && rq.rowPitch == (u64)nC && (!rq.nMasks || rq.maskRowPitch == (u64)nC);
   return g;
 }
 
@@ -99,6 +119,20 @@ RtChunk rtChunk(const RasterTilesRequest& rq, const RtClass& k, u32 k0, u32 n, b
   return ch;
 }
 
+// the data of a chunk: planes through k_rt_cut / k_rt_paste, an interleaved raster through k_rt_cut_px / k_rt_paste_px
+void rtCutData(const RasterTilesRequest& rq, const RtClass& k, u32 k0, u32 n, u8* stage, u32 eb, hipStream_t st)
+{
+  const RtChunk ch = rtChunk(rq, k, k0, n, false);
+  if (rq.pixelPitch == 1) launchRasterCut(rq.dRaster, stage, ch, eb, st);
+  else launchRasterCutPx(rq.dRaster, stage, RtChunkPx{ ch, rq.pixelPitch }, eb, st);
+}
+void rtPasteData(const RasterTilesRequest& rq, const RtClass& k, u32 k0, u32 n, const u8* stage, u32 eb, hipStream_t st)
+{
+  const RtChunk ch = rtChunk(rq, k, k0, n, false);
+  if (rq.pixelPitch == 1) launchRasterPaste(stage, rq.dRaster, ch, eb, st);
+  else launchRasterPastePx(stage, rq.dRaster, RtChunkPx{ ch, rq.pixelPitch }, eb, st);
+}
+
 size_t rtTileIndex(const RtGrid& g, const RtClass& k, u32 i) { return (size_t)(k.ty0 + i / k.nTX) * g.nTX + (k.tx0 + i % k.nTX); }
 
 }    // namespace
@@ -138,7 +172,7 @@ u32 encodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq, u64& are
       else
       {
         (void)hipGetLastError();
-        launchRasterCut(rq.dRaster, stage, rtChunk(rq, k, k0, n, false), eb, st);
+        rtCutData(rq, k, k0, n, stage, eb, st);
         if (rq.nMasks) launchRasterCut(rq.dValidBytes, stage + rtMaskAt(p, n), rtChunk(rq, k, k0, n, true), 1, st);
         if (hipGetLastError() != hipSuccess) { ctx.lastError = "lerc_amd: the raster cut kernel could not be launched"; return kFailed; }
         sub.dData = stage;
@@ -240,7 +274,7 @@ u32 decodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq)
       {
         hipStream_t st = ctx.activeStream();
         (void)hipGetLastError();
-        launchRasterPaste(stage, rq.dRaster, rtChunk(rq, k, k0, n, false), eb, st);
+        rtPasteData(rq, k, k0, n, stage, eb, st);
         if (rq.nMasks) launchRasterPaste(stage + rtMaskAt(p, n), rq.dValidBytes, rtChunk(rq, k, k0, n, true), 1, st);
         if (hipGetLastError() != hipSuccess) { ctx.lastError = "lerc_amd: the raster paste kernel could not be launched"; return kFailed; }
       }

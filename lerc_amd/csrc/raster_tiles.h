@@ -31,4 +31,25 @@ inline u32 rtLanesPerRowLog2(u32 c, u32 elemBytes)
 void launchRasterCut(const void* dRaster, void* dStage, const RtChunk& ch, u32 elemBytes, hipStream_t st);
 void launchRasterPaste(const void* dStage, void* dRaster, const RtChunk& ch, u32 elemBytes, hipStream_t st);
 
+// ---- pixel-interleaved rasters (raster_tiles_px.hip): element (b, i, j) lies at b + i * rowPitch + j * pixelPitch, pixelPitch >= 2
+// and nBands <= pixelPitch (one band: channel 0 of the pointer handed over).  ch.bandPitch is not used.
+struct RtChunkPx
+{
+  RtChunk ch;
+  u64 pixelPitch;
+};
+
+// The staged form takes a row in segments of kRtPxSegBytes / elemBytes pixels (512, 256, 128, 64 for 1, 2, 4, 8 bytes), kRtPxRows rows
+// of a tile at a time, through an LDS buffer of kRtPxSlotDwords a row: room for a segment at kRtPxMaxPitch elements a pixel, the up to
+// 15 bytes the run begins behind a 16-byte boundary, and the padding dword after every 16 * pixelPitch bytes.  A pixelPitch above
+// kRtPxMaxPitch goes the plain way, a lane an element; the results are the same.
+static const u32 kRtPxMaxPitch = 8;
+static const u32 kRtPxSegBytes = 512;
+static const u32 kRtPxRows = 8;
+static const u32 kRtPxSlotDwords = 1168;    // >= (15 + kRtPxSegBytes * kRtPxMaxPitch) * (1 + 1 / 8) / 4: pixelPitch 2 pads most, 4 bytes in 32
+
+// staging <- interleaved raster and back, data only (the mask is a plane: launchRasterCut / launchRasterPaste).  One launch.
+void launchRasterCutPx(const void* dRaster, void* dStage, const RtChunkPx& cx, u32 elemBytes, hipStream_t st);
+void launchRasterPastePx(const void* dStage, void* dRaster, const RtChunkPx& cx, u32 elemBytes, hipStream_t st);
+
 }    // namespace lerc

@@ -19,6 +19,17 @@ per chunk, the records' round trip per class; beyond that the cut kernel is not 
 Every call is queued on torch's current stream and timed with events around it; warm-up, then the median and the interquartile range
 of REPS (21) repetitions.  Prints the numbers (they are recorded in DESIGN.md 8.3); exit status 1 if the target is missed.  Run it under a time limit of its own:
   timeout -k 10 600 python tools/time_raster_tiles.py
+
+`python tools/time_raster_tiles.py interleaved` times the strided calls (lerc_amd_*_raster_tiles_device_strided) on PIXEL-INTERLEAVED
+rasters instead: 4096 x 4096 x 3 uint8 lossless and 4096 x 4096 x 4 float32 at 0.01, as [H, W, C] tensors, tiles of 256 x 256:
+
+  (1) the strided call on hwc.permute(2, 0, 1), no copy: k_rt_cut_px / k_rt_paste_px do the transposition
+  (2) what a caller did before: permute(2, 0, 1).contiguous() and the planar call; back: the planar call and a copy into [H, W, C]
+  (3) the planar call alone on the planar raster of the same bytes: (1) - (3) is what the transposing kernels cost over
+      k_rt_cut / k_rt_paste, the rest of the two calls being the same launches
+
+No pass mark (exit status 0): the numbers are recorded in DESIGN.md 8.3.  The kernels' own times come from running this mode under
+rocprofv3 --kernel-trace --stats (k_rt_cut_px, k_rt_paste_px against k_rt_cut, k_rt_paste).
 """
 import os
 import statistics
@@ -29,6 +40,96 @@ sys.path.insert(0, ROOT)
 REPS = int(os.environ.get("REPS", "21"))
 TILE = 256
 E = 0.01
+
+
+def interleaved():
+    import torch
+    from lerc_amd import api, synth
+    assert torch.cuda.is_available(), "needs a GPU"
+    size, tile = 4096, (TILE, TILE)
+    codec = api.DeviceCodec(torch.cuda.current_stream().cuda_stream)
+    print("strided raster tile calls on pixel-interleaved rasters -- %s; %d x %d, tiles of %d x %d; median [interquartile range] of %d, ms"
+          % (torch.cuda.get_device_name(0), size, size, TILE, TILE, REPS))
+    terrain = synth.c2_float32(size, size, device="cuda:0")
+    for name, nb, e in (("uint8", 3, 0.0), ("float32", 4, E)):
+        chans = [terrain.roll(37 * b, 0).roll(91 * b, 1) + 3.0 * b for b in range(nb)]
+        if name == "uint8":
+            lo, hi = float(terrain.min()), float(terrain.max())
+            chans = [((c - lo) * (255.0 / (hi - lo + 3.0 * nb))).to(torch.uint8) for c in chans]
+        hwc = torch.stack(chans, dim=2).contiguous()
+        del chans
+        view = hwc.permute(2, 0, 1)
+        item = hwc.element_size()
+        n = len(api.raster_tile_grid(size, size, tile))
+        arena = torch.zeros(n * (nb * (TILE * TILE * item + TILE * TILE // 4 + 1024) + 16), dtype=torch.uint8, device="cuda")
+        hwc_back = torch.zeros_like(hwc)
+        planes = view.contiguous()
+        planes_back = torch.zeros_like(planes)
+        state = {}
+
+        def enc_1():
+            rc, offs, sizes, used = api.encode_raster_tiles_device(codec, view, None, e, tile, arena)
+            assert rc == 0, (rc, codec.last_error())
+            state["t"] = (offs, sizes, used)
+
+        def dec_1():
+            assert api.decode_raster_tiles_device(codec, arena, state["t"][0], state["t"][1], hwc_back.permute(2, 0, 1), None, tile) == 0
+
+        def enc_2():
+            rc, offs, sizes, used = api.encode_raster_tiles_device(codec, view.contiguous(), None, e, tile, arena)
+            assert rc == 0, (rc, codec.last_error())
+
+        def dec_2():
+            assert api.decode_raster_tiles_device(codec, arena, state["t"][0], state["t"][1], planes_back, None, tile) == 0
+            hwc_back.copy_(planes_back.permute(1, 2, 0))
+
+        def enc_3():
+            rc, offs, sizes, used = api.encode_raster_tiles_device(codec, planes, None, e, tile, arena)
+            assert rc == 0, (rc, codec.last_error())
+
+        def dec_3():
+            assert api.decode_raster_tiles_device(codec, arena, state["t"][0], state["t"][1], planes_back, None, tile) == 0
+
+        def copy_c():
+            hwc_back.copy_(hwc)
+
+        r0 = codec.raster_tiles_counters()
+        enc_1()
+        dec_1()
+        torch.cuda.synchronize()
+        r1 = codec.raster_tiles_counters()
+        err = float((hwc_back.double() - hwc.double()).abs().max())
+        assert err <= e + 1e-4, err
+        t = {k: timed_on(torch, f) for k, f in (("e1", enc_1), ("d1", dec_1), ("e2", enc_2), ("d2", dec_2), ("e3", enc_3), ("d3", dec_3), ("c", copy_c))}
+        mib = hwc.numel() * item / 2 ** 20
+        print("%s x %d (%.0f MiB, %d blob bytes): raster call counters [cut, in place, pasted, in place] %s; max error %.6f"
+              % (name, nb, mib, state["t"][2], [int(y - x) for x, y in zip(r0, r1)], err))
+        print("  (1) strided call, no copy               encode %8.3f [%6.3f]   decode %8.3f [%6.3f]" % (t["e1"] + t["d1"]))
+        print("  (2) contiguous() + planar call / back   encode %8.3f [%6.3f]   decode %8.3f [%6.3f]" % (t["e2"] + t["d2"]))
+        print("  (3) planar call on the planar raster    encode %8.3f [%6.3f]   decode %8.3f [%6.3f]" % (t["e3"] + t["d3"]))
+        print("  device-to-device copy of the raster     %8.3f [%6.3f]   (%.0f GB/s read + written)" % (t["c"][0], t["c"][1], 2 * mib * 2 ** 20 / t["c"][0] / 1e6))
+        print("  (1) - (3), the transposition's price    encode %8.3f   decode %8.3f" % (t["e1"][0] - t["e3"][0], t["d1"][0] - t["d3"][0]))
+        print("  (2) - (1), the gain over a planar copy  encode %8.3f   decode %8.3f" % (t["e2"][0] - t["e1"][0], t["d2"][0] - t["d1"][0]))
+        del hwc, view, arena, hwc_back, planes, planes_back
+        torch.cuda.empty_cache()
+    codec.close()
+    return 0
+
+
+def timed_on(torch, fn, reps=REPS, warm=3):
+    for _ in range(warm):
+        fn()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ms.append(a.elapsed_time(b))
+    q = statistics.quantiles(ms, n=4)
+    return statistics.median(ms), q[2] - q[0]
 
 
 def main():
@@ -120,4 +221,4 @@ def main():
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(interleaved() if sys.argv[1:] == ["interleaved"] else main())
