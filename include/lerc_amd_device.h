@@ -206,7 +206,38 @@ LERC_AMD_API lerc_status lerc_amd_decode_raster_tiles_device_strided(lerc_amd_co
     const unsigned long long* offsets, const unsigned int* sizes, unsigned int dataType, int nCols, int nRows, int nBands,
     unsigned long long pixelPitch, unsigned long long rowPitch, unsigned long long bandPitch, int tileCols, int tileRows, void* dRaster, int nMasks,
     unsigned char* dValidBytes, unsigned long long maskRowPitch);
-/* Diagnostics of the four calls above: tiles out[0] cut through the staging buffer, out[1] encoded where they lie, out[2] pasted from
+/* A RANGE of the grid's tiles, coded: lerc_amd_encode_raster_tiles_device_strided with tileCol0, tileRow0, nTileCols, nTileRows behind
+ * tileRows.  dRaster and its sizes, pitches and mask describe the WHOLE raster, as above; only the tiles (ty, tx) with tileRow0 <= ty <
+ * tileRow0 + nTileRows and tileCol0 <= tx < tileCol0 + nTileCols are cut and coded -- the tiles a dirty region touches, a rank's rows of
+ * tiles.  offsets / sizes stay the full grid's tables (nTY * nTX entries, tile order as above): only the range's entries are written.
+ * Offsets are relative to dArena; packed, 16-byte aligned; slotted, the range's tiles take rooms 0 .. nRange - 1 (nRange = nTileRows *
+ * nTileCols) and arenaCapacity >= nRange * slotBytes, else BufferTooSmall(3).  arenaUsed counts the range only.  Every blob is byte
+ * for byte what the whole-raster call makes of that tile; coded where they lie under the condition above (a range of tile rows then).
+ * WrongParam(2) for an empty range or one not inside the grid. */
+LERC_AMD_API lerc_status lerc_amd_encode_raster_tiles_device_range(lerc_amd_context* ctx, const void* dRaster, unsigned int dataType, int nCols,
+    int nRows, int nBands, unsigned long long pixelPitch, unsigned long long rowPitch, unsigned long long bandPitch, int tileCols, int tileRows,
+    int tileCol0, int tileRow0, int nTileCols, int nTileRows, int nMasks, const unsigned char* dValidBytes, unsigned long long maskRowPitch,
+    double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity, unsigned long long slotBytes, unsigned long long* offsets,
+    unsigned int* sizes, unsigned long long* arenaUsed);
+/* A WINDOW of a mosaic, decoded: rows [winRow0, winRow0 + winRows) by columns [winCol0, winCol0 + winCols) of the raster, into a buffer
+ * of the caller's that holds the window only.  nCols, nRows, tileCols, tileRows describe the mosaic and its grid as above; offsets /
+ * sizes are the full grid's HOST tables, of which only the entries of tiles that intersect the window are read, and only those tiles
+ * are decoded.  Element (band b, row i, column j) of the window is pixel (winRow0 + i, winCol0 + j) of band b and lies at dWindow +
+ * b * bandPitch + i * rowPitch + j * pixelPitch (ELEMENTS); the layouts are those of the _strided calls with their rules applied to
+ * winCols / winRows: band-sequential, line-interleaved, pixel-interleaved with nBands <= pixelPitch (the plain kernel form above 8).
+ * dValidBytes (nMasks 1): the window's mask, [winRows][winCols] bytes, maskRowPitch >= winCols from row to row; NULL with nMasks 0.
+ * Pixels and valid bytes are exactly what lerc_amd_decode_raster_tiles_device[_strided] writes at those positions for the same blobs.
+ * Nothing outside [0, winCols) of a window row is written -- gaps between pixels, row padding, whatever lies beside a view -- and
+ * nothing of the destination is read.  A blob that fails leaves its part of the window zeroed, all bands and the mask's part; the
+ * other tiles are decoded all the same, and the call returns the first such status.  WrongParam(2) for a window with a size that is
+ * not positive or one not inside [0, nRows) x [0, nCols), a layout the strided calls would refuse for a raster of the window's size,
+ * nMasks other than 0 or 1.  The window's tiles always go through the staging buffer (out[2] of lerc_amd_raster_tiles_counters: the
+ * intersecting tiles), a chunk of a shape class at a time as above, and are written by a clipped paste (k_rw_paste / k_rw_paste_px). */
+LERC_AMD_API lerc_status lerc_amd_decode_raster_window_device(lerc_amd_context* ctx, const unsigned char* dArena, const unsigned long long* offsets,
+    const unsigned int* sizes, unsigned int dataType, int nCols, int nRows, int nBands, int tileCols, int tileRows, int winCol0, int winRow0,
+    int winCols, int winRows, void* dWindow, unsigned long long pixelPitch, unsigned long long rowPitch, unsigned long long bandPitch, int nMasks,
+    unsigned char* dValidBytes, unsigned long long maskRowPitch);
+/* Diagnostics of the calls above: tiles out[0] cut through the staging buffer, out[1] encoded where they lie, out[2] pasted from
  * the staging buffer, out[3] decoded where they lie. */
 LERC_AMD_API void lerc_amd_raster_tiles_counters(lerc_amd_context* ctx, unsigned long long out[4]);
 

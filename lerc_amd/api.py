@@ -101,6 +101,16 @@ def load_library():
         lib.lerc_amd_decode_raster_tiles_device_strided.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int,
                                                                     ct.c_int, ct.c_int, ct.c_ulonglong, ct.c_ulonglong, ct.c_ulonglong, ct.c_int,
                                                                     ct.c_int, ct.c_void_p, ct.c_int, ct.c_void_p, ct.c_ulonglong]
+    # (the tile range and window calls: the same rule)
+    have_window = not os.environ.get("LERC_AMD_LIBRARY") or hasattr(lib, "lerc_amd_decode_raster_window_device")
+    if have_window:
+        lib.lerc_amd_encode_raster_tiles_device_range.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int, ct.c_int, ct.c_int,
+                                                                  ct.c_ulonglong, ct.c_ulonglong, ct.c_ulonglong, ct.c_int, ct.c_int, ct.c_int,
+                                                                  ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_void_p, ct.c_ulonglong, ct.c_double,
+                                                                  ct.c_void_p, ct.c_ulonglong, ct.c_ulonglong, ct.c_void_p, ct.c_void_p, ct.c_void_p]
+        lib.lerc_amd_decode_raster_window_device.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int, ct.c_int,
+                                                             ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_void_p,
+                                                             ct.c_ulonglong, ct.c_ulonglong, ct.c_ulonglong, ct.c_int, ct.c_void_p, ct.c_ulonglong]
     lib.lerc_amd_tile_batch_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_ulonglong)]
     lib.lerc_amd_tile_batch_counters.restype = None
     lib.lerc_amd_encode_device_async.argtypes = [ct.c_void_p] + enc + [ct.c_void_p, ct.c_uint, u32p]
@@ -113,7 +123,8 @@ def load_library():
               "lerc_amd_decode_tiles_device_slots", "lerc_amd_encode_tiles_device_masked", "lerc_amd_decode_tiles_device_masked") + \
             (("lerc_amd_encode_tiles_device_bands", "lerc_amd_decode_tiles_device_bands") if have_bands else ()) + \
             (("lerc_amd_encode_raster_tiles_device", "lerc_amd_decode_raster_tiles_device") if have_raster else ()) + \
-            (("lerc_amd_encode_raster_tiles_device_strided", "lerc_amd_decode_raster_tiles_device_strided") if have_strided else ()):
+            (("lerc_amd_encode_raster_tiles_device_strided", "lerc_amd_decode_raster_tiles_device_strided") if have_strided else ()) + \
+            (("lerc_amd_encode_raster_tiles_device_range", "lerc_amd_decode_raster_window_device") if have_window else ()):
         getattr(lib, n).restype = ct.c_uint
     _LIB = lib
     return lib
@@ -357,6 +368,34 @@ class DeviceCodec:
                                                                     int(tile[0]), d_raster, 1 if d_valid else 0, d_valid or None,
                                                                     int(mask_row_pitch))
 
+    def encode_raster_tiles_range(self, d_raster, dt_code, n_cols, n_rows, n_bands, pixel_pitch, row_pitch, band_pitch, tile, tile_range,
+                                  d_valid, mask_row_pitch, max_z_err, d_arena, arena_cap, slot_bytes=0):
+        """encode_raster_tiles_strided for the tiles of tile_range = (tileRow0, tileCol0, nTileRows, nTileCols) only: offsets / sizes are
+        the full grid's tables, zero outside the range; offsets are relative to d_arena, arena bytes used count the range only"""
+        n_tiles = len(raster_tile_grid(n_rows, n_cols, tile))
+        offsets = np.zeros(n_tiles, np.uint64)
+        sizes = np.zeros(n_tiles, np.uint32)
+        used = ct.c_ulonglong(0)
+        rc = self.lib.lerc_amd_encode_raster_tiles_device_range(self.h, d_raster, dt_code, n_cols, n_rows, n_bands, int(pixel_pitch),
+                                                                int(row_pitch), int(band_pitch), int(tile[1]), int(tile[0]), int(tile_range[1]),
+                                                                int(tile_range[0]), int(tile_range[3]), int(tile_range[2]), 1 if d_valid else 0,
+                                                                d_valid or None, int(mask_row_pitch), float(max_z_err), d_arena, int(arena_cap),
+                                                                int(slot_bytes), offsets.ctypes.data, sizes.ctypes.data, ct.byref(used))
+        return rc, offsets, sizes, int(used.value)
+
+    def decode_raster_window(self, d_arena, offsets, sizes, dt_code, n_cols, n_rows, n_bands, tile, window_rect, d_window, pixel_pitch,
+                             row_pitch, band_pitch, d_valid, mask_row_pitch):
+        """window_rect = (row0, col0, rows, cols) of the mosaic n_rows x n_cols into the buffer at d_window, which holds the window only;
+        offsets / sizes: the full grid's tables, read at the window's tiles (raster_window_tiles)"""
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        sizes = np.ascontiguousarray(sizes, np.uint32)
+        assert len(offsets) == len(sizes) == len(raster_tile_grid(n_rows, n_cols, tile))
+        return self.lib.lerc_amd_decode_raster_window_device(self.h, d_arena, offsets.ctypes.data, sizes.ctypes.data, dt_code, n_cols, n_rows,
+                                                             n_bands, int(tile[1]), int(tile[0]), int(window_rect[1]), int(window_rect[0]),
+                                                             int(window_rect[3]), int(window_rect[2]), d_window, int(pixel_pitch),
+                                                             int(row_pitch), int(band_pitch), 1 if d_valid else 0, d_valid or None,
+                                                             int(mask_row_pitch))
+
     def raster_tile_grid(self, n_rows, n_cols, tile):
         return raster_tile_grid(n_rows, n_cols, tile)
 
@@ -586,3 +625,38 @@ def decode_raster_tiles_device(codec, arena, offsets, sizes, out, valid_out, til
                                          out.data_ptr(), d_valid, mask_pitch)
     return codec.decode_raster_tiles_strided(arena.data_ptr(), offsets, sizes, _torch_dt_code(out), n_cols, n_rows, n_bands, pixel_pitch, row_pitch,
                                              band_pitch, tile, out.data_ptr(), d_valid, mask_pitch)
+
+
+def raster_window_tiles(n_rows, n_cols, tile, window_rect):
+    """the indices, in the order of raster_tile_grid, of the tiles the window window_rect = (row0, col0, rows, cols) of a raster of
+    n_rows x n_cols touches: the entries of offsets / sizes decode_raster_window_device reads"""
+    tile_rows, tile_cols = int(tile[0]), int(tile[1])
+    row0, col0, rows, cols = (int(v) for v in window_rect)
+    assert n_rows > 0 and n_cols > 0 and tile_rows > 0 and tile_cols > 0
+    assert rows > 0 and cols > 0 and 0 <= row0 and row0 + rows <= n_rows and 0 <= col0 and col0 + cols <= n_cols, "the window lies inside the raster"
+    n_tx = -(-n_cols // tile_cols)
+    return [ty * n_tx + tx for ty in range(row0 // tile_rows, (row0 + rows - 1) // tile_rows + 1)
+            for tx in range(col0 // tile_cols, (col0 + cols - 1) // tile_cols + 1)]
+
+
+def encode_raster_tile_range_device(codec, raster, valid, max_z_err, tile, tile_range, arena, slot_bytes=0):
+    """encode_raster_tiles_device for a rectangle of the grid's tiles: tile_range = (tileRow0, tileCol0, nTileRows, nTileCols) -- the tiles
+    a dirty region touches, a rank's rows of tiles (shard.raster_tile_rows).  raster and valid are the WHOLE raster, as there (any
+    strides).  Only the range's tiles are cut and coded, each blob what the whole-raster call makes of that tile; slotted, they take
+    the first nTileRows * nTileCols rooms of the arena.
+    -> (status, offsets uint64[nTiles], sizes uint32[nTiles], arena bytes used): full-grid tables, zero outside the range"""
+    n_bands, n_rows, n_cols, pixel_pitch, row_pitch, band_pitch, d_valid, mask_pitch = _raster_view(raster, valid)
+    return codec.encode_raster_tiles_range(raster.data_ptr(), _torch_dt_code(raster), n_cols, n_rows, n_bands, pixel_pitch, row_pitch, band_pitch,
+                                           tile, tile_range, d_valid, mask_pitch, max_z_err, arena.data_ptr(), arena.numel(), slot_bytes)
+
+
+def decode_raster_window_device(codec, arena, offsets, sizes, raster_shape, tile, window, out, valid_out):
+    """a window of a mosaic: raster_shape = (nRows, nCols) of the raster the grid of `tile` was cut from, offsets / sizes its full-grid
+    tables, window = (row0, col0) the raster position of out's first pixel; out a tensor [h, w] or [B, h, w] with any strides (as
+    decode_raster_tiles_device's), whose size is the window's; valid_out uint8 [h, w] with dense rows, or None.  Only the tiles of
+    raster_window_tiles are read and decoded; nothing beside out's elements is written.  A tile whose blob fails leaves its part of
+    the window zeroed."""
+    n_bands, rows, cols, pixel_pitch, row_pitch, band_pitch, d_valid, mask_pitch = _raster_view(out, valid_out)
+    return codec.decode_raster_window(arena.data_ptr(), offsets, sizes, _torch_dt_code(out), int(raster_shape[1]), int(raster_shape[0]), n_bands,
+                                      tile, (int(window[0]), int(window[1]), rows, cols), out.data_ptr(), pixel_pitch, row_pitch, band_pitch,
+                                      d_valid, mask_pitch)

@@ -811,6 +811,45 @@ lerc_status lerc_amd_decode_raster_tiles_device_strided(lerc_amd_context* h, con
   return decodeRasterTilesDevice(h->ctx, rq);
 }
 
+// ---- a range of the grid's tiles coded, and a window of the mosaic decoded into a buffer of its own
+lerc_status lerc_amd_encode_raster_tiles_device_range(lerc_amd_context* h, const void* dRaster, unsigned int dataType, int nCols, int nRows, int nBands,
+  unsigned long long pixelPitch, unsigned long long rowPitch, unsigned long long bandPitch, int tileCols, int tileRows, int tileCol0, int tileRow0,
+  int nTileCols, int nTileRows, int nMasks, const unsigned char* dValidBytes, unsigned long long maskRowPitch, double maxZErr, unsigned char* dArena,
+  unsigned long long arenaCapacity, unsigned long long slotBytes, unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed)
+{
+  if (arenaUsed) *arenaUsed = 0;
+  if (!h || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || tileCols <= 0 || tileRows <= 0) return kWrongParam;
+  if (tileCol0 < 0 || tileRow0 < 0 || nTileCols <= 0 || nTileRows <= 0) return kWrongParam;    // (inside the grid: the driver's check)
+  if (!rasterTileDimsOk(nCols, nRows, tileCols, tileRows, dataType)) return kDimsTooLarge;
+  RasterTilesRequest rq;
+  rq.dRaster = const_cast<void*>(dRaster); rq.dValidBytes = const_cast<unsigned char*>(dValidBytes); rq.dt = (int)dataType;
+  rq.nCols = nCols; rq.nRows = nRows; rq.nBands = nBands; rq.nMasks = nMasks; rq.tileCols = tileCols; rq.tileRows = tileRows;
+  rq.tileCol0 = tileCol0; rq.tileRow0 = tileRow0; rq.nTileCols = nTileCols; rq.nTileRows = nTileRows;
+  rq.pixelPitch = pixelPitch; rq.anyLayout = true; rq.rowPitch = rowPitch; rq.bandPitch = bandPitch; rq.maskRowPitch = maskRowPitch;
+  rq.dArena = dArena; rq.hOffsets = offsets; rq.hSizes = sizes; rq.maxZErr = maxZErr; rq.arenaCapacity = arenaCapacity; rq.slotBytes = slotBytes;
+  u64 used = 0;
+  const u32 rc = encodeRasterTilesDevice(h->ctx, rq, used);
+  if (arenaUsed) *arenaUsed = used;
+  return rc;
+}
+
+lerc_status lerc_amd_decode_raster_window_device(lerc_amd_context* h, const unsigned char* dArena, const unsigned long long* offsets,
+  const unsigned int* sizes, unsigned int dataType, int nCols, int nRows, int nBands, int tileCols, int tileRows, int winCol0, int winRow0,
+  int winCols, int winRows, void* dWindow, unsigned long long pixelPitch, unsigned long long rowPitch, unsigned long long bandPitch, int nMasks,
+  unsigned char* dValidBytes, unsigned long long maskRowPitch)
+{
+  if (!h || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || tileCols <= 0 || tileRows <= 0) return kWrongParam;
+  if (!rasterTileDimsOk(nCols, nRows, tileCols, tileRows, dataType)) return kDimsTooLarge;
+  RasterTilesRequest rq;
+  rq.dRaster = dWindow; rq.dValidBytes = dValidBytes; rq.dt = (int)dataType;
+  rq.nCols = nCols; rq.nRows = nRows; rq.nBands = nBands; rq.nMasks = nMasks; rq.tileCols = tileCols; rq.tileRows = tileRows;
+  rq.pixelPitch = pixelPitch; rq.anyLayout = true; rq.rowPitch = rowPitch; rq.bandPitch = bandPitch; rq.maskRowPitch = maskRowPitch;
+  rq.dArena = const_cast<unsigned char*>(dArena); rq.hOffsets = const_cast<unsigned long long*>(offsets); rq.hSizes = const_cast<unsigned int*>(sizes);
+  RasterWindow win;
+  win.col0 = winCol0; win.row0 = winRow0; win.cols = winCols; win.rows = winRows;
+  return decodeRasterWindowDevice(h->ctx, rq, win);
+}
+
 void lerc_amd_raster_tiles_counters(lerc_amd_context* h, unsigned long long out[4])
 {
   for (int i = 0; i < 4; i++) out[i] = h ? h->ctx.rasterTilesCount[i] : 0;

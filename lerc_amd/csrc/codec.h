@@ -329,9 +329,17 @@ struct RasterTilesRequest
   // encode only
   double maxZErr = 0;
   u64 arenaCapacity = 0, slotBytes = 0;
+  // the tiles of the grid the call is about, [tileRow0, tileRow0 + nTileRows) x [tileCol0, tileCol0 + nTileCols); a negative count: all
+  // from the first on (the default: the whole grid).  hOffsets / hSizes stay full-grid tables, only the range's entries are touched
+  int tileCol0 = 0, tileRow0 = 0, nTileCols = -1, nTileRows = -1;
 };
 u32 encodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq, u64& arenaUsed);
 u32 decodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq);
+// A window of the mosaic, in raster coordinates.  decodeRasterWindowDevice: rq describes the mosaic (nCols, nRows, the tile sizes, the
+// full-grid tables) and, with dRaster, the pitches and dValidBytes / maskRowPitch, the DESTINATION, which holds the window only; the
+// tiles the window touches are decoded, through the staging buffer always, and pasted clipped (raster_window.hip)
+struct RasterWindow { int col0 = 0, row0 = 0, cols = 0, rows = 0; };
+u32 decodeRasterWindowDevice(Context& ctx, const RasterTilesRequest& rq, const RasterWindow& win);
 
 // header-only queries (host)
 struct BlobInfo

@@ -12,6 +12,12 @@
 // over where they lie.  A pixel-interleaved raster (pixelPitch >= 2, the _strided calls) differs in the kernels that cut and paste its
 // data, k_rt_cut_px / k_rt_paste_px (raster_tiles_px.hip), and in nothing else: same staging buffer, same chunks, same counters; it is
 // never coded where it lies.
+//
+// Both ways take a RANGE of the grid's tiles (RasterTilesRequest: the whole grid by default; lerc_amd_encode_raster_tiles_device_range
+// names one): every class is cut down to it, which leaves classes, so nothing behind rtGrid knows about ranges but the tables' indices
+// and the slots' count.  lerc_amd_decode_raster_window_device is the decode of the range of tiles a window touches into a buffer that
+// holds the window only: the same chunks, tables gathered at those tiles alone, the same tile calls into the staging buffer -- and a
+// clipped paste behind them, k_rw_paste / k_rw_paste_px (raster_window.hip).
 #include "codec.h"
 #include "raster_tiles.h"
 
@@ -29,8 +35,9 @@ struct RtClass { u32 ty0, tx0, nTY, nTX, r, c; u64 tiles() const { return (u64)n
 
 struct RtGrid
 {
-  u32 nTY = 0, nTX = 0;
-  std::vector<RtClass> classes;
+  u32 nTY = 0, nTX = 0;            // the whole grid
+  std::vector<RtClass> classes;    // of the request's tile range: every shape class cut down to it
+  u64 nRange = 0;                  // tiles in the range (0: the range is empty or not inside the grid)
   bool inPlace = false;
   u64 nTiles() const { return (u64)nTY * nTX; }
 };
@@ -38,9 +45,9 @@ struct RtGrid
 // The layouts taken.  pixelPitch 1: band-sequential (rows inside a band), and for the _strided calls line-interleaved as well (bands
 // inside a row) -- rtRasterAt is linear in its pitches, so k_rt_cut / k_rt_paste serve both.  pixelPitch >= 2 (the _strided calls
 // only): pixel-interleaved, one band or bands one element apart that fit into a pixel; a row holds its last pixel's last band.
-bool rtLayoutOk(const RasterTilesRequest& rq)
+bool rtLayoutOk(const RasterTilesRequest& rq, u64 nCols, u64 nRows)
 {
-  const u64 nCols = (u64)rq.nCols, nRows = (u64)rq.nRows, nBands = (u64)rq.nBands;
+  const u64 nBands = (u64)rq.nBands;
   if (rq.pixelPitch == 1)
   {
     if (rq.rowPitch >= nCols && (nBands == 1 || rq.bandPitch >= (nRows - 1) * rq.rowPitch + nCols)) return true;
@@ -53,13 +60,17 @@ bool rtLayoutOk(const RasterTilesRequest& rq)
   return rq.rowPitch >= nBands && (nCols == 1 || (rq.rowPitch - nBands) / (nCols - 1) >= rq.pixelPitch);
 }
 
-bool rtArgsOk(const RasterTilesRequest& rq, bool encode)
+// (win: the buffer at dRaster and the mask hold that window of the raster, and the layout's rules apply to its size)
+bool rtArgsOk(const RasterTilesRequest& rq, bool encode, const RasterWindow* win = nullptr)
 {
+  if (win && (win->cols <= 0 || win->rows <= 0 || win->col0 < 0 || win->row0 < 0 || win->cols > rq.nCols - win->col0 || win->rows > rq.nRows - win->row0))
+    return false;
+  const u64 bufCols = (u64)(win ? win->cols : rq.nCols), bufRows = (u64)(win ? win->rows : rq.nRows);
   if (!rq.dRaster || !rq.dArena || !rq.hOffsets || !rq.hSizes || rq.dt < 0 || rq.dt > DT_Double || rq.nCols <= 0 || rq.nRows <= 0 || rq.nBands <= 0
     || rq.tileCols <= 0 || rq.tileRows <= 0 || (rq.nMasks != 0 && rq.nMasks != 1) || (rq.nMasks == 0) != (rq.dValidBytes == nullptr))
     return false;
-  if (rq.nMasks && rq.maskRowPitch < (u64)rq.nCols) return false;
-  if (!rtLayoutOk(rq)) return false;
+  if (rq.nMasks && rq.maskRowPitch < bufCols) return false;
+  if (!rtLayoutOk(rq, bufCols, bufRows)) return false;
   if (((uintptr_t)rq.dRaster & (uintptr_t)(dtSize(rq.dt) - 1)) != 0) return false;    // (elements lie on their own boundaries)
   if (encode && (rq.maxZErr < 0 || (rq.slotBytes & 15u) != 0)) return false;
   return true;
@@ -71,10 +82,21 @@ RtGrid rtGrid(const RasterTilesRequest& rq)
   const u32 tr = (u32)rq.tileRows, tc = (u32)rq.tileCols, nR = (u32)rq.nRows, nC = (u32)rq.nCols;
   const u32 fullY = nR / tr, fullX = nC / tc, remR = nR % tr, remC = nC % tc;
   g.nTY = fullY + (remR ? 1 : 0); g.nTX = fullX + (remC ? 1 : 0);
-  if (fullY && fullX) g.classes.push_back({ 0, 0, fullY, fullX, tr, tc });
-  if (fullY && remC) g.classes.push_back({ 0, fullX, fullY, 1, tr, remC });
-  if (remR && fullX) g.classes.push_back({ fullY, 0, 1, fullX, remR, tc });
-  if (remR && remC) g.classes.push_back({ fullY, fullX, 1, 1, remR, remC });
+  // the request's tile range [y0, y1) x [x0, x1): the whole grid unless it says otherwise
+  if (rq.tileRow0 < 0 || rq.tileCol0 < 0 || rq.nTileRows == 0 || rq.nTileCols == 0 || (u32)rq.tileRow0 >= g.nTY || (u32)rq.tileCol0 >= g.nTX) return g;
+  const u32 y0 = (u32)rq.tileRow0, x0 = (u32)rq.tileCol0;
+  if ((rq.nTileRows > 0 && (u32)rq.nTileRows > g.nTY - y0) || (rq.nTileCols > 0 && (u32)rq.nTileCols > g.nTX - x0)) return g;
+  const u32 y1 = rq.nTileRows < 0 ? g.nTY : y0 + (u32)rq.nTileRows, x1 = rq.nTileCols < 0 ? g.nTX : x0 + (u32)rq.nTileCols;
+  g.nRange = (u64)(y1 - y0) * (x1 - x0);
+  auto add = [&](u32 ty0, u32 tx0, u32 nTY, u32 nTX, u32 r, u32 c)
+  {
+    const u32 a0 = std::max(ty0, y0), a1 = std::min(ty0 + nTY, y1), b0 = std::max(tx0, x0), b1 = std::min(tx0 + nTX, x1);
+    if (a0 < a1 && b0 < b1) g.classes.push_back({ a0, b0, a1 - a0, b1 - b0, r, c });
+  };
+  if (fullY && fullX) add(0, 0, fullY, fullX, tr, tc);
+  if (fullY && remC) add(0, fullX, fullY, 1, tr, remC);
+  if (remR && fullX) add(fullY, 0, 1, fullX, remR, tc);
+  if (remR && remC) add(fullY, fullX, 1, 1, remR, remC);
   g.inPlace = rq.pixelPitch == 1 && rq.nBands == 1 && tc >= nC && rq.rowPitch == (u64)nC && (!rq.nMasks || rq.maskRowPitch == (u64)nC);
   return g;
 }
@@ -143,8 +165,9 @@ u32 encodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq, u64& are
   if (!rtArgsOk(rq, true)) return kWrongParam;
   const RtGrid g = rtGrid(rq);
   if (g.nTiles() > 0x7FFFFFFFull) return kDimsTooLarge;
+  if (g.nRange == 0) return kWrongParam;
   const bool slotted = rq.slotBytes != 0;
-  if (slotted && rq.arenaCapacity < g.nTiles() * rq.slotBytes) return kBufferTooSmall;
+  if (slotted && rq.arenaCapacity < g.nRange * rq.slotBytes) return kBufferTooSmall;
   const u32 eb = (u32)dtSize(rq.dt);
   hipStream_t st = ctx.activeStream();
   u8* stage = g.inPlace ? nullptr : rtStageFor(ctx, rq, g);
@@ -204,15 +227,20 @@ u32 encodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq, u64& are
       if (slotted) room += n; else base += used;
     }
   }
-  arenaUsed = slotted ? g.nTiles() * rq.slotBytes : base;
+  arenaUsed = slotted ? g.nRange * rq.slotBytes : base;
   return kOk;
 }
 
-u32 decodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq)
+// The way back.  win == nullptr: the request's tiles into the raster at rq.dRaster.  win: into a buffer that holds that window of the
+// raster -- the request's tile range is the tiles the window touches, they are never decoded where they lie, and the paste is the
+// clipped one.
+static u32 rtDecode(Context& ctx, const RasterTilesRequest& rq, const RasterWindow* win)
 {
-  if (!rtArgsOk(rq, false)) return kWrongParam;
-  const RtGrid g = rtGrid(rq);
+  if (!rtArgsOk(rq, false, win)) return kWrongParam;
+  RtGrid g = rtGrid(rq);
   if (g.nTiles() > 0x7FFFFFFFull) return kDimsTooLarge;
+  if (g.nRange == 0) return kWrongParam;
+  if (win) g.inPlace = false;
   const u32 eb = (u32)dtSize(rq.dt);
   u8* stage = g.inPlace ? nullptr : rtStageFor(ctx, rq, g);
   if (!g.inPlace && !stage) return kFailed;
@@ -274,14 +302,36 @@ u32 decodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq)
       {
         hipStream_t st = ctx.activeStream();
         (void)hipGetLastError();
-        rtPasteData(rq, k, k0, n, stage, eb, st);
-        if (rq.nMasks) launchRasterPaste(stage + rtMaskAt(p, n), rq.dValidBytes, rtChunk(rq, k, k0, n, true), 1, st);
+        if (win)
+        {
+          const RwChunk cw{ rtChunk(rq, k, k0, n, false), rq.pixelPitch, (u32)win->row0, (u32)win->col0, (u32)win->rows, (u32)win->cols };
+          if (rq.pixelPitch == 1) launchWindowPaste(stage, rq.dRaster, cw, eb, st);
+          else launchWindowPastePx(stage, rq.dRaster, cw, eb, st);
+          if (rq.nMasks) launchWindowPaste(stage + rtMaskAt(p, n), rq.dValidBytes, RwChunk{ rtChunk(rq, k, k0, n, true), 1, cw.winRow0, cw.winCol0, cw.winRows, cw.winCols }, 1, st);
+        }
+        else
+        {
+          rtPasteData(rq, k, k0, n, stage, eb, st);
+          if (rq.nMasks) launchRasterPaste(stage + rtMaskAt(p, n), rq.dValidBytes, rtChunk(rq, k, k0, n, true), 1, st);
+        }
         if (hipGetLastError() != hipSuccess) { ctx.lastError = "lerc_amd: the raster paste kernel could not be launched"; return kFailed; }
       }
     }
   }
   if (!ctx.sync()) return kFailed;    // (the pastes: the raster is the caller's when the call returns)
   return firstError;
+}
+
+u32 decodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq) { return rtDecode(ctx, rq, nullptr); }
+
+u32 decodeRasterWindowDevice(Context& ctx, const RasterTilesRequest& rq, const RasterWindow& win)
+{
+  if (rq.tileCols <= 0 || rq.tileRows <= 0 || !rtArgsOk(rq, false, &win)) return kWrongParam;
+  // the tiles the window touches are a rectangle of the grid
+  RasterTilesRequest sub = rq;
+  sub.tileRow0 = win.row0 / rq.tileRows; sub.nTileRows = (win.row0 + win.rows - 1) / rq.tileRows - sub.tileRow0 + 1;
+  sub.tileCol0 = win.col0 / rq.tileCols; sub.nTileCols = (win.col0 + win.cols - 1) / rq.tileCols - sub.tileCol0 + 1;
+  return rtDecode(ctx, sub, &win);
 }
 
 }    // namespace lerc

@@ -52,4 +52,19 @@ static const u32 kRtPxSlotDwords = 1168;    // >= (15 + kRtPxSegBytes * kRtPxMax
 void launchRasterCutPx(const void* dRaster, void* dStage, const RtChunkPx& cx, u32 elemBytes, hipStream_t st);
 void launchRasterPastePx(const void* dStage, void* dRaster, const RtChunkPx& cx, u32 elemBytes, hipStream_t st);
 
+// ---- the clipped paste of the window decode (raster_window.hip): the staged tiles of a chunk go into a buffer that holds a WINDOW of
+// the raster, rows [winRow0, winRow0 + winRows) by columns [winCol0, winCol0 + winCols) in raster coordinates, and nothing else.  ch's
+// pitches (and pixelPitch) are the window buffer's; ch's grid and class are the raster's.  Of every staged tile the rows and columns
+// inside the window are written, at (row - winRow0, col - winCol0); a tile that misses the window writes nothing.
+struct RwChunk
+{
+  RtChunk ch;
+  u64 pixelPitch;    // of the window buffer: 1 planes or line-interleaved (k_rw_paste), >= 2 pixel-interleaved (k_rw_paste_px)
+  u32 winRow0, winCol0, winRows, winCols;
+};
+
+// window <- staging.  pixelPitch 1 only (the mask plane: its own row pitch, nBands 1) / pixelPitch >= 2 only.  One launch.
+void launchWindowPaste(const void* dStage, void* dWindow, const RwChunk& cw, u32 elemBytes, hipStream_t st);
+void launchWindowPastePx(const void* dStage, void* dWindow, const RwChunk& cw, u32 elemBytes, hipStream_t st);
+
 }    // namespace lerc

@@ -8,57 +8,18 @@
 // address admits (16, 8, 4, 2, 1 bytes, never less than an element) -- a row of a raster that begins an element into its buffer, or a
 // staged tile of an edge class, which begins at t * r * c elements, is 16-byte aligned only by luck.  Nothing outside [0, c) of a
 // row is read or written.  All addresses are 64-bit: rowPitch * nRows passes 2^32 elements on large rasters.
-#include "raster_tiles.h"
-#include "wave_utils.h"
+#include "raster_tiles_dev.h"
 
 #include <algorithm>
 
 namespace lerc {
 
-template<class T>
-__device__ __forceinline__ void rtStore16(T* p, const uint4& x, u32 dstAlign)
-{
-  const u32 w[4] = { x.x, x.y, x.z, x.w };
-  if (dstAlign == 0u) { *reinterpret_cast<uint4*>(p) = x; return; }
-  if ((dstAlign & 7u) == 0u)
-  {
-    u64* q = reinterpret_cast<u64*>(p);
-    q[0] = (u64)w[0] | ((u64)w[1] << 32);
-    q[1] = (u64)w[2] | ((u64)w[3] << 32);
-    return;
-  }
-  if (sizeof(T) <= 4 && (dstAlign & 3u) == 0u)
-  {
-    u32* q = reinterpret_cast<u32*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; i++) q[i] = w[i];
-    return;
-  }
-  if (sizeof(T) <= 2 && (dstAlign & 1u) == 0u)
-  {
-    u16* q = reinterpret_cast<u16*>(p);
-#pragma unroll
-    for (int i = 0; i < 8; i++) q[i] = (u16)(w[i >> 1] >> (16 * (i & 1)));
-    return;
-  }
-  if (sizeof(T) == 1)
-  {
-    u8* q = reinterpret_cast<u8*>(p);
-#pragma unroll
-    for (int i = 0; i < 16; i++) q[i] = (u8)(w[i >> 2] >> (8 * (i & 3)));
-  }
-}
-
-// where row i of band b of the chunk's tile kk lies: in the raster (elements from its first), and in the staging buffer
+// where row i of band b of the chunk's tile kk lies in the raster, in elements from its first (in the staging buffer: rtStageAt)
 __device__ __forceinline__ u64 rtRasterAt(const RtChunk& ch, u32 kk, u32 b, u32 i)
 {
   const u32 k = ch.k0 + kk;
   const u32 ty = ch.ty0 + k / ch.classW, tx = ch.tx0 + k % ch.classW;
   return (u64)b * ch.bandPitch + ((u64)ty * ch.tileRows + i) * ch.rowPitch + (u64)tx * ch.tileCols;
-}
-__device__ __forceinline__ u64 rtStageAt(const RtChunk& ch, u32 kk, u32 b, u32 i)
-{
-  return (((u64)kk * ch.nBands + b) * ch.r + i) * ch.c;
 }
 
 // A unit: a strip of stripRows rows of one plane (units beyond the grid are taken in further rounds).  A lane works on four rows at a

@@ -32,73 +32,15 @@
 // no LDS.  Same results, and such rasters have more gap than data in every line they fetch anyway.
 // Nothing in front of band 0 of a row's first pixel or behind the last band of its last pixel is read or written.  All addresses are
 // 64-bit.  The kernels wait for nobody (__syncthreads only), so tools/hipsim runs them as they are.
-#include "raster_tiles.h"
-#include "wave_utils.h"
+#include "raster_tiles_dev.h"
 
 #include <algorithm>
-#include <type_traits>
 
 namespace lerc {
 
 namespace {
 
-// T in LDS: units of T (1, 2, 4 bytes) or two dwords (8 bytes); a chunk is the V * pixelPitch elements one lane transposes
-template<class T> struct PxLds
-{
-  using U = typename std::conditional<sizeof(T) == 8, u32, T>::type;
-  static constexpr u32 V = 16u / (u32)sizeof(T);            // elements a 16-byte vector
-  static constexpr u32 UE = (u32)(sizeof(T) / sizeof(U));   // units an element
-  static constexpr u32 PU = 4u / (u32)sizeof(U);            // units a padding dword
-};
-
-// the chunk an element lies in, e / (V * pixelPitch), by multiplication: inv = ceil(2^20 / (V * P)) is exact while e * V * P < 2^20,
-// and e < 16 + 512 * 8, V * P <= 128
-__device__ __forceinline__ u32 pxChunkOf(u32 e, u32 inv) { return (e * inv) >> 20; }
-
-template<class T> __device__ __forceinline__ u32 pxUnitAt(u32 e, u32 inv) { return e * PxLds<T>::UE + PxLds<T>::PU * pxChunkOf(e, inv); }
-
-template<class T> __device__ __forceinline__ T pxRead(const typename PxLds<T>::U* s, u32 e, u32 inv)
-{
-  const u32 u = pxUnitAt<T>(e, inv);
-  if constexpr (sizeof(T) == 8) return (T)s[u] | ((T)s[u + 1] << 32);
-  else return s[u];
-}
-
-template<class T> __device__ __forceinline__ void pxWrite(typename PxLds<T>::U* s, u32 e, u32 inv, T x)
-{
-  const u32 u = pxUnitAt<T>(e, inv);
-  if constexpr (sizeof(T) == 8) { s[u] = (u32)x; s[u + 1] = (u32)(x >> 32); }
-  else s[u] = x;
-}
-
-// the dword at which 16-byte vector k of the run (elements k * V ..: a chunk is a whole number of vectors) begins
-template<class T> __device__ __forceinline__ u32 pxVecAt(u32 k, u32 inv) { return 4u * k + pxChunkOf(k * PxLds<T>::V, inv); }
-
-template<class T> __device__ __forceinline__ uint4 pxPack(const T (&t)[PxLds<T>::V])
-{
-  constexpr u32 V = PxLds<T>::V;
-  u32 w[4] = { 0u, 0u, 0u, 0u };
-#pragma unroll
-  for (u32 q = 0; q < V; q++)
-  {
-    if constexpr (sizeof(T) == 8) { w[2 * q] = (u32)t[q]; w[2 * q + 1] = (u32)(t[q] >> 32); }
-    else w[q * (u32)sizeof(T) / 4u] |= (u32)t[q] << (8u * (u32)sizeof(T) * (q % (4u / (u32)sizeof(T))) % 32u);
-  }
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-template<class T> __device__ __forceinline__ void pxUnpack(const uint4& x, T (&t)[PxLds<T>::V])
-{
-  constexpr u32 V = PxLds<T>::V;
-  const u32 w[4] = { x.x, x.y, x.z, x.w };
-#pragma unroll
-  for (u32 q = 0; q < V; q++)
-  {
-    if constexpr (sizeof(T) == 8) t[q] = (T)w[2 * q] | ((T)w[2 * q + 1] << 32);
-    else t[q] = (T)(w[q * (u32)sizeof(T) / 4u] >> (8u * (u32)sizeof(T) * (q % (4u / (u32)sizeof(T))) % 32u));
-  }
-}
-
+// (the LDS layout's pieces -- PxLds, pxRead / pxWrite, pxVecAt, pxPack / pxUnpack, pxHead, pxStoreRun --: raster_tiles_dev.h)
 // where row i of the chunk's tile kk begins (band 0 of its first pixel), and a staged row of band b
 __device__ __forceinline__ u64 pxRasterAt(const RtChunkPx& cx, u32 kk, u32 i)
 {
@@ -110,14 +52,6 @@ __device__ __forceinline__ u64 pxRasterAt(const RtChunkPx& cx, u32 kk, u32 i)
 __device__ __forceinline__ u64 pxStageAt(const RtChunk& ch, u32 kk, u32 b, u32 i)
 {
   return (((u64)kk * ch.nBands + b) * ch.r + i) * ch.c;
-}
-
-// elements of a row in front of the first 16-byte aligned address (at most n)
-template<class T> __device__ __forceinline__ u32 pxHead(const T* p, u32 n)
-{
-  constexpr u32 V = PxLds<T>::V;
-  const u32 mis = ((u32)(uintptr_t)p & 15u) / (u32)sizeof(T);
-  return min(n, (V - mis) & (V - 1u));
 }
 
 // the plain form: a lane an element
@@ -141,65 +75,6 @@ __device__ __forceinline__ void pxPlain(const T* __restrict__ from, T* __restric
         else to[ra + (u64)x * cx.pixelPitch + b] = from[sa + x];
       }
     }
-  }
-}
-
-// a pixel's nb elements, LDS elements e .., to g: the widest pieces the address of each admits
-template<class T>
-__device__ __forceinline__ void pxStoreRun(T* g, const typename PxLds<T>::U* su, u32 e, u32 nb, u32 inv)
-{
-  constexpr u32 V = PxLds<T>::V;
-  u32 k = 0;
-  while (k < nb)
-  {
-    T* p = g + k;
-    const u32 a = (u32)(uintptr_t)p, left = nb - k;
-    if ((a & 15u) == 0u && left >= V)
-    {
-      T t[V];
-#pragma unroll
-      for (u32 q = 0; q < V; q++) t[q] = pxRead<T>(su, e + k + q, inv);
-      *reinterpret_cast<uint4*>(p) = pxPack<T>(t);
-      k += V;
-      continue;
-    }
-    if constexpr (sizeof(T) <= 4)
-    {
-      constexpr u32 N8 = 8u / (u32)sizeof(T);
-      if ((a & 7u) == 0u && left >= N8)
-      {
-        u64 x = 0;
-#pragma unroll
-        for (u32 q = 0; q < N8; q++) x |= (u64)pxRead<T>(su, e + k + q, inv) << (8u * (u32)sizeof(T) * q);
-        *reinterpret_cast<u64*>(p) = x;
-        k += N8;
-        continue;
-      }
-    }
-    if constexpr (sizeof(T) <= 2)
-    {
-      constexpr u32 N4 = 4u / (u32)sizeof(T);
-      if ((a & 3u) == 0u && left >= N4)
-      {
-        u32 x = 0;
-#pragma unroll
-        for (u32 q = 0; q < N4; q++) x |= (u32)pxRead<T>(su, e + k + q, inv) << (8u * (u32)sizeof(T) * q);
-        *reinterpret_cast<u32*>(p) = x;
-        k += N4;
-        continue;
-      }
-    }
-    if constexpr (sizeof(T) == 1)
-    {
-      if ((a & 1u) == 0u && left >= 2u)
-      {
-        *reinterpret_cast<u16*>(p) = (u16)((u32)pxRead<T>(su, e + k, inv) | ((u32)pxRead<T>(su, e + k + 1u, inv) << 8));
-        k += 2u;
-        continue;
-      }
-    }
-    *p = pxRead<T>(su, e + k, inv);
-    k++;
   }
 }
 

@@ -35,6 +35,15 @@ def tile_range(rank, world, n_tiles):
     return first, count
 
 
+def raster_tile_rows(rank, world, n_rows, tile_rows):
+    """`rank`'s run of TILE ROWS of a raster of n_rows rows cut at tile_rows (api.raster_tile_grid): (first tile row, count) -- with all
+    tile columns, the tile_range of api.encode_raster_tile_range_device.  The ranks' runs are tile_range's shares of the grid's rows of
+    tiles, so they partition the grid; with fewer rows of tiles than ranks the last ranks get a count of 0 (and make no call)."""
+    if n_rows <= 0 or tile_rows <= 0:
+        raise ValueError((n_rows, tile_rows))
+    return tile_range(rank, world, -(-int(n_rows) // int(tile_rows)))
+
+
 def _world():
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 

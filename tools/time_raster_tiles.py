@@ -30,6 +30,12 @@ rasters instead: 4096 x 4096 x 3 uint8 lossless and 4096 x 4096 x 4 float32 at 0
 
 No pass mark (exit status 0): the numbers are recorded in DESIGN.md 8.3.  The kernels' own times come from running this mode under
 rocprofv3 --kernel-trace --stats (k_rt_cut_px, k_rt_paste_px against k_rt_cut, k_rt_paste).
+
+`python tools/time_raster_tiles.py window` times lerc_amd_decode_raster_window_device on the 8192 x 8192 raster: windows of one tile,
+1/16, 1/4 and the whole of it, each once on tile boundaries and once shifted by (3, 5), against what a caller did before -- the
+whole-raster decode and a device copy of the slice.  The shifted whole-raster window (8189 x 8187 from (3, 5)) against the whole-raster
+decode is what the clipped paste costs over k_rt_paste.  Every window is checked bit for bit against the slice first.  No pass mark;
+the numbers are recorded in DESIGN.md 8.3 and profiles/raster_window_time.txt.
 """
 import os
 import statistics
@@ -112,6 +118,57 @@ def interleaved():
         print("  (2) - (1), the gain over a planar copy  encode %8.3f   decode %8.3f" % (t["e2"][0] - t["e1"][0], t["d2"][0] - t["d1"][0]))
         del hwc, view, arena, hwc_back, planes, planes_back
         torch.cuda.empty_cache()
+    codec.close()
+    return 0
+
+
+def window():
+    import torch
+    from lerc_amd import api, synth
+    assert torch.cuda.is_available(), "needs a GPU"
+    size, tile = 8192, (TILE, TILE)
+    codec = api.DeviceCodec(torch.cuda.current_stream().cuda_stream)
+    print("window decode against the whole-raster decode and a slice -- %s; %d x %d float32 at %.2f, tiles of %d x %d, packed; "
+          "median [interquartile range] of %d, ms" % (torch.cuda.get_device_name(0), size, size, E, TILE, TILE, REPS))
+    raster = synth.c2_float32(size, size, device="cuda:0")
+    n = len(api.raster_tile_grid(size, size, tile))
+    arena = torch.zeros(n * (TILE * TILE * 4 + TILE * TILE // 4 + 1024 + 16), dtype=torch.uint8, device="cuda")
+    rc, offs, sizes, used = api.encode_raster_tiles_device(codec, raster, None, E, tile, arena)
+    assert rc == 0, (rc, codec.last_error())
+    back = torch.zeros_like(raster)
+
+    def whole():
+        assert api.decode_raster_tiles_device(codec, arena, offs, sizes, back, None, tile) == 0
+
+    whole()
+    torch.cuda.synchronize()
+    ref = back.clone()
+    t_whole = timed_on(torch, whole)
+    print("  whole-raster decode (lerc_amd_decode_raster_tiles_device)   %8.3f [%6.3f]" % t_whole)
+    print("  window (row0, col0, rows x cols)        tiles   window decode        whole decode + copy of the slice")
+    for name, side in (("one tile", TILE), ("1/16", size // 4), ("1/4", size // 2), ("whole", size)):
+        for shift in ((0, 0), (3, 5)):
+            rows, cols = (side, side) if shift == (0, 0) or side < size else (size - shift[0], size - shift[1])
+            r0, c0 = (0 if side == size else TILE * 3) + shift[0], (0 if side == size else TILE * 5) + shift[1]
+            out = torch.zeros((rows, cols), dtype=torch.float32, device="cuda")
+            touched = len(api.raster_window_tiles(size, size, tile, (r0, c0, rows, cols)))
+
+            def win():
+                assert api.decode_raster_window_device(codec, arena, offs, sizes, (size, size), tile, (r0, c0), out, None) == 0
+
+            def old():
+                assert api.decode_raster_tiles_device(codec, arena, offs, sizes, back, None, tile) == 0
+                out.copy_(back[r0:r0 + rows, c0:c0 + cols])
+
+            c_0 = codec.raster_tiles_counters()
+            win()
+            torch.cuda.synchronize()
+            c_1 = codec.raster_tiles_counters()
+            assert [int(b - a) for a, b in zip(c_0, c_1)] == [0, 0, touched, 0]
+            assert torch.equal(out.view(torch.int32), ref[r0:r0 + rows, c0:c0 + cols].contiguous().view(torch.int32)), "the window is not the slice"
+            t_win, t_old = timed_on(torch, win), timed_on(torch, old)
+            print("  %-8s (%4d, %4d, %4d x %4d)   %5d   %8.3f [%6.3f]   %8.3f [%6.3f]" % ((name, r0, c0, rows, cols, touched) + t_win + t_old))
+            del out
     codec.close()
     return 0
 
@@ -221,4 +278,4 @@ def main():
 
 
 if __name__ == "__main__":
-    sys.exit(interleaved() if sys.argv[1:] == ["interleaved"] else main())
+    sys.exit(interleaved() if sys.argv[1:] == ["interleaved"] else window() if sys.argv[1:] == ["window"] else main())
