@@ -286,6 +286,10 @@ u32* enqueueMaskCount(Context& ctx, const u8* dBits, i64 nPix, hipStream_t st);
 bool enqueueMaskedOneSweep(Context& ctx, bool pack, const u8* src, u8* dst, const u8* dBits, i64 nPix, int bytesPerPixel, hipStream_t st);
 // what every user of the block kernels fills alike; callers set intLossless, tryDiff, zMaxHdr, checkOverflow where they differ from 0
 BandParams makeBandParams(int dt, int nRows, int nCols, int nD, int version, int mb, double maxZErr, bool allValid);
+// what the streaming encode kernels assume of a raster they take blind (codec_encode.cpp): one band of codec 6, every pixel valid, 8 x 8
+// blocks, the error bound as Lerc2 rounds it for integer types; and the TryRaiseMaxZError candidates worth a look, bit c = candidate c
+BandParams fastBandParams(int dt, int nRows, int nCols, double maxZErr);
+u32 raiseCandidates(int dt, double maxZErr);
 
 // The same two calls in two halves, for callers that keep several operations in flight on the stream (the asynchronous
 // device API, capi.cpp): the enqueue half puts the streaming kernels and the copy of their verdict into `slot` (pinned,

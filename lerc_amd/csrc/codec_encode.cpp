@@ -2,28 +2,22 @@
 //
 // A request the streaming kernels take is decided on the device; every other one, and every band they hand
 // back, goes band by band through encodeBands() (codec_encode_band.cpp).
+//   streamingEligible   may the streaming kernels take rasters of this shape blind?
+//   FastEncodePlan      one launch sequence: workspaceBytes(), layout(), arm(), launch(), fetch()
+//   FastHarvest         what became of a launch's rasters; the counters of the streaming encodes
+//   TileBatchEncoder    a mosaic's worth of tiles in sub-batches, the tiles handed back one by one behind them
 #include "codec.h"
 #include "huffman.h"
 #include "fpl.h"
 #include "tile_fast.h"
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <vector>
 
 namespace lerc {
-
-// ------------------------------------------------------------------------------------------------
-// streaming kernels: buffers + launches for nTiles rasters of one shape (a single raster is nTiles == 1)
-// ------------------------------------------------------------------------------------------------
-struct FastEncodeLaunch
-{
-  FastEncodeBuffers fb;
-  FastBatch batch;
-  BandParams bp;
-  u32 cand;
-  double maxZErr;
-};
 
 // LERC_AMD_ENCODE_LAUNCHES=2 keeps the two-launch form (statistics, then scan + pack) for a single raster: a tuning / test knob
 bool fastEncodeOneLaunch()
@@ -32,160 +26,293 @@ bool fastEncodeOneLaunch()
   return one;
 }
 
-static size_t fastEncodeWorkspace(int nRows, int nCols, u32 nTiles)
+// May the streaming kernels take rasters of this shape blind?  The callers differ in three ways:
+//   dOut        what has to lie on a 16-byte boundary besides the pixels: a request's output buffer (nullptr, a size query, does) or a batch's arena
+//   nDepth, hasMask, plain   a request (each band of a stack alike) may ask for depth, a mask, noData values, an older codec (!plain); a tile is one plain band
+//   tileStride  bytes from one raster to the next, 0: there is only one.  Rasters of whole blocks are read 16 bytes a lane and must lie 16 bytes apart; ragged
+//               ones (257 x 257 elevation tiles) are read pixel by pixel where rows do not start on 16-byte boundaries, and are the one-launch encoder's alone
+static bool streamingEligible(int dt, int nRows, int nCols, int nDepth, bool hasMask, bool plain, double maxZErr, const void* dData,
+                              const void* dOut, u64 tileStride)
 {
-  const size_t nWG = fastEncodeNumWG(nRows, nCols);
-  return (size_t)nTiles * (nWG * (kFastBlocksPerWG * sizeof(FastBlockDesc) + 64) + kFastPrefixStage + sizeof(FastEncodeResult)
-                           + (fastScanGroups((u32)nWG) + 1) * (4 + 8 * kScanPartWords) + fastPackGroups((u32)nWG) * 16 + fastTicketStride((u32)nWG) * 4 + 256)
-    + 65536;
+  const bool ragged = nRows % 8 != 0 || nCols % 8 != 0;
+  return plain && maxZErr != 777 && ((uintptr_t)dOut & 15) == 0 && ((uintptr_t)dData & 15) == 0 && (ragged || tileStride % 16 == 0)
+    && fastEncodeEligible(dt, nRows, nCols, nDepth, hasMask, maxZErr, fastEncodeOneLaunch());
 }
-
-static bool prepareFastEncode(Context& ctx, int dt, int nRows, int nCols, double maxZErr, u32 nTiles, u64 tileElems, bool arena,
-                              FastEncodeLaunch& fl)
+static bool anyNoData(const EncodeRequest& rq)
 {
-  const u32 nWG = fastEncodeNumWG(nRows, nCols);
-  const bool isFlt = dt >= DT_Float;
-  const size_t nT = nTiles;
-  FastEncodeBuffers& fb = fl.fb;
-  fl.batch.nTiles = nTiles; fl.batch.nWG = nWG; fl.batch.tileElems = tileElems; fl.batch.nBlobsMore = 0;
-  memset(&fb.solo, 0, sizeof(fb.solo));
-  memset(&fb.fused, 0, sizeof(fb.fused));
-  if (nTiles == 1 && !arena && fastSoloOk(dt, nRows, nCols))
-  {
-    // one raster: two launches, the pack step's first blocks scan and decide (tile_fast.h)
-    memset(&fb, 0, sizeof(fb));
-    const bool form = fastEncodeOneLaunch();
-    const u32 nWGf = form ? fastFusedNumWG(dt, nRows, nCols) : nWG;    // (the one-launch form counts its own workgroups)
-    const size_t nGroups = std::max(fastPackGroups(nWG), fastPackGroups(nWGf)), nFused = fastFusedGroups(std::max(nWG, nWGf));
-    // (counters: the pack accumulators, then the one-launch form's key cells; cells: a cell per workgroup, then the
-    // one-launch form's group cells and first-row errors)
-    u8* counters = ctx.persistentState(0, (nGroups + 1) * 8 + 2 * nGroups * 8 + 256);
-    u8* cells = ctx.persistentState(1, ((size_t)std::max(nWG, nWGf) + 2 * nFused + 16) * 8 + 256);
-    fb.desc = ctx.allocT<FastBlockDesc>((size_t)nWG * kFastBlocksPerWG);
-    fb.wgSize = ctx.allocT<u32>(fastWgStride(nWG) + 4);
-    fb.wgMinKey = ctx.allocT<u64>(nWG + 4);
-    fb.wgMaxKey = ctx.allocT<u64>(nWG + 4);
-    fb.wgFlags = ctx.allocT<u32>(nWG + 4);
-    fb.tickets = ctx.allocT<u32>(fastTicketStride(nWG) + 4);
-    fb.result = ctx.allocT<FastEncodeResult>(1);
-    fb.prefixStage = ctx.allocT<u8>(kFastPrefixStage);
-    if (!counters || !cells || !fb.desc || !fb.wgSize || !fb.wgMinKey || !fb.wgMaxKey || !fb.wgFlags || !fb.tickets || !fb.result || !fb.prefixStage)
-      return false;
-    fb.packPart = (u64*)counters;
-    fb.solo.cells = (u64*)cells;
-    if (form)
-    {
-      const size_t nCell = std::max(nWG, nWGf);
-      fb.fused.sizeCell = (u64*)cells;
-      fb.fused.baseCell = (u64*)cells + nCell;
-      fb.fused.totalCell = (u64*)cells + nCell + nFused;
-      fb.fused.raise = (u64*)cells + nCell + 2 * nFused;
-      fb.fused.packPart = (u64*)counters;
-      fb.fused.keyPart = (u64*)counters + nGroups + 1;
-      fb.fused.nWG = nWGf;
-    }
-  }
-  else
-  {
-    fb.desc = ctx.allocT<FastBlockDesc>(nT * nWG * kFastBlocksPerWG);
-    fb.wgSize = ctx.allocT<u32>(nT * fastWgStride(nWG) + 4);
-    fb.wgBase = ctx.allocT<u32>(nT * fastWgStride(nWG) + 4);
-    fb.wgMinKey = ctx.allocT<u64>(nT * nWG + 4);
-    fb.wgMaxKey = ctx.allocT<u64>(nT * nWG + 4);
-    fb.wgFlags = ctx.allocT<u32>(nT * nWG + 4);
-    fb.groupBase = ctx.allocT<u32>(nT * (fastScanGroups(nWG) + 1) + 4);
-    fb.scanPart = ctx.allocT<u64>(kScanPartWords * nT * fastScanGroups(nWG) + 4);
-    fb.packPart = ctx.allocT<u64>(nT * fastPackGroups(nWG) + 4);
-    fb.tickets = ctx.allocT<u32>(nT * fastTicketStride(nWG) + 4);
-    fb.result = ctx.allocT<FastEncodeResult>(nT);
-    fb.prefixStage = ctx.allocT<u8>(nT * kFastPrefixStage);
-    fb.tileOffset = arena ? ctx.allocT<u64>(nT + 1) : nullptr;
-    if (!fb.desc || !fb.wgSize || !fb.wgBase || !fb.wgMinKey || !fb.wgMaxKey || !fb.wgFlags || !fb.result
-      || !fb.groupBase || !fb.scanPart || !fb.packPart || !fb.tickets
-      || !fb.prefixStage || (arena && !fb.tileOffset))
-      return false;
-  }
-  fl.cand = 0;
-  if (isFlt)
-  {
-    static const double errCand[9] = { 1, 0.5, 0.1, 0.05, 0.01, 0.005, 0.001, 0.0005, 0.0001 };
-    for (int c = 0; c < 9; c++) if (errCand[c] / 2 > maxZErr) fl.cand |= 1u << c;
-  }
-  BandParams& bp = fl.bp;
-  memset(&bp, 0, sizeof(bp));
-  bp.nRows = nRows; bp.nCols = nCols; bp.nDepth = 1; bp.dt = dt; bp.version = kCodecVersion;
-  bp.mb = 8; bp.nTV = (nRows + 7) / 8; bp.nTH = (nCols + 7) / 8;
-  bp.allValid = 1;
-  bp.maxQ = maxValToQuantize(dt);
-  bp.maxZErr = isFlt ? maxZErr : std::max(0.5, floor(maxZErr));
-  bp.scale = 1 / (2 * bp.maxZErr);
-  bp.invScale = 2 * bp.maxZErr;
-  bp.intLossless = (!isFlt && bp.maxZErr == 0.5) ? 1 : 0;
-  fl.maxZErr = maxZErr;
-  return true;
+  bool any = false;
+  if (rq.hUsesNoData) for (int i = 0; i < rq.nBands; i++) any = any || rq.hUsesNoData[i] != 0;
+  return any;
 }
-
-static void runFastEncode(Context& ctx, const FastEncodeLaunch& fl, const void* dData, u8* dOut, u64 capacity, u64 arenaBase)
-{
-  // one kernel per stage (and per profiling group): statistics (+ first-row rounding errors), scan + decide (+ tile
-  // placement for batches), pack + checksum
-  static const char* kStage[3] = { "fast_stats_sizes", "fast_scan_decide", "fast_pack" };
-  const bool ragged = fl.bp.nRows % 8 != 0 || fl.bp.nCols % 8 != 0;
-  if (fl.fb.fused.sizeCell && (dOut || ragged))    // one raster, one launch (size queries: only where the two-launch form cannot go)
-  {
-    ProfScope ps(ctx, "fast_encode1");
-    FastEncodeBuffers fb = fl.fb;
-    fb.fused.epoch = ctx.nextEpoch();    // (never 0, the tag of a cell nobody has written yet)
-    fb.fused.publishEpoch = (fastTestGiveUp() & 1u) ? fb.fused.epoch ^ 0x5A5A5A5Au : fb.fused.epoch;
-    fb.fused.spinLimit = (fastTestGiveUp() & 1u) ? 8u : (1u << 22);
-    launchFastEncode(0, fl.bp, fl.maxZErr, fl.cand, dData, dOut, capacity, arenaBase, fb, fl.batch, ctx.activeStream());
-    return;
-  }
-  // (no output buffer: the size is known after the decisions -- one raster: the pack step's last workgroup takes them)
-  const int nStages = (dOut || fl.fb.solo.cells) ? 3 : 2;
-  for (int stage = 0; stage < nStages; stage++)
-  {
-    if (stage == 1 && fl.fb.solo.cells) continue;    // (one raster: the pack step scans and decides itself)
-    ProfScope ps(ctx, kStage[stage]);
-    FastEncodeBuffers fb = fl.fb;
-    if (stage == 2 && fb.solo.cells) fb.solo.epoch = ctx.nextEpoch();    // (never 0, the tag of a cell nobody has written yet)
-    launchFastEncode(stage, fl.bp, fl.maxZErr, fl.cand, dData, dOut, capacity, arenaBase, fb, fl.batch, ctx.activeStream());
-  }
-}
-
-// single band requests the streaming kernels can take (the same test encodeDevice makes)
 static bool encodeStreamingOk(const EncodeRequest& rq)
 {
-  bool anyNoData = false;
-  if (rq.hUsesNoData) for (int i = 0; i < rq.nBands; i++) anyNoData = anyNoData || rq.hUsesNoData[i] != 0;
-  return !anyNoData && rq.version == kCodecVersion && rq.maxZErr != 777 && ((uintptr_t)rq.dOut & 15) == 0 && ((uintptr_t)rq.dData & 15) == 0
-    && fastEncodeEligible(rq.dt, rq.nRows, rq.nCols, rq.nDepth, rq.nMasks > 0, rq.maxZErr, fastEncodeOneLaunch());
+  return streamingEligible(rq.dt, rq.nRows, rq.nCols, rq.nDepth, rq.nMasks > 0, !anyNoData(rq) && rq.version == kCodecVersion, rq.maxZErr,
+                           rq.dData, rq.dOut, 0);
+}
+
+// ---- the kernels' parameters
+BandParams fastBandParams(int dt, int nRows, int nCols, double maxZErr)
+{
+  // integer types: Lerc2 rounds the bound down to a whole number, and a bound below 1 is lossless (0.5).  So the bound is > 0 here: a
+  // float request with maxZErr == 0 never gets this far (fastEncodeEligible refuses it, the entry points refuse negative bounds), and
+  // makeBandParams' scale -- 0 for a bound of 0 -- is 1 / (2 * maxZErr)
+  const bool isFlt = dt >= DT_Float;
+  BandParams bp = makeBandParams(dt, nRows, nCols, 1, kCodecVersion, 8, isFlt ? maxZErr : std::max(0.5, floor(maxZErr)), true);
+  bp.intLossless = (!isFlt && bp.maxZErr == 0.5) ? 1 : 0;
+  return bp;
+}
+u32 raiseCandidates(int dt, double maxZErr)
+{
+  static const double errCand[9] = { 1, 0.5, 0.1, 0.05, 0.01, 0.005, 0.001, 0.0005, 0.0001 };
+  u32 cand = 0;
+  if (dt >= DT_Float) for (int c = 0; c < 9; c++) if (errCand[c] / 2 > maxZErr) cand |= 1u << c;
+  return cand;
+}
+
+// ---- one launch sequence of the streaming kernels over nTiles rasters of one shape (a single raster, a band of a stack: nTiles == 1)
+struct FastEncodePlan
+{
+  // kOneLaunch     k_fast_encode1: statistics, block decisions, pack and checksum from one read (a tile per blockIdx.y)
+  // kTwoLaunches   one raster: statistics, then a pack step whose first blocks scan and decide (LERC_AMD_ENCODE_LAUNCHES=2; every size query of whole blocks)
+  // kThreeLaunches statistics, scan + decide (+ the tiles' places in the arena), pack: a tile batch under that knob; a raster beyond the others' 32-bit byte counts
+  enum Form { kOneLaunch, kTwoLaunches, kThreeLaunches };
+  // where the blobs go.  kOwnBuffer: one raster, into the buffer given to launch().  A batch: kSlots -- every tile has its place, t * slotBytes;
+  // kCursor -- straight into the arena, a tile's last workgroup claims the tile's room with an atomic add on the batch's cursor (tile_fast.h:
+  // FastFused::arenaCursor), the tiles lie in the order of their claims; kCopy -- into slots of the workspace, then placed and moved
+  // (k_fast_tile_copy); kPlaced -- the three-launch form: its second step places the tiles, its third packs them there
+  enum Arena { kOwnBuffer, kSlots, kCursor, kCopy, kPlaced };
+  Form form;
+  Arena arena;
+  int dt, nRows, nCols;
+  u32 nTiles, nWG, nCell;    // nWG: workgroups of 64 blocks a raster; nCell: workgroups a raster whose cells the persistent areas hold
+  u64 tileElems, slotBytes, arenaCapacity = 0;
+  u8* dArena = nullptr;
+  FastEncodeBuffers fb;
+  FastBatch batch;
+  BandParams bp;
+  u32 cand; double maxZErr;
+  u8* slots = nullptr;       // kCopy: the slots
+  u64* dOff = nullptr;       // a batch: [nTiles + 1] where the tiles lie in the arena
+  const FastEncodeResult* res = nullptr; const u64* off = nullptr;    // (after fetch(), in pinned memory)
+  u64 claimed = 0;           // kCursor: bytes the batch has claimed (incl. the room of tiles that were handed back: holes)
+  FastEncodePlan(int dt_, int nRows_, int nCols_, double maxZErr_, u32 nTiles_ = 1, Arena arena_ = kOwnBuffer, u64 slotBytes_ = 0)
+    : arena(arena_), dt(dt_), nRows(nRows_), nCols(nCols_), nTiles(nTiles_), nWG(fastEncodeNumWG(nRows_, nCols_)),
+      tileElems(arena_ == kOwnBuffer ? 0 : (u64)nRows_ * (u64)nCols_), slotBytes(slotBytes_), bp(fastBandParams(dt_, nRows_, nCols_, maxZErr_)),
+      cand(raiseCandidates(dt_, maxZErr_)), maxZErr(maxZErr_)
+  {
+    const bool one = fastEncodeOneLaunch();
+    if (arena == kOwnBuffer) form = !fastSoloOk(dt, nRows, nCols) ? kThreeLaunches : one ? kOneLaunch : kTwoLaunches;
+    else form = arena == kPlaced ? kThreeLaunches : kOneLaunch;
+    const u32 nWGf = fastFusedNumWG(dt, nRows, nCols);    // (the one-launch form counts its own workgroups)
+    nCell = oneRaster() ? (one ? std::max(nWG, nWGf) : nWG) : nWGf;    // (one raster keeps cells for both of its forms)
+    memset(&fb, 0, sizeof(fb));
+    if (form == kOneLaunch) fb.fused.nWG = nWGf;
+    batch.nTiles = nTiles; batch.nWG = (form == kOneLaunch && !oneRaster()) ? nWGf : nWG; batch.tileElems = tileElems; batch.nBlobsMore = 0;
+  }
+  bool oneRaster() const { return arena == kOwnBuffer && form != kThreeLaunches; }
+  // the staged forms' buffers for n rasters (one raster's one launch keeps them too, for its size queries)
+  static size_t stagedBytes(int nRows, int nCols, u32 n)
+  {
+    const size_t nWG = fastEncodeNumWG(nRows, nCols);
+    return (size_t)n * (nWG * (kFastBlocksPerWG * sizeof(FastBlockDesc) + 64) + kFastPrefixStage + sizeof(FastEncodeResult)
+                        + (fastScanGroups((u32)nWG) + 1) * (4 + 8 * kScanPartWords) + fastPackGroups((u32)nWG) * 16 + fastTicketStride((u32)nWG) * 4 + 256)
+      + 65536;
+  }
+  size_t workspaceBytes() const
+  {
+    // (a batch in one launch: the results, the cursor and the offsets -- and the slots where the blobs are moved afterwards)
+    if (form == kOneLaunch && !oneRaster()) return (size_t)nTiles * ((arena == kCopy ? slotBytes : 0) + sizeof(FastEncodeResult) + 8) + (1u << 16);
+    return stagedBytes(nRows, nCols, nTiles);
+  }
+  // carves the plan's buffers out of the context's two persistent areas ([0] counters the kernels leave zero, [1] epoch-tagged cells)
+  // and the bump workspace (reserve() first): every per-raster array holds nTiles consecutive sets
+  bool layout(Context& ctx)
+  {
+    const size_t nT = nTiles;
+    const bool raster = oneRaster(), three = form == kThreeLaunches;
+    const u32 nGrp = fastFusedGroups(nCell), nPack = fastPackGroups(nCell);
+    const size_t cellWords = fastFusedCellWords(nCell), counterWords = fastFusedCounterWords(nCell);
+    u64 *cells = nullptr, *counters = nullptr;
+    if (!three)
+    {
+      // (cells: per workgroup, then the one-launch form's group cells and first-row errors -- kCursor: and a cell a tile behind all sets; counters: pack accumulators, key cells)
+      cells = (u64*)ctx.persistentState(1, nT * (cellWords + (arena == kCursor ? 1 : 0)) * 8 + 256);
+      counters = (u64*)ctx.persistentState(0, nT * counterWords * 8 + 256);
+      if (!cells || !counters) return false;
+    }
+    if (raster || three)
+    {
+      // (one raster: the pack step's first blocks scan and decide, tile_fast.h -- no scan buffers, the accumulators and cells persistent)
+      fb.desc = ctx.allocT<FastBlockDesc>(nT * nWG * kFastBlocksPerWG);
+      fb.wgSize = ctx.allocT<u32>(nT * fastWgStride(nWG) + 4);
+      if (three) fb.wgBase = ctx.allocT<u32>(nT * fastWgStride(nWG) + 4);
+      fb.wgMinKey = ctx.allocT<u64>(nT * nWG + 4);
+      fb.wgMaxKey = ctx.allocT<u64>(nT * nWG + 4);
+      fb.wgFlags = ctx.allocT<u32>(nT * nWG + 4);
+      if (three) fb.groupBase = ctx.allocT<u32>(nT * (fastScanGroups(nWG) + 1) + 4);
+      if (three) fb.scanPart = ctx.allocT<u64>(kScanPartWords * nT * fastScanGroups(nWG) + 4);
+      if (three) fb.packPart = ctx.allocT<u64>(nT * fastPackGroups(nWG) + 4);
+      fb.tickets = ctx.allocT<u32>(nT * fastTicketStride(nWG) + 4);
+      fb.result = ctx.allocT<FastEncodeResult>(nT);
+      fb.prefixStage = ctx.allocT<u8>(nT * kFastPrefixStage);
+      if (arena == kPlaced) dOff = fb.tileOffset = ctx.allocT<u64>(nT + 1);
+      if (!fb.desc || !fb.wgSize || !fb.wgMinKey || !fb.wgMaxKey || !fb.wgFlags || !fb.tickets || !fb.result || !fb.prefixStage
+        || (three && (!fb.wgBase || !fb.groupBase || !fb.scanPart || !fb.packPart)) || (arena == kPlaced && !dOff))
+        return false;
+      if (raster) { fb.packPart = counters; fb.solo.cells = cells; }
+    }
+    else
+    {
+      if (arena == kCopy) slots = ctx.allocT<u8>(nT * slotBytes);
+      // (the results and, behind them, the batch's cursor: cleared by one memset)
+      static_assert(sizeof(FastEncodeResult) % 8 == 0, "the cursor behind the results is 8-byte aligned");
+      fb.result = (FastEncodeResult*)ctx.alloc(nT * sizeof(FastEncodeResult) + 16);
+      dOff = ctx.allocT<u64>(nT + 1);
+      if ((arena == kCopy && !slots) || !fb.result || !dOff) return false;
+    }
+    if (form != kOneLaunch) return true;
+    FastFused& f = fb.fused;
+    f.sizeCell = cells; f.baseCell = f.sizeCell + nCell; f.totalCell = f.baseCell + nGrp; f.raise = f.totalCell + nGrp;
+    f.packPart = counters; f.keyPart = f.packPart + nPack + 1;
+    if (raster) return true;
+    f.nTiles = nTiles; f.cellStride = (u32)cellWords; f.counterStride = (u32)counterWords;
+    f.tileElems = tileElems; f.outStride = arena == kCursor ? 0 : slotBytes;
+    if (arena != kCursor) return true;
+    f.arenaCursor = reinterpret_cast<u64*>(reinterpret_cast<u8*>(fb.result) + nT * sizeof(FastEncodeResult));
+    f.tileCell = cells + nT * cellWords;    // (epoch-tagged, behind the tiles' own cells)
+    f.tileOffset = dOff;
+    f.arenaCapacity = arenaCapacity;
+    return true;
+  }
+  // a launch's tag (never 0, the tag of a cell nobody has written yet), and how long its workgroups wait for each other
+  void arm(Context& ctx, Form now)
+  {
+    const u32 epoch = ctx.nextEpoch();
+    if (now == kTwoLaunches) { fb.solo.epoch = epoch; return; }
+    const bool giveUp = (fastTestGiveUp() & 1u) != 0;    // (the test knob: nobody ever sees a cell arrive, every waiter gives up after a few polls)
+    fb.fused.epoch = epoch;
+    fb.fused.publishEpoch = giveUp ? epoch ^ 0x5A5A5A5Au : epoch;
+    fb.fused.spinLimit = giveUp ? 8u : (1u << 22);
+#ifdef HIPSIM
+    // (the emulator runs workgroups one after the other: one that waits for one BEHIND it gives up after a few polls -- the hand-back path's test)
+    if (arena == kCursor) fb.fused.spinLimit = 64u;
+#endif
+  }
+  // one kernel per stage (and per profiling group): statistics (+ first-row rounding errors), scan + decide (+ tile placement for
+  // batches), pack + checksum -- or all of it in one.  arenaBase: where a batch's first byte goes
+  void launch(Context& ctx, const void* dData, u8* out, u64 capacity, u64 arenaBase = 0)
+  {
+    static const char* kStage[3] = { "fast_stats_sizes", "fast_scan_decide", "fast_pack" };
+    hipStream_t st = ctx.activeStream();
+    // (one raster, no output buffer: one launch only where the two-launch form cannot go)
+    const Form now = (form == kOneLaunch && oneRaster() && !out && nRows % 8 == 0 && nCols % 8 == 0) ? kTwoLaunches : form;
+    if (now != kThreeLaunches) arm(ctx, now);
+    if (now == kOneLaunch)
+    {
+      if (arena == kCursor) fb.fused.arenaBase = arenaBase;
+      if (!oneRaster()) hipMemsetAsync(fb.result, 0, (size_t)nTiles * sizeof(FastEncodeResult) + 16, st);    // (the kernels raise `stuck`, nobody else clears it; the cursor)
+      {
+        ProfScope ps(ctx, "fast_encode1");
+        launchFastEncode(0, bp, maxZErr, cand, dData, out, capacity, 0, fb, batch, st);
+      }
+      if (arena != kCopy) return;
+      ProfScope ps(ctx, "fast_tile_move");
+      launchFastTileCopy(fb.result, dOff, slots, slotBytes, slotBytes, dArena, nTiles, arenaBase, arenaCapacity, st);
+      return;
+    }
+    for (int stage = 0; stage < 3; stage++)
+    {
+      if (stage == 1 && now == kTwoLaunches) continue;      // (one raster: the pack step scans and decides itself)
+      if (stage == 2 && now == kThreeLaunches && !out) continue;    // (no output buffer: the size is known after the decisions)
+      ProfScope ps(ctx, kStage[stage]);
+      launchFastEncode(stage, bp, maxZErr, cand, dData, out, capacity, arenaBase, fb, batch, st);
+    }
+  }
+  // a batch's results (+ the cursor) and offsets on their way into pinned memory; waits for the stream
+  bool fetch(Context& ctx)
+  {
+    hipStream_t st = ctx.activeStream();
+    const size_t resBytes = (size_t)nTiles * sizeof(FastEncodeResult) + (form == kOneLaunch ? 16 : 0), offBytes = ((size_t)nTiles + 1) * 8;
+    u8* pin = (u8*)ctx.pinned(resBytes + offBytes);
+    if (!pin) return false;
+    hipMemcpyAsync(pin, fb.result, resBytes, hipMemcpyDeviceToHost, st);
+    if (arena != kSlots) hipMemcpyAsync(pin + resBytes, dOff, offBytes, hipMemcpyDeviceToHost, st);
+    if (!ctx.sync()) return false;
+    if (ctx.profOn()) ctx.profCollect();
+    res = reinterpret_cast<const FastEncodeResult*>(pin);
+    off = reinterpret_cast<const u64*>(pin + resBytes);
+    if (arena == kCursor) memcpy(&claimed, pin + (size_t)nTiles * sizeof(FastEncodeResult), 8);
+    return true;
+  }
+};
+
+// ---- what became of the rasters of a launch, read from their results once the stream has passed them.  The only place that counts
+// streaming encodes: pathCount[0] (calls; every tile of a batch is one) and tileBatchCount[0]
+struct FastHarvest
+{
+  enum Count { kCountNothing, kCountCalls, kCountTiles };
+  std::vector<std::pair<int, u32> > back;    // the rasters handed back: index, reason bits (FastRedo) -- 0 where a workgroup gave up waiting
+  unsigned long long nDone = 0;
+  Count counted = kCountNothing;
+  bool arenaFull = false;                    // a tile says that the batch's ARENA is full: the call is over, nothing behind that tile was read
+  // sign -1: the batch is run again, what it has counted is taken back
+  static void credit(Context& ctx, Count what, unsigned long long n, int sign = 1)
+  {
+    if (what != kCountNothing) ctx.pathCount[0] += sign > 0 ? n : 0ull - n;
+    if (what == kCountTiles) ctx.tileBatchCount[0] += sign > 0 ? n : 0ull - n;
+  }
+  // res[i] is raster first + i; a raster that is done leaves its size in hSizes and its offset -- off[i], or its slot's -- in hOffsets
+  // (where given).  arena: the blobs share an arena that can be full
+  void read(Context& ctx, const FastEncodeResult* res, int n, Count what, bool arena = false, int first = 0, u64* hOffsets = nullptr,
+            u32* hSizes = nullptr, const u64* off = nullptr, u64 slotBytes = 0)
+  {
+    back.clear();
+    counted = what; arenaFull = false;
+    unsigned long long done = 0;
+    bool stuck = false;
+    for (int i = 0; i < n && !arenaFull; i++)
+    {
+      const FastEncodeResult& r = res[i];
+      if (r.redo || r.stuck)
+      {
+        stuck = stuck || r.stuck != 0;
+        if (arena && (r.redoReason & kRedoArena)) arenaFull = true;
+        else back.push_back(std::make_pair(first + i, r.stuck ? 0u : r.redoReason));    // (a tile that does not fit its SLOT says so when it is encoded by itself)
+        continue;
+      }
+      if (hOffsets) hOffsets[first + i] = off ? off[i] : (u64)(first + i) * slotBytes;
+      if (hSizes) hSizes[first + i] = r.blobSize;
+      done++;
+    }
+    credit(ctx, what, nDone = done);
+    if (stuck && !arenaFull) ctx.wipePersistentState();    // (late workgroups may have left residue in the counters)
+  }
+};
+
+// a result the kernels write straight into pinned memory, as it is before they do: if a launch fails, what the operation that had the
+// memory before left there must not read as this one's verdict -- "redo" sends the request to the general path, which reports what is wrong
+static void presetResult(void* slot)
+{
+  FastEncodeResult init;
+  memset(&init, 0, sizeof(init));
+  init.redo = 1u; init.redoReason = kRedoNotLaunched;
+  memcpy(slot, &init, sizeof(init));
 }
 
 bool encodeEnqueueStreaming(Context& ctx, const EncodeRequest& rq, u8* slot)
 {
   if (!slot || rq.nBands != 1 || !encodeStreamingOk(rq)) return false;
   ctx.reset();
-  if (!ctx.reserve(fastEncodeWorkspace(rq.nRows, rq.nCols, 1) + (1u << 16))) return false;
-  FastEncodeLaunch fl;
-  if (!prepareFastEncode(ctx, rq.dt, rq.nRows, rq.nCols, rq.maxZErr, 1, 0, false, fl)) return false;
+  FastEncodePlan plan(rq.dt, rq.nRows, rq.nCols, rq.maxZErr);
+  if (!ctx.reserve(plan.workspaceBytes() + (1u << 16)) || !plan.layout(ctx)) return false;
   // (one raster: the deciding block and the last workgroup write the result straight into `slot`, pinned host memory -- no
   // kernel reads it, and a copy kernel behind the encode would cost every call 4 us)
-  const bool direct = fl.fb.solo.cells != nullptr;
-  if (direct)
-  {
-    // (wiped first: if a launch fails, what the operation that had the slot before left there must not read as this one's
-    // verdict -- "redo" sends the request to the general path, which reports what is wrong)
-    FastEncodeResult init;
-    memset(&init, 0, sizeof(init));
-    init.redo = 1u; init.redoReason = 0x80000000u;
-    memcpy(slot, &init, sizeof(init));
-    fl.fb.result = reinterpret_cast<FastEncodeResult*>(slot);
-  }
+  const bool direct = plan.oneRaster();
+  if (direct) { presetResult(slot); plan.fb.result = reinterpret_cast<FastEncodeResult*>(slot); }
   (void)hipGetLastError();
-  runFastEncode(ctx, fl, rq.dData, rq.dOut, rq.dOut ? (u64)rq.outCapacity : ~0ull, 0);
+  plan.launch(ctx, rq.dData, rq.dOut, rq.dOut ? (u64)rq.outCapacity : ~0ull);
   if (hipGetLastError() != hipSuccess) { ctx.lastError = "lerc_amd: a streaming encode kernel could not be launched"; return false; }
-  return direct || hipMemcpyAsync(slot, fl.fb.result, sizeof(FastEncodeResult), hipMemcpyDeviceToHost, ctx.activeStream()) == hipSuccess;
+  return direct || hipMemcpyAsync(slot, plan.fb.result, sizeof(FastEncodeResult), hipMemcpyDeviceToHost, ctx.activeStream()) == hipSuccess;
 }
 
 void encodeStreamingVerdict(Context& ctx, const EncodeRequest& rq, const u8* slot, bool& redo, u32& status, u32& numBytesNeeded, u32& numBytesWritten)
@@ -194,22 +321,63 @@ void encodeStreamingVerdict(Context& ctx, const EncodeRequest& rq, const u8* slo
   memcpy(&hres, slot, sizeof(hres));
   if (ctx.profOn()) ctx.profCollect();
   redo = false; status = kOk;
-  if (!hres.redo && !hres.stuck)
+  FastHarvest got;
+  got.read(ctx, &hres, 1, FastHarvest::kCountCalls);
+  if (got.back.empty())
   {
-    ctx.pathCount[0]++;
     numBytesNeeded = hres.blobSize;
     numBytesWritten = rq.dOut ? hres.blobSize : 0;
     return;
   }
-  {
-    char msg[160];
-    snprintf(msg, sizeof(msg), "streaming encode handed the band to the general kernels (redo %u, reason bits 0x%x, stuck %u, blob %u bytes)",
-             hres.redo, hres.redoReason, hres.stuck, hres.blobSize);
-    ctx.lastNote = msg;
-  }
-  if (hres.stuck) ctx.wipePersistentState();
-  if (rq.dOut && hres.redoReason == 64u && hres.blobSize > rq.outCapacity) { status = kBufferTooSmall; return; }
+  char msg[160];
+  snprintf(msg, sizeof(msg), "streaming encode handed the band to the general kernels (redo %u, reason bits 0x%x, stuck %u, blob %u bytes)",
+           hres.redo, hres.redoReason, hres.stuck, hres.blobSize);
+  ctx.lastNote = msg;
+  if (rq.dOut && hres.redoReason == kRedoCapacity && hres.blobSize > rq.outCapacity) { status = kBufferTooSmall; return; }
   redo = true;
+}
+
+// several bands: each is a blob of its own with "bands to follow" in its header (Lerc.cpp:628-789); a band is packed into 16-byte
+// aligned scratch (its place in the output is wherever the band before it ended) and copied over.  redo: a band was handed back, the
+// general path takes the whole request
+static u32 encodeBandStack(Context& ctx, const EncodeRequest& rq, size_t bandCap, bool& redo, u32& numBytesNeeded, u32& numBytesWritten)
+{
+  hipStream_t st = ctx.activeStream();
+  const size_t bandBytes = (size_t)rq.nRows * rq.nCols * dtSize(rq.dt);
+  FastEncodePlan plan(rq.dt, rq.nRows, rq.nCols, rq.maxZErr);
+  if (!plan.layout(ctx)) return kFailed;
+  u8* dBandBlob = rq.dOut ? ctx.allocT<u8>(bandCap) : nullptr;
+  FastEncodeResult* pinRes = (FastEncodeResult*)ctx.pinned(sizeof(FastEncodeResult));
+  if (!pinRes || (rq.dOut && !dBandBlob)) return kFailed;
+  const bool direct = plan.oneRaster();    // (the kernels write the result into pinned memory themselves)
+  FastHarvest got;
+  u64 total = 0;
+  redo = false;
+  for (int iBand = 0; iBand < rq.nBands; iBand++)
+  {
+    plan.batch.nBlobsMore = (u32)(rq.nBands - 1 - iBand);
+    if (direct) { presetResult(pinRes); plan.fb.result = pinRes; }
+    plan.launch(ctx, (const u8*)rq.dData + (size_t)iBand * bandBytes, dBandBlob, dBandBlob ? (u64)bandCap : ~0ull);
+    if (!direct) hipMemcpyAsync(pinRes, plan.fb.result, sizeof(FastEncodeResult), hipMemcpyDeviceToHost, st);
+    if (!ctx.sync()) return kFailed;
+    got.read(ctx, pinRes, 1, FastHarvest::kCountNothing);
+    if (!got.back.empty()) { redo = true; break; }
+    const u32 blobBytes = pinRes->blobSize;
+    if (total + blobBytes > (u64)UINT_MAX) return kDimsTooLarge;
+    if (rq.dOut)
+    {
+      if (total + blobBytes > rq.outCapacity) return kBufferTooSmall;
+      hipMemcpyAsync(rq.dOut + total, dBandBlob, blobBytes, hipMemcpyDeviceToDevice, st);
+    }
+    total += blobBytes;
+  }
+  if (ctx.profOn()) ctx.profCollect();
+  if (redo) return kOk;
+  if (rq.dOut && !ctx.sync()) return kFailed;
+  FastHarvest::credit(ctx, FastHarvest::kCountCalls, 1);    // (a call counts once)
+  numBytesNeeded = (u32)total;
+  numBytesWritten = rq.dOut ? (u32)total : 0;
+  return kOk;
 }
 
 u32 encodeDevice(Context& ctx, const EncodeRequest& rq, u32& numBytesNeeded, u32& numBytesWritten)
@@ -222,112 +390,75 @@ u32 encodeDevice(Context& ctx, const EncodeRequest& rq, u32& numBytesNeeded, u32
   // workspace: two bit masks, block sizes + offsets + scan scratch, one-sweep ranks, Huffman scratch, small stuff
   size_t need = 2 * maskBytes + 3 * (nPos8 + 1024) * 4 + 3 * ((size_t)(nPix >> 5) + 1024) * 4
     + (rq.dt <= DT_Byte ? huffmanScratchBytes(nPix, rq.nDepth) : 0) + (size_t)rq.nDepth * 16 + (1u << 16);
-  bool anyNoData = false;
-  if (rq.hUsesNoData) for (int i = 0; i < rq.nBands; i++) anyNoData = anyNoData || rq.hUsesNoData[i] != 0;
-  if (anyNoData && !rq.hNoDataValues) return kWrongParam;
-  if (anyNoData) need += (size_t)nPix * rq.nDepth * tb + (size_t)nPix + 8192;
+  const bool noData = anyNoData(rq);
+  if (noData && !rq.hNoDataValues) return kWrongParam;
+  if (noData) need += (size_t)nPix * rq.nDepth * tb + (size_t)nPix + 8192;
   if (rq.nMasks > 0 || rq.dt >= DT_Float) need += maskRleScratchBytes(maskBytes) + (4u << 20) + 8192;    // a large mask is run-length coded on the device
-  if (rq.dt >= DT_Float && (rq.maxZErr == 0 || anyNoData) && rq.version >= 6) need += fplEncodeScratchBytes(nPix * rq.nDepth, tb);
-  // (a size query, dOut == nullptr, takes the first two steps of the streaming path: statistics and decisions)
+  if (rq.dt >= DT_Float && (rq.maxZErr == 0 || noData) && rq.version >= 6) need += fplEncodeScratchBytes(nPix * rq.nDepth, tb);
   if (rq.version < 2 || rq.version > kCodecVersion) return kWrongParam;
-  if (rq.version < 6 && anyNoData) return kWrongParam;    // Lerc.cpp:341-344
+  if (rq.version < 6 && noData) return kWrongParam;    // Lerc.cpp:341-344
   if (rq.version < 4 && rq.nDepth > 1) return kFailed;    // Lerc2::Set refuses (Lerc2.cpp:85-86)
-  const bool fastOk = !anyNoData && rq.version == kCodecVersion && rq.maxZErr != 777 && ((uintptr_t)rq.dOut & 15) == 0 && ((uintptr_t)rq.dData & 15) == 0
-    && fastEncodeEligible(rq.dt, rq.nRows, rq.nCols, rq.nDepth, rq.nMasks > 0, rq.maxZErr, fastEncodeOneLaunch());
-  const u32 nWG = fastOk ? fastEncodeNumWG(rq.nRows, rq.nCols) : 0;
-  need += fastOk ? fastEncodeWorkspace(rq.nRows, rq.nCols, 1) : 0;
+  // (a size query, dOut == nullptr, takes the streaming path too: its statistics and decisions)
+  const bool fastOk = encodeStreamingOk(rq);
+  need += fastOk ? FastEncodePlan::stagedBytes(rq.nRows, rq.nCols, 1) : 0;
   const size_t bandCap = (size_t)nPix * tb + 4096;    // a band's blob never exceeds its raw form by more than the small sections
   if (fastOk && rq.nBands > 1 && rq.dOut) need += bandCap + 256;
-  (void)nWG;
   if (!ctx.reserve(need)) return kFailed;
-  (void)tb;
 
-  // ---- streaming path: everything is decided on the device, one synchronisation at the end.  If an
-  // assumption fails (NaN, all-integer floats, raisable error bound, constant image, 16 x 16 retry,
-  // raw fallback) the device says so and the general path below redoes the band.
-  if (fastOk && rq.nBands > 1)
+  // ---- streaming path: everything is decided on the device, one synchronisation at the end.  If an assumption fails (NaN, all-integer floats,
+  // raisable error bound, constant image, 16 x 16 retry, raw fallback) the device says so and the general path below redoes the band.
+  if (fastOk)
   {
-    // several bands: each is a blob of its own with "bands to follow" in its header (Lerc.cpp:628-789); a band is packed
-    // into 16-byte aligned scratch (its place in the output is wherever the band before it ended) and copied over
-    hipStream_t st = ctx.activeStream();
-    FastEncodeLaunch fl;
-    if (!prepareFastEncode(ctx, rq.dt, rq.nRows, rq.nCols, rq.maxZErr, 1, 0, false, fl)) return kFailed;
-    u8* dBandBlob = rq.dOut ? ctx.allocT<u8>(bandCap) : nullptr;
-    FastEncodeResult* pinRes = (FastEncodeResult*)ctx.pinned(sizeof(FastEncodeResult));
-    if (!pinRes || (rq.dOut && !dBandBlob)) return kFailed;
-    u64 total = 0;
-    bool redo = false;
-    for (int iBand = 0; iBand < rq.nBands && !redo; iBand++)
-    {
-      fl.batch.nBlobsMore = (u32)(rq.nBands - 1 - iBand);
-      const u8* dBand = (const u8*)rq.dData + (size_t)iBand * nPix * tb;
-      const bool direct = fl.fb.solo.cells != nullptr;    // (the kernels write the result into pinned memory themselves)
-      if (direct) { memset(pinRes, 0, sizeof(*pinRes)); pinRes->redo = 1u; pinRes->redoReason = 0x80000000u; fl.fb.result = pinRes; }
-      runFastEncode(ctx, fl, dBand, dBandBlob, dBandBlob ? (u64)bandCap : ~0ull, 0);
-      if (!direct) hipMemcpyAsync(pinRes, fl.fb.result, sizeof(FastEncodeResult), hipMemcpyDeviceToHost, st);
-      if (!ctx.sync()) return kFailed;
-      if (pinRes->stuck) ctx.wipePersistentState();
-      if (pinRes->redo || pinRes->stuck) { redo = true; break; }
-      const u32 bandBytes = pinRes->blobSize;
-      if (total + bandBytes > (u64)UINT_MAX) return kDimsTooLarge;
-      if (rq.dOut)
-      {
-        if (total + bandBytes > rq.outCapacity) return kBufferTooSmall;
-        hipMemcpyAsync(rq.dOut + total, dBandBlob, bandBytes, hipMemcpyDeviceToDevice, st);
-      }
-      total += bandBytes;
-    }
-    if (ctx.profOn()) ctx.profCollect();
-    if (!redo)
-    {
-      if (rq.dOut && !ctx.sync()) return kFailed;
-      ctx.pathCount[0]++;
-      numBytesNeeded = (u32)total;
-      numBytesWritten = rq.dOut ? (u32)total : 0;
-      return kOk;
-    }
-    ctx.reset();
-  }
-  else if (fastOk)
-  {
-    FastEncodeResult* pinRes = (FastEncodeResult*)ctx.pinned(sizeof(FastEncodeResult));
-    if (!pinRes) return kFailed;
-    if (!encodeEnqueueStreaming(ctx, rq, reinterpret_cast<u8*>(pinRes))) return kFailed;
-    if (!ctx.sync()) return kFailed;
     bool redo = false;
     u32 status = kOk;
-    encodeStreamingVerdict(ctx, rq, reinterpret_cast<const u8*>(pinRes), redo, status, numBytesNeeded, numBytesWritten);
+    if (rq.nBands > 1) status = encodeBandStack(ctx, rq, bandCap, redo, numBytesNeeded, numBytesWritten);
+    else
+    {
+      FastEncodeResult* pinRes = (FastEncodeResult*)ctx.pinned(sizeof(FastEncodeResult));
+      if (!pinRes || !encodeEnqueueStreaming(ctx, rq, reinterpret_cast<u8*>(pinRes)) || !ctx.sync()) return kFailed;
+      encodeStreamingVerdict(ctx, rq, reinterpret_cast<const u8*>(pinRes), redo, status, numBytesNeeded, numBytesWritten);
+    }
     if (!redo) return status;
     ctx.reset();
   }
-
   return encodeBands(ctx, rq, numBytesNeeded, numBytesWritten);
 }
 
-// ------------------------------------------------------------------------------------------------
-// A mosaic's worth of independent tiles in one call: every tile becomes its own blob (own header, ranges,
-// checksum), byte for byte what encodeDevice() makes of it; the blobs go into one arena at 16-byte aligned offsets.
-// Tiles the streaming kernels hand back (constant tiles, NaNs, ...) are encoded one by one behind their sub-batch.
-// ------------------------------------------------------------------------------------------------
-u32 encodeTilesDevice(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed)
+// ---- a mosaic's worth of independent tiles in one call: every tile becomes its own blob (own header, ranges, checksum), byte for byte
+// what encodeDevice() makes of it; the blobs go into one arena at 16-byte aligned offsets.  Tiles the streaming kernels hand back
+// (constant tiles, NaNs, ...) are encoded one by one behind their sub-batch.
+struct TileBatchEncoder
 {
-  arenaUsed = 0;
-  if (!rq.dData || !rq.dArena || !rq.hOffsets || !rq.hSizes || rq.nTiles <= 0 || rq.nRows <= 0 || rq.nCols <= 0 || rq.dt < 0 || rq.dt > DT_Double
-    || rq.maxZErr < 0 || (rq.slotBytes & 15u) != 0)
-    return kWrongParam;
-  if (tilesBytesEncodeEligible(rq)) return encodeTilesBytes(ctx, rq, arenaUsed);    // (8-bit: the Huffman decision, a tile per workgroup)
-  const bool slotted = rq.slotBytes != 0;    // every tile has its place: no arena to fill front to back
-  const int tb = dtSize(rq.dt);
-  const u64 tileElems = (u64)rq.nRows * (u64)rq.nCols;
-  // (tiles whose sides are no multiples of 8 -- 257 x 257 elevation tiles -- go through the one-launch encoder's ragged form, pixel by
-  // pixel where rows do not start on 16-byte boundaries; whole-block tiles must lie 16 bytes apart)
-  const bool raggedTile = rq.nRows % 8 != 0 || rq.nCols % 8 != 0;
-  const bool fastOk = rq.maxZErr != 777 && ((uintptr_t)rq.dArena & 15) == 0 && ((uintptr_t)rq.dData & 15) == 0
-    && (raggedTile ? fastEncodeOneLaunch() : (tileElems * tb) % 16 == 0)
-    && fastEncodeEligible(rq.dt, rq.nRows, rq.nCols, 1, false, rq.maxZErr, raggedTile);
-  u64 end = 0;    // arena bytes in use
+  Context& ctx; const TilesEncodeRequest& rq;
+  const int tb; const u64 tileElems;
+  const bool slotted;      // every tile has its place: no arena to fill front to back
+  bool direct;             // the one-launch encoder's blobs go straight into the arena (FastEncodePlan::kCursor): no slots, no pass that moves them
+  // the one-launch encoder's slots, a tile each: half the tile's raw size -- a tile that needs more is encoded by itself afterwards -- and,
+  // for a batch full of such tiles, slots that hold raw blocks
+  u64 slotBytes, slotBig;
+  u64 end = 0;             // arena bytes in use
+  static constexpr int kFewTooBig = 8;    // so many tiles (or a 32nd of the batch, if that is more) that outgrow their slots are encoded one by one
 
-  auto encodeOne = [&](int t) -> u32
+  TileBatchEncoder(Context& c, const TilesEncodeRequest& r)
+    : ctx(c), rq(r), tb(dtSize(r.dt)), tileElems((u64)r.nRows * (u64)r.nCols), slotted(r.slotBytes != 0)
+  {
+    // LERC_AMD_TILE_ARENA=copy keeps the slots + k_fast_tile_copy form (a knob for A/B runs and tests).  Emulator builds keep it unless
+    // asked: they run workgroups one after the other, and a tile's workgroups wait for its LAST one's claim (FastEncodePlan::arm)
+#ifdef HIPSIM
+    static const bool cursorMode = []() { const char* e = getenv("LERC_AMD_TILE_ARENA"); return e && strcmp(e, "cursor") == 0; }();
+#else
+    static const bool cursorMode = []() { const char* e = getenv("LERC_AMD_TILE_ARENA"); return !(e && strcmp(e, "copy") == 0); }();
+#endif
+    direct = !slotted && cursorMode;
+    slotBytes = slotted ? rq.slotBytes : ((tileElems * tb / 2 + 4096) + 15) & ~15ull;
+    slotBig = slotted ? rq.slotBytes : ((tileElems * tb + tileElems / 64 + 4096) + 15) & ~15ull;
+  }
+  FastEncodePlan::Arena arena() const
+  {
+    return !fastEncodeOneLaunch() ? FastEncodePlan::kPlaced : slotted ? FastEncodePlan::kSlots : direct ? FastEncodePlan::kCursor : FastEncodePlan::kCopy;
+  }
+  // tile t by itself, behind what the arena holds (or into its slot)
+  u32 encodeOne(int t)
   {
     end = slotted ? (u64)t * rq.slotBytes : (end + 15) & ~15ull;
     EncodeRequest one;
@@ -343,205 +474,74 @@ u32 encodeTilesDevice(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed
     end += written;
     ctx.tileBatchCount[1]++;
     return kOk;
-  };
-
-  if (slotted && rq.arenaCapacity < (u64)rq.nTiles * rq.slotBytes) return kBufferTooSmall;
-  if (!fastOk || (slotted && !fastEncodeOneLaunch()))
+  }
+  // one launch sequence for tiles [t0, t0 + n), the one-launch encoder's blobs in slots of `slot` bytes; then the tiles it hands back, one
+  // by one (they reuse the workspace: the batch is done with it) -- unless the batch is to be run once more, with larger slots
+  u32 runBatch(int t0, int n, u64 slot, bool& onceMore)
   {
-    for (int t = 0; t < rq.nTiles; t++) { const u32 rc = encodeOne(t); if (rc != kOk) return rc; }
-    arenaUsed = slotted ? (u64)rq.nTiles * rq.slotBytes : end;
+    FastEncodePlan plan(rq.dt, rq.nRows, rq.nCols, rq.maxZErr, (u32)n, arena(), slot);
+    plan.dArena = rq.dArena; plan.arenaCapacity = rq.arenaCapacity;
+    if (!ctx.reserve(plan.workspaceBytes()) || !plan.layout(ctx)) return kFailed;
+    const u64 end0 = end = (end + 15) & ~15ull;
+    u8* out = slotted ? rq.dArena + (size_t)t0 * slot : plan.arena == FastEncodePlan::kCopy ? plan.slots : rq.dArena;
+    (void)hipGetLastError();
+    plan.launch(ctx, (const u8*)rq.dData + (size_t)t0 * tileElems * tb, out, (slotted || plan.arena == FastEncodePlan::kCopy) ? slot : rq.arenaCapacity, end);
+    if (hipGetLastError() != hipSuccess) { ctx.lastError = "lerc_amd: a streaming encode kernel could not be launched"; return kFailed; }
+    if (!plan.fetch(ctx)) return kFailed;
+    FastHarvest got;
+    got.read(ctx, plan.res, n, FastHarvest::kCountTiles, !slotted, t0, rq.hOffsets, rq.hSizes, slotted ? nullptr : plan.off, slot);
+    if (got.arenaFull) return kBufferTooSmall;
+    if (plan.arena == FastEncodePlan::kCursor) end += plan.claimed;
+    else if (!slotted) end = plan.off[n];
+    // A tile that compresses to more than half its raw size -- lossless noise, a small error bound -- does not fit the batch's first slots.
+    // A few such tiles are encoded one by one behind the batch; a batch full of them is encoded once more with slots that hold raw blocks,
+    // instead of tile after tile with a wait each.  (Only where the blobs are moved out of their slots: a caller's slots are what they
+    // are, and the cursor form and the three-launch form have none.)
+    size_t tooBig = 0;
+    for (const auto& r : got.back) if (r.second == kRedoCapacity) tooBig++;    // (and nothing else)
+    onceMore = plan.arena == FastEncodePlan::kCopy && slot != slotBig && tooBig > (size_t)std::max(kFewTooBig, n / 32);
+    if (onceMore) { FastHarvest::credit(ctx, got.counted, got.nDone, -1); end = end0; return kOk; }
+    for (const auto& r : got.back) { const u32 rc = encodeOne(r.first); if (rc != kOk) return rc; }
     return kOk;
   }
-
-  hipStream_t st = ctx.activeStream();
-  std::vector<int> redo;
-  if (fastEncodeOneLaunch())
+  u32 run(bool fastOk, u64& arenaUsed)
   {
-    // ---- the one-launch encoder, a tile per blockIdx.y: every tile's blob goes into a slot of its own (half the tile's raw
-    // size: a tile that needs more is encoded by itself afterwards), then the tiles are placed and moved into the arena
-    const u32 nWGt = fastFusedNumWG(rq.dt, rq.nRows, rq.nCols);
-    const size_t cellWords = fastFusedCellWords(nWGt), counterWords = fastFusedCounterWords(nWGt);
-    const u64 slotBytes = slotted ? rq.slotBytes : ((tileElems * tb / 2 + 4096) + 15) & ~15ull;
-    const bool isFlt = rq.dt >= DT_Float;
-    // one launch for tiles [t0, t0 + n), every blob in a slot of slotBytes; redoOut: the tiles it hands back, with the reason bits
-    // An arena is filled WITHOUT slots and without a pass that moves the blobs: a tile's last workgroup claims the tile's room with an
-    // atomic add on the batch's cursor (tile_fast.h: FastFused::arenaCursor), the tiles lie in the order of their claims.
-    // LERC_AMD_TILE_ARENA=copy keeps the slots + k_fast_tile_copy form (a knob for A/B runs and tests).
-    // (The emulator runs workgroups one after the other: a workgroup that waits for one BEHIND it waits for ever there.  Emulator builds keep
-    // the copy form unless asked, and then give up after a few polls -- which is the hand-back path's test.)
-#ifdef HIPSIM
-    static const bool cursorMode = []() { const char* e = getenv("LERC_AMD_TILE_ARENA"); return e && strcmp(e, "cursor") == 0; }();
-#else
-    static const bool cursorMode = []() { const char* e = getenv("LERC_AMD_TILE_ARENA"); return !(e && strcmp(e, "copy") == 0); }();
-#endif
-    const bool direct = !slotted && cursorMode;
-    auto runBatch = [&](int t0, int n, u64 slotBytes, std::vector<std::pair<int, u32> >& redoOut) -> u32
+    if (slotted && rq.arenaCapacity < (u64)rq.nTiles * rq.slotBytes) return kBufferTooSmall;
+    const bool placed = arena() == FastEncodePlan::kPlaced;
+    if (!fastOk || (slotted && placed))    // (tile by tile: what the streaming kernels do not take, and -- the three-launch form has no slots -- a slotted batch under its knob)
     {
-      if (!ctx.reserve((size_t)n * (((slotted || direct) ? 0 : slotBytes) + sizeof(FastEncodeResult) + 8) + (1u << 16))) return kFailed;
-      u8* cells = ctx.persistentState(1, (size_t)n * (cellWords + (direct ? 1 : 0)) * 8 + 256);
-      u8* counters = ctx.persistentState(0, (size_t)n * counterWords * 8 + 256);
-      u8* slots = slotted ? rq.dArena + (size_t)t0 * slotBytes : direct ? rq.dArena : ctx.allocT<u8>((size_t)n * slotBytes);
-      // (the results and, behind them, the batch's cursor: cleared by one memset)
-      FastEncodeResult* dRes = (FastEncodeResult*)ctx.alloc((size_t)n * sizeof(FastEncodeResult) + 16);
-      u64* dCursor = dRes ? reinterpret_cast<u64*>(reinterpret_cast<u8*>(dRes) + (size_t)n * sizeof(FastEncodeResult)) : nullptr;
-      static_assert(sizeof(FastEncodeResult) % 8 == 0, "the cursor behind the results is 8-byte aligned");
-      u64* dOff = ctx.allocT<u64>((size_t)n + 1);
-      if (!cells || !counters || !slots || !dRes || !dOff) return kFailed;
-      FastEncodeLaunch fl;
-      memset(&fl.fb, 0, sizeof(fl.fb));
-      const u32 nG = fastFusedGroups(nWGt), nPG = fastPackGroups(nWGt);
-      FastFused& f = fl.fb.fused;
-      f.sizeCell = (u64*)cells; f.baseCell = f.sizeCell + nWGt; f.totalCell = f.baseCell + nG; f.raise = f.totalCell + nG;
-      f.packPart = (u64*)counters; f.keyPart = f.packPart + nPG + 1;
-      f.nWG = nWGt; f.nTiles = (u32)n; f.cellStride = (u32)cellWords; f.counterStride = (u32)counterWords;
-      f.tileElems = tileElems; f.outStride = slotBytes;
-      end = (end + 15) & ~15ull;
-      if (direct)
-      {
-        f.outStride = 0;
-        f.arenaCursor = dCursor;
-        f.tileCell = (u64*)cells + (size_t)n * cellWords;    // (epoch-tagged, behind the tiles' own cells)
-        f.tileOffset = dOff;
-        f.arenaBase = end; f.arenaCapacity = rq.arenaCapacity;
-      }
-      f.epoch = ctx.nextEpoch();
-      f.publishEpoch = (fastTestGiveUp() & 1u) ? f.epoch ^ 0x5A5A5A5Au : f.epoch;
-      f.spinLimit = (fastTestGiveUp() & 1u) ? 8u : (1u << 22);
-#ifdef HIPSIM
-      if (direct) f.spinLimit = 64u;
-#endif
-      fl.fb.result = dRes;
-      fl.batch.nTiles = (u32)n; fl.batch.nWG = nWGt; fl.batch.tileElems = tileElems; fl.batch.nBlobsMore = 0;
-      fl.cand = 0;
-      if (isFlt)
-      {
-        static const double errCand[9] = { 1, 0.5, 0.1, 0.05, 0.01, 0.005, 0.001, 0.0005, 0.0001 };
-        for (int c = 0; c < 9; c++) if (errCand[c] / 2 > rq.maxZErr) fl.cand |= 1u << c;
-      }
-      BandParams& bp = fl.bp;
-      memset(&bp, 0, sizeof(bp));
-      bp.nRows = rq.nRows; bp.nCols = rq.nCols; bp.nDepth = 1; bp.dt = rq.dt; bp.version = kCodecVersion;
-      bp.mb = 8; bp.nTV = (rq.nRows + 7) / 8; bp.nTH = (rq.nCols + 7) / 8;
-      bp.allValid = 1;
-      bp.maxQ = maxValToQuantize(rq.dt);
-      bp.maxZErr = isFlt ? rq.maxZErr : std::max(0.5, floor(rq.maxZErr));
-      bp.scale = 1 / (2 * bp.maxZErr);
-      bp.invScale = 2 * bp.maxZErr;
-      bp.intLossless = (!isFlt && bp.maxZErr == 0.5) ? 1 : 0;
-      fl.maxZErr = rq.maxZErr;
-      (void)hipGetLastError();
-      hipMemsetAsync(dRes, 0, (size_t)n * sizeof(FastEncodeResult) + 16, st);    // (the kernels raise `stuck`, nobody else clears it; the cursor)
-      {
-        ProfScope ps(ctx, "fast_encode1");
-        launchFastEncode(0, fl.bp, fl.maxZErr, fl.cand, (const u8*)rq.dData + (size_t)t0 * tileElems * tb, slots, direct ? rq.arenaCapacity : slotBytes, 0, fl.fb, fl.batch, st);
-      }
-      if (!slotted && !direct)
-      {
-        ProfScope ps(ctx, "fast_tile_move");
-        launchFastTileCopy(dRes, dOff, slots, slotBytes, slotBytes, rq.dArena, (u32)n, end, rq.arenaCapacity, st);
-      }
-      if (hipGetLastError() != hipSuccess) { ctx.lastError = "lerc_amd: a streaming encode kernel could not be launched"; return kFailed; }
-      const size_t resBytes = (size_t)n * sizeof(FastEncodeResult) + 16, offBytes = ((size_t)n + 1) * 8;    // (+ the cursor)
-      u8* pin = (u8*)ctx.pinned(resBytes + offBytes);
-      if (!pin) return kFailed;
-      hipMemcpyAsync(pin, dRes, resBytes, hipMemcpyDeviceToHost, st);
-      if (!slotted) hipMemcpyAsync(pin + resBytes, dOff, offBytes, hipMemcpyDeviceToHost, st);
-      if (!ctx.sync()) return kFailed;
-      if (ctx.profOn()) ctx.profCollect();
-      const FastEncodeResult* res = reinterpret_cast<const FastEncodeResult*>(pin);
-      const u64* off = reinterpret_cast<const u64*>(pin + resBytes);
-      redoOut.clear();
-      bool anyStuck = false;
-      for (int i = 0; i < n; i++)
-      {
-        if (res[i].redo || res[i].stuck)
-        {
-          anyStuck = anyStuck || res[i].stuck != 0;
-          if (!slotted && (res[i].redoReason & 128u)) return kBufferTooSmall;    // the arena is full
-          redoOut.push_back(std::make_pair(t0 + i, res[i].stuck ? 0u : res[i].redoReason));    // (slotted: a tile that does not fit its slot says so when it is encoded by itself)
-          continue;
-        }
-        rq.hOffsets[t0 + i] = slotted ? (u64)(t0 + i) * slotBytes : off[i];
-        rq.hSizes[t0 + i] = res[i].blobSize;
-        ctx.pathCount[0]++; ctx.tileBatchCount[0]++;
-      }
-      if (anyStuck) ctx.wipePersistentState();
-      if (direct) { u64 claimed; memcpy(&claimed, pin + (size_t)n * sizeof(FastEncodeResult), 8); end += claimed; }    // (incl. the room of tiles that were handed back: holes)
-      else if (!slotted) end = off[n];
+      for (int t = 0; t < rq.nTiles; t++) { const u32 rc = encodeOne(t); if (rc != kOk) return rc; }
+      arenaUsed = slotted ? (u64)rq.nTiles * rq.slotBytes : end;
       return kOk;
-    };
-    // (a tile that compresses to more than half its raw size -- lossless noise, a small error bound -- does not fit the batch's
-    // slots.  A few such tiles are encoded one by one behind the batch; a batch full of them is encoded once more with slots
-    // that hold raw blocks, instead of tile after tile with a wait each)
-    const u64 slotBig = slotted ? slotBytes : ((tileElems * tb + tileElems / 64 + 4096) + 15) & ~15ull;
-    // (a tile is a blockIdx.y: at most 65535 of them per launch)
-    const int maxBatch = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)rq.nTiles, 65535), ((size_t)2 << 30) / slotBytes));
-    const int maxBig = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)rq.nTiles, 65535), ((size_t)2 << 30) / slotBig));
-    std::vector<std::pair<int, u32> > back;
+    }
+    // sub-batches: a tile is a blockIdx.y, at most 65535 of them per launch, and the slots stay below 2 GB; the three-launch form keeps its
+    // workspace bounded (block descriptors are 1/16 of the pixels)
+    const size_t nT = (size_t)rq.nTiles, perTile = FastEncodePlan::stagedBytes(rq.nRows, rq.nCols, 1) - 65536;
+    const int maxBatch = (int)std::max<size_t>(1, placed ? std::min<size_t>(nT, ((size_t)256 << 20) / perTile)
+                                                         : std::min<size_t>(std::min<size_t>(nT, 65535), ((size_t)2 << 30) / slotBytes));
+    const int maxBig = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(nT, 65535), ((size_t)2 << 30) / slotBig));
     for (int t0 = 0; t0 < rq.nTiles; t0 += maxBatch)
     {
       const int n = std::min(maxBatch, rq.nTiles - t0);
-      const u64 end0 = end;
-      const unsigned long long count0 = ctx.pathCount[0], batch0 = ctx.tileBatchCount[0];
-      u32 rc = runBatch(t0, n, slotBytes, back);
+      bool onceMore = false;
+      u32 rc = runBatch(t0, n, placed ? 0 : slotBytes, onceMore);
+      for (int s0 = t0; onceMore && s0 < t0 + n && rc == kOk; s0 += maxBig) { bool again = false; rc = runBatch(s0, std::min(maxBig, t0 + n - s0), slotBig, again); }
       if (rc != kOk) return rc;
-      size_t tooBig = 0;
-      for (const auto& r : back) if (r.second == 64u) tooBig++;    // (kRedoCapacity and nothing else)
-      if (!slotted && !direct && tooBig > (size_t)std::max(8, n / 32))
-      {
-        end = end0; ctx.pathCount[0] = count0; ctx.tileBatchCount[0] = batch0;
-        for (int s0 = t0; s0 < t0 + n; s0 += maxBig)
-        {
-          rc = runBatch(s0, std::min(maxBig, t0 + n - s0), slotBig, back);
-          if (rc != kOk) return rc;
-          for (const auto& r : back) { rc = encodeOne(r.first); if (rc != kOk) return rc; }
-        }
-        continue;
-      }
-      for (const auto& r : back) { rc = encodeOne(r.first); if (rc != kOk) return rc; }    // (reuses the workspace: the batch is done with it)
     }
-    arenaUsed = slotted ? (u64)rq.nTiles * slotBytes : end;
+    arenaUsed = slotted ? (u64)rq.nTiles * rq.slotBytes : end;
     return kOk;
   }
+};
 
-  // sub-batches keep the workspace bounded (block descriptors are 1/16 of the pixels)
-  const size_t perTile = fastEncodeWorkspace(rq.nRows, rq.nCols, 1) - 65536;
-  const int maxBatch = (int)std::max<size_t>(1, std::min<size_t>((size_t)rq.nTiles, ((size_t)256 << 20) / perTile));
-  for (int t0 = 0; t0 < rq.nTiles; t0 += maxBatch)
-  {
-    const int n = std::min(maxBatch, rq.nTiles - t0);
-    if (!ctx.reserve(fastEncodeWorkspace(rq.nRows, rq.nCols, (u32)n))) return kFailed;
-    FastEncodeLaunch fl;
-    if (!prepareFastEncode(ctx, rq.dt, rq.nRows, rq.nCols, rq.maxZErr, (u32)n, tileElems, true, fl)) return kFailed;
-    end = (end + 15) & ~15ull;
-    runFastEncode(ctx, fl, (const u8*)rq.dData + (size_t)t0 * tileElems * tb, rq.dArena, rq.arenaCapacity, end);
-    const size_t resBytes = (size_t)n * sizeof(FastEncodeResult), offBytes = ((size_t)n + 1) * 8;
-    u8* pin = (u8*)ctx.pinned(resBytes + offBytes);
-    if (!pin) return kFailed;
-    hipMemcpyAsync(pin, fl.fb.result, resBytes, hipMemcpyDeviceToHost, st);
-    hipMemcpyAsync(pin + resBytes, fl.fb.tileOffset, offBytes, hipMemcpyDeviceToHost, st);
-    if (!ctx.sync()) return kFailed;
-    if (ctx.profOn()) ctx.profCollect();
-    const FastEncodeResult* res = reinterpret_cast<const FastEncodeResult*>(pin);
-    const u64* off = reinterpret_cast<const u64*>(pin + resBytes);
-    redo.clear();
-    for (int i = 0; i < n; i++)
-    {
-      if (res[i].redo || res[i].stuck)
-      {
-        if (res[i].redoReason & 128u) return kBufferTooSmall;    // the arena is full
-        redo.push_back(t0 + i);
-        continue;
-      }
-      rq.hOffsets[t0 + i] = off[i];
-      rq.hSizes[t0 + i] = res[i].blobSize;
-      ctx.pathCount[0]++; ctx.tileBatchCount[0]++;
-    }
-    end = off[n];
-    for (int t : redo) { const u32 rc = encodeOne(t); if (rc != kOk) return rc; }    // (reuses the workspace: the batch is done with it)
-  }
-  arenaUsed = end;
-  return kOk;
+u32 encodeTilesDevice(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed)
+{
+  arenaUsed = 0;
+  if (!rq.dData || !rq.dArena || !rq.hOffsets || !rq.hSizes || rq.nTiles <= 0 || rq.nRows <= 0 || rq.nCols <= 0 || rq.dt < 0 || rq.dt > DT_Double
+    || rq.maxZErr < 0 || (rq.slotBytes & 15u) != 0)
+    return kWrongParam;
+  if (tilesBytesEncodeEligible(rq)) return encodeTilesBytes(ctx, rq, arenaUsed);    // (8-bit: the Huffman decision, a tile per workgroup)
+  TileBatchEncoder enc(ctx, rq);
+  return enc.run(streamingEligible(rq.dt, rq.nRows, rq.nCols, 1, false, true, rq.maxZErr, rq.dData, rq.dArena, enc.tileElems * enc.tb), arenaUsed);
 }
 
 }    // namespace lerc

@@ -12,7 +12,7 @@ static const int kFastBlocksPerWG = 64;    // one workgroup = 64 consecutive blo
 struct FastEncodeResult
 {
   u32 redo;            // != 0: an assumption of the fast path does not hold, the host must take the general path
-  u32 redoReason;      // diagnostic bit set (see tile_fast.hip)
+  u32 redoReason;      // diagnostic bit set (FastRedo)
   u32 blobSize;
   u32 nBytesTiling;
   double zMin, zMax;
@@ -22,6 +22,13 @@ struct FastEncodeResult
   u32 stuck;           // != 0: a workgroup gave up waiting for another one (never seen; the host then takes the general path)
   u32 streamSums;      // Fletcher terms of the block stream's bytes at their place in the band: sum of the 16-bit words mod 65535 |
                        // (sum of word index * word mod 65535) << 16 -- a masked band's host adds header and mask to them
+};
+// why a raster is handed back (FastEncodeResult::redoReason)
+enum FastRedo : u32
+{
+  kRedoNaN = 1, kRedoAllInt = 2, kRedoRaise = 4, kRedoConst = 8, kRedoMb16 = 16, kRedoOneSweep = 32, kRedoCapacity = 64,
+  kRedoArena = 128,    // (with kRedoCapacity: the ARENA of a batch is full, not a tile's own room)
+  kRedoNotLaunched = 0x80000000u    // the host's, pre-set in a result the kernels write straight into pinned memory: if a launch fails, nothing overwrites it
 };
 
 #ifdef LERC_SMALL_GROUPS                   // (emulator builds: small rasters then take the multi-group hand-offs too)

@@ -58,12 +58,6 @@ extern "C" __attribute__((visibility("default"))) void lerc_amd_probe_trace(unsi
 #endif
 #define ENC_EXIT(n) do { if (LERC_ENC_EXIT == (n)) return; } while (0)
 
-enum FastRedo : u32
-{
-  kRedoNaN = 1, kRedoAllInt = 2, kRedoRaise = 4, kRedoConst = 8, kRedoMb16 = 16, kRedoOneSweep = 32, kRedoCapacity = 64,
-  kRedoArena = 128    // (with kRedoCapacity: the ARENA of a batch is full, not a tile's own room)
-};
-
 template<class T> struct FastCfg
 {
   static constexpr int V = (sizeof(T) >= 4) ? 16 / (int)sizeof(T) : 8;    // pixels per lane: f32 4, f64 2, 16-bit 8
