@@ -1,6 +1,7 @@
 // capi.cpp -- extern "C" boundary of liblerc_amd.so (include/lerc_amd.h).
 // Argument validation and status codes follow the reference's Lerc_c_api_impl.cpp:33-304; host
 // buffers are staged through HBM, all codec work happens in codec_encode.cpp / codec_decode.cpp.
+// An entry point is: what it zeroes, one argument check of its family, one request builder, the driver's call.
 #include "../../include/lerc_amd.h"
 #include "../../include/lerc_amd_device.h"
 #include "codec.h"
@@ -89,16 +90,61 @@ lerc_amd_context* threadHandle()
   return (holder.h && holder.h->ctx.ok()) ? holder.h : nullptr;
 }
 
-bool masksArgOk(int nMasks, int nBands, const void* pValidBytes)
-{
-  return (nMasks == 0 || nMasks == 1 || nMasks == nBands) && !(nMasks > 0 && !pValidBytes);
-}
-
+// ---- argument checks: one per call family.  WrongParam is always decided before DimsTooLarge; `alsoOk` carries what only the one
+// entry point asks (a pointer its siblings leave to the driver, its slot rule, its mask rule) into the WrongParam half.
 bool dimsOk(int nDepth, int nCols, int nRows, size_t elemSize)    // Lerc.cpp:1622-1639
 {
   if (nDepth <= 0 || nCols <= 0 || nRows <= 0) return false;
   const u64 nPix = (u64)nRows * nCols, lim = INT_MAX, bpp = elemSize;
   return !(nPix > lim || bpp > lim || bpp * nDepth > lim || bpp * nDepth * nPix > lim);
+}
+
+// a single raster of the stock and the device calls: its data pointer, type and four counts; maxZErr where the call has one
+bool rasterArgsOk(const void* pData, unsigned dataType, int nDepth, int nCols, int nRows, int nBands, double maxZErr = 0)
+{
+  return !(!pData || dataType >= DT_Undefined || nDepth <= 0 || nCols <= 0 || nRows <= 0 || nBands <= 0 || maxZErr < 0);
+}
+
+// the stock rule for masks: none, one, or one per band -- and a pointer where there are any (a pointer without masks is ignored)
+bool masksArgOk(int nMasks, int nBands, const void* pValidBytes)
+{
+  return (nMasks == 0 || nMasks == 1 || nMasks == nBands) && !(nMasks > 0 && !pValidBytes);
+}
+
+// Band stacks are stricter: count and pointer must agree both ways, since a NULL pointer is how these calls say "every pixel valid".
+bool bandStackMasksOk(int nMasks, int nBands, const void* dValidBytes)
+{
+  return (nMasks == 0 || nMasks == 1 || nMasks == nBands) && (nMasks == 0) == (dValidBytes == nullptr);
+}
+
+bool slotBytesOk(u64 slotBytes, bool mayBeZero) { return (slotBytes & 15u) == 0 && (mayBeZero || slotBytes != 0); }
+
+// the device calls on one raster: the raster, the masks, then the size
+lerc_status deviceRasterArgs(const void* dData, unsigned dataType, int nDepth, int nCols, int nRows, int nBands, int nMasks,
+                             const void* dValidBytes, double maxZErr = 0)
+{
+  if (!rasterArgsOk(dData, dataType, nDepth, nCols, nRows, nBands, maxZErr)) return kWrongParam;
+  if (!masksArgOk(nMasks, nBands, dValidBytes)) return kWrongParam;
+  return dimsOk(nDepth, nCols, nRows, (size_t)dtSize((int)dataType)) ? kOk : kDimsTooLarge;
+}
+
+lerc_status tileBatchArgs(const lerc_amd_context* h, unsigned dataType, int nCols, int nRows, int nTiles, bool alsoOk)
+{
+  if (!h || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || nTiles <= 0 || !alsoOk) return kWrongParam;
+  return dimsOk(1, nCols, nRows, (size_t)dtSize((int)dataType)) ? kOk : kDimsTooLarge;
+}
+
+// ---- a pitched raster cut into a grid of tiles (codec_raster_tiles.cpp): pointers, pitches, masks and slots are the driver's to check
+bool rasterTileDimsOk(int nCols, int nRows, int tileCols, int tileRows, unsigned int dataType)
+{
+  return dimsOk(1, std::min(nCols, tileCols), std::min(nRows, tileRows), (size_t)dtSize((int)dataType));
+}
+
+lerc_status rasterTilesArgs(const lerc_amd_context* h, unsigned dataType, int nCols, int nRows, int tileCols, int tileRows, bool alsoOk = true)
+{
+  if (!h || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || tileCols <= 0 || tileRows <= 0) return kWrongParam;
+  if (!alsoOk) return kWrongParam;
+  return rasterTileDimsOk(nCols, nRows, tileCols, tileRows, dataType) ? kOk : kDimsTooLarge;
 }
 
 bool usesNoData(const unsigned char* pUsesNoData, int nBands)
@@ -108,33 +154,126 @@ bool usesNoData(const unsigned char* pUsesNoData, int nBands)
   return false;
 }
 
-// shared by lerc_encode / lerc_computeCompressedSize: host pointers in, blob (optionally) out
-lerc_status encodeHost(const void* pData, unsigned dataType, int nDepth, int nCols, int nRows, int nBands, int nMasks,
-                       const unsigned char* pValidBytes, double maxZErr, unsigned char* pOut, unsigned outSize,
-                       unsigned* result, bool sizeOnly, const unsigned char* pUsesNoData = nullptr, const double* noDataValues = nullptr,
-                       int version = kCodecVersion)
+// ---- request builders: the C arguments in, a filled request out; each request type is filled here and nowhere else
+EncodeRequest encodeRequest(const void* data, unsigned dataType, int nDepth, int nCols, int nRows, int nBands, int nMasks,
+                            const unsigned char* validBytes, double maxZErr, unsigned char* out, unsigned outCapacity)
+{
+  EncodeRequest rq;
+  rq.dData = data; rq.dValidBytes = validBytes; rq.dt = (int)dataType; rq.nDepth = nDepth; rq.nCols = nCols; rq.nRows = nRows;
+  rq.nBands = nBands; rq.nMasks = nMasks; rq.maxZErr = maxZErr; rq.dOut = out; rq.outCapacity = outCapacity;
+  return rq;
+}
+
+// (one of hBlob / dBlob)
+DecodeRequest decodeRequest(const unsigned char* hBlob, const unsigned char* dBlob, unsigned blobSize, int nMasks, unsigned char* validBytes,
+                            int nDepth, int nCols, int nRows, int nBands, unsigned dataType, void* out)
+{
+  DecodeRequest rq;
+  rq.hBlob = hBlob; rq.dBlob = dBlob; rq.blobSize = blobSize; rq.dt = (int)dataType; rq.nDepth = nDepth; rq.nCols = nCols; rq.nRows = nRows;
+  rq.nBands = nBands; rq.nMasks = nMasks; rq.dOut = out; rq.dValidBytes = validBytes;
+  return rq;
+}
+
+TilesEncodeRequest tilesEncodeRequest(const void* dTiles, unsigned dataType, int nCols, int nRows, int nTiles, double maxZErr, unsigned char* dArena,
+                                      u64 arenaCapacity, u64* offsets, unsigned* sizes, u64 slotBytes = 0, const unsigned char* dValidBytes = nullptr,
+                                      int nBands = 1, int nMasks = -1)
+{
+  TilesEncodeRequest rq;
+  rq.dData = dTiles; rq.dt = (int)dataType; rq.nCols = nCols; rq.nRows = nRows; rq.nTiles = nTiles; rq.maxZErr = maxZErr;
+  rq.dArena = dArena; rq.arenaCapacity = arenaCapacity; rq.hOffsets = offsets; rq.hSizes = sizes; rq.slotBytes = slotBytes;
+  rq.dValidBytes = dValidBytes; rq.nBands = nBands; rq.nMasks = nMasks;
+  return rq;
+}
+
+TilesDecodeRequest tilesDecodeRequest(const unsigned char* dArena, const u64* offsets, const unsigned* sizes, int nTiles, int nCols, int nRows,
+                                      unsigned dataType, void* dTiles, unsigned char* dValidBytes = nullptr, int nBands = 1, int nMasks = -1)
+{
+  TilesDecodeRequest rq;
+  rq.dArena = dArena; rq.hOffsets = offsets; rq.hSizes = sizes; rq.dt = (int)dataType; rq.nCols = nCols; rq.nRows = nRows; rq.nTiles = nTiles;
+  rq.dOut = dTiles; rq.dValidBytes = dValidBytes; rq.nBands = nBands; rq.nMasks = nMasks;
+  return rq;
+}
+
+// how a raster (or a window's buffer) lies in memory, in elements; `any`: the description may be line- or pixel-interleaved
+struct RasterLayout
+{
+  u64 pixelPitch, rowPitch, bandPitch, maskRowPitch;
+  bool any;
+};
+RasterLayout planes(u64 rowPitch, u64 bandPitch, u64 maskRowPitch) { return { 1, rowPitch, bandPitch, maskRowPitch, false }; }
+RasterLayout strided(u64 pixelPitch, u64 rowPitch, u64 bandPitch, u64 maskRowPitch) { return { pixelPitch, rowPitch, bandPitch, maskRowPitch, true }; }
+
+// (an encode only reads raster and mask, a decode only reads arena and tables: the request has one set of pointers for both)
+RasterTilesRequest rasterTilesRequest(const void* dRaster, unsigned dataType, int nCols, int nRows, int nBands, const RasterLayout& lay, int tileCols,
+                                      int tileRows, int nMasks, const unsigned char* dValidBytes, const unsigned char* dArena, const u64* offsets,
+                                      const unsigned* sizes, double maxZErr = 0, u64 arenaCapacity = 0, u64 slotBytes = 0)
+{
+  RasterTilesRequest rq;
+  rq.dRaster = const_cast<void*>(dRaster); rq.dValidBytes = const_cast<unsigned char*>(dValidBytes); rq.dt = (int)dataType;
+  rq.nCols = nCols; rq.nRows = nRows; rq.nBands = nBands; rq.nMasks = nMasks; rq.tileCols = tileCols; rq.tileRows = tileRows;
+  rq.pixelPitch = lay.pixelPitch; rq.anyLayout = lay.any; rq.rowPitch = lay.rowPitch; rq.bandPitch = lay.bandPitch; rq.maskRowPitch = lay.maskRowPitch;
+  rq.dArena = const_cast<unsigned char*>(dArena); rq.hOffsets = const_cast<u64*>(offsets); rq.hSizes = const_cast<unsigned*>(sizes);
+  rq.maxZErr = maxZErr; rq.arenaCapacity = arenaCapacity; rq.slotBytes = slotBytes;
+  return rq;
+}
+
+// ---- what the entry points share behind their drivers' calls
+// the tail of a tile encode: slotted tiles lie at t * slotBytes (slotBytes 0: the driver's offsets stand), the arena's use is reported
+lerc_status finishTilesEncode(u32 rc, u64 used, u64 slotBytes, int nTiles, u64* offsets, u64* arenaUsed)
+{
+  if (rc == kOk && slotBytes) for (int t = 0; t < nTiles; t++) offsets[t] = (u64)t * slotBytes;
+  if (arenaUsed) *arenaUsed = used;
+  return rc;
+}
+
+lerc_status encodeRasterTiles(lerc_amd_context* h, const RasterTilesRequest& rq, u64* arenaUsed)
+{
+  u64 used = 0;
+  const u32 rc = encodeRasterTilesDevice(h->ctx, rq, used);
+  return finishTilesEncode(rc, used, 0, 0, nullptr, arenaUsed);    // (rooms are handed out per shape class: the driver's offsets stand)
+}
+
+// header facts of a blob of any version; legacy Lerc1: the bands have to be decoded to know their ranges (Lerc.cpp:184-266)
+u32 blobInfoAnyVersion(const u8* blob, u32 size, BlobInfo& li, double* mins, double* maxs, size_t nElem)
+{
+  const u32 e = getBlobInfo(blob, size, li, mins, maxs, nElem);
+  if (e == kOk || !isLerc1(blob, size)) return e;
+  lerc_amd_context* h = threadHandle();
+  if (!h) return kFailed;
+  return lerc1BlobInfo(h->ctx, blob, size, li, mins, maxs, nElem);
+}
+
+// a four-slot diagnostic read-out; no context: zeros.  (Who falls back to the calling thread's context says so at the call.)
+using Counters = const unsigned long long (&)[4];
+void readCounters(lerc_amd_context* h, Counters (*of)(Context&), unsigned long long out[4])
+{
+  for (int i = 0; i < 4; i++) out[i] = h ? of(h->ctx)[i] : 0;
+}
+lerc_amd_context* orThisThreads(lerc_amd_context* h) { return h ? h : threadHandle(); }    // the context behind the stock entry points
+
+// shared by lerc_encode / lerc_computeCompressedSize and their kin: `host` holds the caller's HOST pointers in dData / dValidBytes
+// until they are staged; pOut == nullptr: the size only
+lerc_status encodeHost(const EncodeRequest& host, unsigned char* pOut, unsigned outSize, unsigned* result)
 {
   lerc_amd_context* h = threadHandle();
   if (!h) return kFailed;
   Context& ctx = h->ctx;
   hipStream_t st = ctx.activeStream();
-  const size_t tb = (size_t)dtSize((int)dataType);
-  if (!dimsOk(nDepth, nCols, nRows, tb)) return kDimsTooLarge;
-  const size_t nPix = (size_t)nRows * nCols;
+  const int nDepth = host.nDepth, nBands = host.nBands, nMasks = host.nMasks;
+  const size_t tb = (size_t)dtSize(host.dt);
+  if (!dimsOk(nDepth, host.nCols, host.nRows, tb)) return kDimsTooLarge;
+  const size_t nPix = (size_t)host.nRows * host.nCols;
   const size_t dataBytes = nPix * nDepth * tb * nBands, maskBytes = (size_t)nMasks * nPix;
   u8* dData = (u8*)h->stage(0, dataBytes);
   u8* dMask = nMasks ? (u8*)h->stage(1, maskBytes) : nullptr;
   if (!dData || (nMasks && !dMask)) return kFailed;
-  hipMemcpyAsync(dData, pData, dataBytes, hipMemcpyHostToDevice, st);
-  if (nMasks) hipMemcpyAsync(dMask, pValidBytes, maskBytes, hipMemcpyHostToDevice, st);
+  hipMemcpyAsync(dData, host.dData, dataBytes, hipMemcpyHostToDevice, st);
+  if (nMasks) hipMemcpyAsync(dMask, host.dValidBytes, maskBytes, hipMemcpyHostToDevice, st);
 
-  EncodeRequest rq;
-  rq.dData = dData; rq.dValidBytes = dMask; rq.dt = (int)dataType; rq.nDepth = nDepth; rq.nCols = nCols; rq.nRows = nRows;
-  rq.nBands = nBands; rq.nMasks = nMasks; rq.maxZErr = maxZErr;
-  rq.hUsesNoData = pUsesNoData; rq.hNoDataValues = noDataValues;
-  rq.version = version;
+  EncodeRequest rq = host;
+  rq.dData = dData; rq.dValidBytes = dMask;
   u32 needed = 0, written = 0;
-  if (sizeOnly)
+  if (!pOut)
   {
     const u32 rc = encodeDevice(ctx, rq, needed, written);
     if (rc == kOk) *result = needed;
@@ -179,56 +318,71 @@ lerc_status encodeHost(const void* pData, unsigned dataType, int nDepth, int nCo
   return kOk;
 }
 
-lerc_status decodeHost(const unsigned char* blob, unsigned blobSize, int nMasks, unsigned char* pValidBytes, int nDepth,
-                       int nCols, int nRows, int nBands, unsigned dataType, void* pData, bool toDouble,
-                       unsigned char* pUsesNoData = nullptr, double* noDataValues = nullptr)
+// The stock encodes and size queries, all eight: *result is zeroed, then the checks of Lerc_c_api_impl.cpp / Lerc.cpp:339-386.
+// codecVersion < 0 or the current one: the _4D call, noData arrays and all; an older one: EncodeInternal_v5, which has none.
+lerc_status encodeStock(const void* pData, int codecVersion, unsigned dataType, int nDepth, int nCols, int nRows, int nBands, int nMasks,
+                        const unsigned char* pValidBytes, double maxZErr, bool wantBlob, unsigned char* pOut, unsigned outSize, unsigned* result,
+                        const unsigned char* pUsesNoData, const double* noDataValues)
+{
+  if (!result) return kWrongParam;
+  *result = 0;
+  if (codecVersion > kCodecVersion) return kWrongParam;
+  if (!rasterArgsOk(pData, dataType, nDepth, nCols, nRows, nBands, maxZErr) || (wantBlob && (!pOut || !outSize))) return kWrongParam;
+  if (!masksArgOk(nMasks, nBands, pValidBytes)) return kWrongParam;
+  const bool older = codecVersion >= 0 && codecVersion < kCodecVersion;
+  if (older && codecVersion < 2) return kWrongParam;    // Lerc2::SetEncoderToOldVersion (Lerc2.cpp:52-62)
+  if (!older && usesNoData(pUsesNoData, nBands) && !noDataValues) return kWrongParam;
+  EncodeRequest host = encodeRequest(pData, dataType, nDepth, nCols, nRows, nBands, nMasks, pValidBytes, maxZErr, nullptr, 0);
+  if (older) host.version = codecVersion;
+  else { host.hUsesNoData = pUsesNoData; host.hNoDataValues = noDataValues; }
+  return encodeHost(host, wantBlob ? pOut : nullptr, outSize, result);
+}
+
+// `host` holds the caller's HOST pointers: the blob in hBlob, where pixels and valid bytes go in dOut / dValidBytes
+lerc_status decodeHost(const DecodeRequest& host, bool toDouble)
 {
   lerc_amd_context* h = threadHandle();
   if (!h) return kFailed;
   Context& ctx = h->ctx;
   hipStream_t st = ctx.activeStream();
-  const size_t tb = (size_t)dtSize((int)dataType);
-  if (!dimsOk(nDepth, nCols, nRows, tb)) return kDimsTooLarge;
-  const size_t nPix = (size_t)nRows * nCols, nVals = nPix * nDepth * nBands;
+  void* pData = host.dOut;
+  unsigned char* pValidBytes = host.dValidBytes;
+  const int nMasks = host.nMasks;
+  const size_t tb = (size_t)dtSize(host.dt);
+  if (!dimsOk(host.nDepth, host.nCols, host.nRows, tb)) return kDimsTooLarge;
+  const size_t nPix = (size_t)host.nRows * host.nCols, nVals = nPix * host.nDepth * host.nBands;
   const size_t outBytes = nVals * tb, maskBytes = (size_t)nMasks * nPix;
-  const bool widen = toDouble && dataType != DT_Double;
+  const bool widen = toDouble && host.dt != DT_Double;
   u8* dOut = (u8*)h->stage(0, outBytes + (widen ? nVals * 8 + 256 : 0));
   u8* dMask = nMasks ? (u8*)h->stage(1, maskBytes) : nullptr;
   if (!dOut || (nMasks && !dMask)) return kFailed;
 
-  if (isLerc1(blob, blobSize))
+  if (isLerc1(host.hBlob, host.blobSize))
   {
     // Lerc1 leaves pixels that are not valid as the caller's buffer had them (Lerc::Convert, Lerc.cpp:795-845): the staging
     // buffer starts out as a copy of it (lerc_decodeToDouble decodes into the tail of the double buffer, Lerc_c_api_impl.cpp:288-300)
     const u8* src = (const u8*)pData + (widen ? nVals * (8 - tb) : 0);
     hipMemcpyAsync(dOut, src, outBytes, hipMemcpyHostToDevice, st);
   }
-  DecodeRequest rq;
-  rq.hBlob = blob; rq.blobSize = blobSize; rq.dt = (int)dataType; rq.nDepth = nDepth; rq.nCols = nCols; rq.nRows = nRows;
-  rq.nBands = nBands; rq.nMasks = nMasks; rq.dOut = dOut; rq.dValidBytes = dMask;
-  rq.hUsesNoData = pUsesNoData; rq.hNoDataValues = noDataValues;
+  DecodeRequest rq = host;
+  rq.dOut = dOut; rq.dValidBytes = dMask;
   StreamTicket tried;    // (form kFormGeneral: nothing enqueued -- no form has refused the blob, nothing was written)
-  // What the streaming kernels can take -- the header says so: one band, every pixel valid, 8 x 8 blocks, nDepth 1 -- goes
-  // up, through the kernels and back in one go: upload, kernels, verdict and the pixels' way back are enqueued together
-  // and this thread waits once (two waits and the gap between them are a quarter of a small raster's call).
+  // What the streaming kernels can take (speculativeDecodeEligible: the header says so) goes up, through the kernels and back in
+  // one go: upload, kernels, verdict and the pixels' way back are enqueued together and this thread waits once (two waits and the
+  // gap between them are a quarter of a small raster's call).
+  Header hd;
+  size_t used = 0;
+  if (!widen && readHeader(host.hBlob, host.blobSize, hd, used) && speculativeDecodeEligible(hd, rq))
   {
-    Header hd;
-    size_t used = 0;
-    const size_t nPixHd = (size_t)nRows * nCols;
-    if (!widen && nBands == 1 && nDepth == 1 && !pUsesNoData && readHeader(blob, blobSize, hd, used) && hd.version >= 3 && hd.nRows == nRows
-      && hd.nCols == nCols && hd.nDepth == 1 && hd.dt == (int)dataType && hd.mbSize == 8 && hd.nBlobsMore == 0
-      && (size_t)hd.numValid == nPixHd && (unsigned)hd.blobSize <= blobSize && hd.maxZErr > 0 && hd.zMin != hd.zMax)
+    u8* dBlob = (u8*)h->stage(2, (size_t)host.blobSize + 256);
+    if (dBlob && hipMemcpyAsync(dBlob, host.hBlob, host.blobSize, hipMemcpyHostToDevice, st) == hipSuccess)
     {
-      u8* dBlob = (u8*)h->stage(2, (size_t)blobSize + 256);
-      if (dBlob && hipMemcpyAsync(dBlob, blob, blobSize, hipMemcpyHostToDevice, st) == hipSuccess)
-      {
-        DecodeRequest rs = rq;
-        rs.hBlob = nullptr; rs.dBlob = dBlob;
-        bool handled = false;
-        const u32 src = decodeSpeculativeToHost(ctx, rs, pData, outBytes, nMasks ? pValidBytes : nullptr, maskBytes, handled, tried);
-        if (src != kOk) return src;
-        if (handled) return kOk;
-      }
+      DecodeRequest rs = rq;
+      rs.hBlob = nullptr; rs.dBlob = dBlob;
+      bool handled = false;
+      const u32 src = decodeSpeculativeToHost(ctx, rs, pData, outBytes, nMasks ? pValidBytes : nullptr, maskBytes, handled, tried);
+      if (src != kOk) return src;
+      if (handled) return kOk;
     }
   }
   const bool triedOne = tried.form > kFormGeneral;
@@ -249,7 +403,7 @@ lerc_status decodeHost(const unsigned char* blob, unsigned blobSize, int nMasks,
   if (widen)
   {
     double* dWide = (double*)(dOut + ((outBytes + 255) / 256) * 256);
-    launchWidenToDouble((int)dataType, dOut, dWide, (i64)nVals, st);
+    launchWidenToDouble(host.dt, dOut, dWide, (i64)nVals, st);
     hipMemcpyAsync(pData, dWide, nVals * 8, hipMemcpyDeviceToHost, st);
   }
   else hipMemcpyAsync(pData, dOut, outBytes, hipMemcpyDeviceToHost, st);
@@ -265,67 +419,31 @@ lerc_status lerc_computeCompressedSize_4D(const void* pData, unsigned int dataTy
   int nBands, int nMasks, const unsigned char* pValidBytes, double maxZErr, unsigned int* numBytes,
   const unsigned char* pUsesNoData, const double* noDataValues)
 {
-  if (!numBytes) return kWrongParam;
-  *numBytes = 0;
-  if (!pData || dataType >= DT_Undefined || nDepth <= 0 || nCols <= 0 || nRows <= 0 || nBands <= 0 || maxZErr < 0) return kWrongParam;
-  if (!masksArgOk(nMasks, nBands, pValidBytes)) return kWrongParam;
-  if (usesNoData(pUsesNoData, nBands) && !noDataValues) return kWrongParam;
-  return encodeHost(pData, dataType, nDepth, nCols, nRows, nBands, nMasks, pValidBytes, maxZErr, nullptr, 0, numBytes, true, pUsesNoData,
-                    noDataValues);
+  return encodeStock(pData, -1, dataType, nDepth, nCols, nRows, nBands, nMasks, pValidBytes, maxZErr, false, nullptr, 0, numBytes, pUsesNoData,
+                     noDataValues);
 }
 
 lerc_status lerc_encode_4D(const void* pData, unsigned int dataType, int nDepth, int nCols, int nRows, int nBands,
   int nMasks, const unsigned char* pValidBytes, double maxZErr, unsigned char* pOutBuffer, unsigned int outBufferSize,
   unsigned int* nBytesWritten, const unsigned char* pUsesNoData, const double* noDataValues)
 {
-  if (!nBytesWritten) return kWrongParam;
-  *nBytesWritten = 0;
-  if (!pData || dataType >= DT_Undefined || nDepth <= 0 || nCols <= 0 || nRows <= 0 || nBands <= 0 || maxZErr < 0
-    || !pOutBuffer || !outBufferSize)
-    return kWrongParam;
-  if (!masksArgOk(nMasks, nBands, pValidBytes)) return kWrongParam;
-  if (usesNoData(pUsesNoData, nBands) && !noDataValues) return kWrongParam;
-  return encodeHost(pData, dataType, nDepth, nCols, nRows, nBands, nMasks, pValidBytes, maxZErr, pOutBuffer, outBufferSize,
-                    nBytesWritten, false, pUsesNoData, noDataValues);
+  return encodeStock(pData, -1, dataType, nDepth, nCols, nRows, nBands, nMasks, pValidBytes, maxZErr, true, pOutBuffer, outBufferSize, nBytesWritten,
+                     pUsesNoData, noDataValues);
 }
 
 lerc_status lerc_computeCompressedSizeForVersion(const void* pData, int codecVersion, unsigned int dataType, int nDepth,
   int nCols, int nRows, int nBands, int nMasks, const unsigned char* pValidBytes, double maxZErr, unsigned int* numBytes)
 {
-  if (!numBytes) return kWrongParam;
-  *numBytes = 0;
-  if (codecVersion > kCodecVersion) return kWrongParam;
-  if (codecVersion >= 0 && codecVersion < kCodecVersion)    // Lerc.cpp:339-347 -> EncodeInternal_v5
-  {
-    if (!pData || dataType >= DT_Undefined || nDepth <= 0 || nCols <= 0 || nRows <= 0 || nBands <= 0 || maxZErr < 0) return kWrongParam;
-    if (!masksArgOk(nMasks, nBands, pValidBytes)) return kWrongParam;
-    if (codecVersion < 2) return kWrongParam;    // Lerc2::SetEncoderToOldVersion (Lerc2.cpp:52-62)
-    return encodeHost(pData, dataType, nDepth, nCols, nRows, nBands, nMasks, pValidBytes, maxZErr, nullptr, 0, numBytes, true, nullptr,
-                      nullptr, codecVersion);
-  }
-  return lerc_computeCompressedSize_4D(pData, dataType, nDepth, nCols, nRows, nBands, nMasks, pValidBytes, maxZErr, numBytes,
-                                       nullptr, nullptr);
+  return encodeStock(pData, codecVersion, dataType, nDepth, nCols, nRows, nBands, nMasks, pValidBytes, maxZErr, false, nullptr, 0, numBytes, nullptr,
+                     nullptr);
 }
 
 lerc_status lerc_encodeForVersion(const void* pData, int codecVersion, unsigned int dataType, int nDepth, int nCols,
   int nRows, int nBands, int nMasks, const unsigned char* pValidBytes, double maxZErr, unsigned char* pOutBuffer,
   unsigned int outBufferSize, unsigned int* nBytesWritten)
 {
-  if (!nBytesWritten) return kWrongParam;
-  *nBytesWritten = 0;
-  if (codecVersion > kCodecVersion) return kWrongParam;
-  if (codecVersion >= 0 && codecVersion < kCodecVersion)    // Lerc.cpp:378-386
-  {
-    if (!pData || dataType >= DT_Undefined || nDepth <= 0 || nCols <= 0 || nRows <= 0 || nBands <= 0 || maxZErr < 0
-      || !pOutBuffer || !outBufferSize)
-      return kWrongParam;
-    if (!masksArgOk(nMasks, nBands, pValidBytes)) return kWrongParam;
-    if (codecVersion < 2) return kWrongParam;    // Lerc2::SetEncoderToOldVersion (Lerc2.cpp:52-62)
-    return encodeHost(pData, dataType, nDepth, nCols, nRows, nBands, nMasks, pValidBytes, maxZErr, pOutBuffer, outBufferSize,
-                      nBytesWritten, false, nullptr, nullptr, codecVersion);
-  }
-  return lerc_encode_4D(pData, dataType, nDepth, nCols, nRows, nBands, nMasks, pValidBytes, maxZErr, pOutBuffer,
-                        outBufferSize, nBytesWritten, nullptr, nullptr);
+  return encodeStock(pData, codecVersion, dataType, nDepth, nCols, nRows, nBands, nMasks, pValidBytes, maxZErr, true, pOutBuffer, outBufferSize,
+                     nBytesWritten, nullptr, nullptr);
 }
 
 lerc_status lerc_computeCompressedSize(const void* pData, unsigned int dataType, int nDepth, int nCols, int nRows,
@@ -349,13 +467,7 @@ lerc_status lerc_getBlobInfo(const unsigned char* pLercBlob, unsigned int blobSi
   if (!pLercBlob || !blobSize || (!infoArray && !dataRangeArray) || ((infoArraySize <= 0) && (dataRangeArraySize <= 0)))
     return kWrongParam;
   BlobInfo li;
-  u32 e = getBlobInfo(pLercBlob, blobSize, li);
-  if (e != kOk && isLerc1(pLercBlob, blobSize))    // legacy Lerc1: the bands have to be decoded to know their ranges (Lerc.cpp:184-266)
-  {
-    lerc_amd_context* h = threadHandle();
-    if (!h) return kFailed;
-    e = lerc1BlobInfo(h->ctx, pLercBlob, blobSize, li, nullptr, nullptr, 0);
-  }
+  const u32 e = blobInfoAnyVersion(pLercBlob, blobSize, li, nullptr, nullptr, 0);
   if (e != kOk) return e;
   if (infoArray)
   {
@@ -379,24 +491,18 @@ lerc_status lerc_getDataRanges(const unsigned char* pLercBlob, unsigned int blob
 {
   if (!pLercBlob || !blobSize || !pMins || !pMaxs || nDepth <= 0 || nBands <= 0) return kWrongParam;
   BlobInfo li;
-  const u32 e = getBlobInfo(pLercBlob, blobSize, li, pMins, pMaxs, (size_t)nDepth * (size_t)nBands);
-  if (e != kOk && isLerc1(pLercBlob, blobSize))
-  {
-    lerc_amd_context* h = threadHandle();
-    if (!h) return kFailed;
-    return lerc1BlobInfo(h->ctx, pLercBlob, blobSize, li, pMins, pMaxs, (size_t)nDepth * (size_t)nBands);
-  }
-  return e;
+  return blobInfoAnyVersion(pLercBlob, blobSize, li, pMins, pMaxs, (size_t)nDepth * (size_t)nBands);
 }
 
 lerc_status lerc_decode_4D(const unsigned char* pLercBlob, unsigned int blobSize, int nMasks, unsigned char* pValidBytes,
   int nDepth, int nCols, int nRows, int nBands, unsigned int dataType, void* pData, unsigned char* pUsesNoData,
   double* noDataValues)
 {
-  if (!pLercBlob || !blobSize || !pData || dataType >= DT_Undefined || nDepth <= 0 || nCols <= 0 || nRows <= 0 || nBands <= 0)
-    return kWrongParam;
+  if (!pLercBlob || !blobSize || !rasterArgsOk(pData, dataType, nDepth, nCols, nRows, nBands)) return kWrongParam;
   if (!masksArgOk(nMasks, nBands, pValidBytes)) return kWrongParam;
-  return decodeHost(pLercBlob, blobSize, nMasks, pValidBytes, nDepth, nCols, nRows, nBands, dataType, pData, false, pUsesNoData, noDataValues);
+  DecodeRequest host = decodeRequest(pLercBlob, nullptr, blobSize, nMasks, pValidBytes, nDepth, nCols, nRows, nBands, dataType, pData);
+  host.hUsesNoData = pUsesNoData; host.hNoDataValues = noDataValues;
+  return decodeHost(host, false);
 }
 
 lerc_status lerc_decode(const unsigned char* pLercBlob, unsigned int blobSize, int nMasks, unsigned char* pValidBytes,
@@ -409,20 +515,15 @@ lerc_status lerc_decodeToDouble_4D(const unsigned char* pLercBlob, unsigned int 
   unsigned char* pValidBytes, int nDepth, int nCols, int nRows, int nBands, double* pData, unsigned char* pUsesNoData,
   double* noDataValues)
 {
-  if (!pLercBlob || !blobSize || !pData || nDepth <= 0 || nCols <= 0 || nRows <= 0 || nBands <= 0) return kWrongParam;
+  if (!pLercBlob || !blobSize || !rasterArgsOk(pData, DT_Double, nDepth, nCols, nRows, nBands)) return kWrongParam;    // (the type is the blob's)
   if (!masksArgOk(nMasks, nBands, pValidBytes)) return kWrongParam;
   BlobInfo li;
-  u32 e = getBlobInfo(pLercBlob, blobSize, li);
-  if (e != kOk && isLerc1(pLercBlob, blobSize))
-  {
-    lerc_amd_context* h = threadHandle();
-    if (!h) return kFailed;
-    e = lerc1BlobInfo(h->ctx, pLercBlob, blobSize, li, nullptr, nullptr, 0);
-  }
+  const u32 e = blobInfoAnyVersion(pLercBlob, blobSize, li, nullptr, nullptr, 0);
   if (e != kOk) return e;
   if (li.nDepth != nDepth || li.nCols != nCols || li.nRows != nRows || li.nBands != nBands) return kFailed;
-  return decodeHost(pLercBlob, blobSize, nMasks, pValidBytes, nDepth, nCols, nRows, nBands, (unsigned)li.dt, pData, true, pUsesNoData,
-                    noDataValues);
+  DecodeRequest host = decodeRequest(pLercBlob, nullptr, blobSize, nMasks, pValidBytes, nDepth, nCols, nRows, nBands, (unsigned)li.dt, pData);
+  host.hUsesNoData = pUsesNoData; host.hNoDataValues = noDataValues;
+  return decodeHost(host, true);
 }
 
 lerc_status lerc_decodeToDouble(const unsigned char* pLercBlob, unsigned int blobSize, int nMasks,
@@ -447,7 +548,7 @@ void lerc_amd_set_stream(lerc_amd_context* h, void* hipStream) { if (h) h->ctx.s
 
 const char* lerc_amd_last_error(lerc_amd_context* h)
 {
-  if (!h) h = threadHandle();    // nullptr: the calling thread's context behind the stock entry points
+  h = orThisThreads(h);
   return h ? h->ctx.lastError.c_str() : "no context";
 }
 
@@ -457,12 +558,8 @@ lerc_status lerc_amd_encode_device(lerc_amd_context* h, const void* dData, unsig
 {
   if (!h || !nBytesWritten) return kWrongParam;
   *nBytesWritten = 0;
-  if (!dData || dataType >= DT_Undefined || nDepth <= 0 || nCols <= 0 || nRows <= 0 || nBands <= 0 || maxZErr < 0) return kWrongParam;
-  if (!masksArgOk(nMasks, nBands, dValidBytes)) return kWrongParam;
-  if (!dimsOk(nDepth, nCols, nRows, (size_t)dtSize((int)dataType))) return kDimsTooLarge;
-  EncodeRequest rq;
-  rq.dData = dData; rq.dValidBytes = dValidBytes; rq.dt = (int)dataType; rq.nDepth = nDepth; rq.nCols = nCols; rq.nRows = nRows;
-  rq.nBands = nBands; rq.nMasks = nMasks; rq.maxZErr = maxZErr; rq.dOut = dOutBuffer; rq.outCapacity = outBufferSize;
+  if (const lerc_status bad = deviceRasterArgs(dData, dataType, nDepth, nCols, nRows, nBands, nMasks, dValidBytes, maxZErr)) return bad;
+  const EncodeRequest rq = encodeRequest(dData, dataType, nDepth, nCols, nRows, nBands, nMasks, dValidBytes, maxZErr, dOutBuffer, outBufferSize);
   u32 needed = 0, written = 0;
   const u32 rc = encodeDevice(h->ctx, rq, needed, written);
   if (rc == kOk) *nBytesWritten = dOutBuffer ? written : needed;
@@ -472,13 +569,9 @@ lerc_status lerc_amd_encode_device(lerc_amd_context* h, const void* dData, unsig
 lerc_status lerc_amd_decode_device(lerc_amd_context* h, const unsigned char* dLercBlob, unsigned int blobSize, int nMasks,
   unsigned char* dValidBytes, int nDepth, int nCols, int nRows, int nBands, unsigned int dataType, void* dData)
 {
-  if (!h || !dLercBlob || !blobSize || !dData || dataType >= DT_Undefined || nDepth <= 0 || nCols <= 0 || nRows <= 0 || nBands <= 0)
-    return kWrongParam;
-  if (!masksArgOk(nMasks, nBands, dValidBytes)) return kWrongParam;
-  if (!dimsOk(nDepth, nCols, nRows, (size_t)dtSize((int)dataType))) return kDimsTooLarge;
-  DecodeRequest rq;
-  rq.dBlob = dLercBlob; rq.blobSize = blobSize; rq.dt = (int)dataType; rq.nDepth = nDepth; rq.nCols = nCols; rq.nRows = nRows;
-  rq.nBands = nBands; rq.nMasks = nMasks; rq.dOut = dData; rq.dValidBytes = dValidBytes;
+  if (!h || !dLercBlob || !blobSize) return kWrongParam;
+  if (const lerc_status bad = deviceRasterArgs(dData, dataType, nDepth, nCols, nRows, nBands, nMasks, dValidBytes)) return bad;
+  const DecodeRequest rq = decodeRequest(nullptr, dLercBlob, blobSize, nMasks, dValidBytes, nDepth, nCols, nRows, nBands, dataType, dData);
   const u32 rc = decodeDevice(h->ctx, rq);
   if (rc == kFailed) wipeDecodeOutputs(h->ctx, rq);
   return rc;
@@ -487,70 +580,79 @@ lerc_status lerc_amd_decode_device(lerc_amd_context* h, const unsigned char* dLe
 // ---- asynchronous device API: operations queue up on the context's stream, the host runs ahead -------------------------
 namespace {
 
+// A streamed operation's verdict, read once the stream has passed it.  false: the streaming kernels handed it back.
+bool encodeVerdict(Context& ctx, AsyncOp& op)
+{
+  bool redo = false;
+  u32 needed = 0, written = 0;
+  encodeStreamingVerdict(ctx, op.er, ctx.asyncSlot(op.ticket), redo, op.status, needed, written);
+  op.bytes = op.er.dOut ? written : needed;
+  return !redo;
+}
+
+bool decodeVerdict(Context& ctx, AsyncOp& op)
+{
+  if (!decodeStreamingVerdict(ctx, ctx.asyncSlot(op.ticket), op.launch)) return false;
+  ctx.pathCount[2]++;
+  return true;
+}
+
+// The blob's true length: an asynchronous decode may have been given the capacity of the buffer an encode still in flight was
+// writing to; the synchronous path wants the blob's own size, which its header on the device holds.
+void trimToBlobSize(DecodeRequest& dr)
+{
+  if (!dr.dBlob || dr.hBlob || dr.blobSize < 70) return;
+  u8 head[64];
+  if (hipMemcpy(head, dr.dBlob, sizeof(head), hipMemcpyDeviceToHost) != hipSuccess) return;
+  BlobInfo info;
+  if (getBlobInfo(head, sizeof(head), info) == kOk && info.blobSize >= 70 && info.blobSize <= dr.blobSize) dr.blobSize = info.blobSize;
+}
+
+// The operation once more, through the synchronous path.
+void encodeAgain(Context& ctx, AsyncOp& op)
+{
+  u32 needed = 0, written = 0;
+  op.status = encodeDevice(ctx, op.er, needed, written);
+  op.bytes = op.er.dOut ? written : needed;
+}
+
+void decodeAgain(Context& ctx, AsyncOp& op)
+{
+  trimToBlobSize(op.dr);
+  if (op.streamed) op.dr.startAt(ctx.tiers.below(op.launch.form, op.launch.shape));    // (that streaming form has just refused this blob)
+  op.status = decodeDevice(ctx, op.dr);
+  if (op.status == kFailed) wipeDecodeOutputs(ctx, op.dr);
+}
+
 // Brings every operation of the context to its result.  The stream is waited for once; verdicts are then read in enqueue
-// order.  An operation the streaming kernels handed back (or that never was theirs) is repeated through the synchronous
-// path -- and so is everything enqueued behind it, which may have worked on what it had not produced yet.
+// order.  After the first operation that needs repeating -- the streaming kernels handed it back, or it never was theirs --
+// everything behind it is repeated too: it may have worked on what that one had not produced yet.
 void completeAll(lerc_amd_context* h)
 {
   bool pending = false;
   for (const AsyncOp& op : h->ops) pending = pending || !op.done;
   if (!pending) return;
   Context& ctx = h->ctx;
-  const bool synced = ctx.sync();
-  bool rerun = !synced;
+  bool repeat = !ctx.sync();
   for (AsyncOp& op : h->ops)
   {
     if (op.done) continue;
-    if (!rerun && op.streamed)
-    {
-      const u8* slot = ctx.asyncSlot(op.ticket);
-      if (op.isEncode)
-      {
-        bool redo = false;
-        u32 needed = 0, written = 0;
-        encodeStreamingVerdict(ctx, op.er, slot, redo, op.status, needed, written);
-        op.bytes = op.er.dOut ? written : needed;
-        rerun = redo;
-      }
-      else rerun = !decodeStreamingVerdict(ctx, slot, op.launch);
-      if (!rerun) { if (!op.isEncode) ctx.pathCount[2]++; op.done = true; continue; }
-    }
-    rerun = true;
-    if (op.isEncode)
-    {
-      u32 needed = 0, written = 0;
-      op.status = encodeDevice(ctx, op.er, needed, written);
-      op.bytes = op.er.dOut ? written : needed;
-    }
-    else
-    {
-      // (the blob's true length: an asynchronous decode may have been given the capacity of the buffer an encode still
-      // in flight was writing to; the synchronous path wants the blob's own size)
-      if (op.dr.dBlob && !op.dr.hBlob && op.dr.blobSize >= 70)
-      {
-        u8 head[64];
-        if (hipMemcpy(head, op.dr.dBlob, sizeof(head), hipMemcpyDeviceToHost) == hipSuccess)
-        {
-          BlobInfo info;
-          if (getBlobInfo(head, sizeof(head), info) == kOk && info.blobSize >= 70 && info.blobSize <= op.dr.blobSize) op.dr.blobSize = info.blobSize;
-        }
-      }
-      if (op.streamed) op.dr.startAt(ctx.tiers.below(op.launch.form, op.launch.shape));    // (that streaming form has just refused this blob)
-      op.status = decodeDevice(ctx, op.dr);
-      if (op.status == kFailed) wipeDecodeOutputs(ctx, op.dr);
-    }
+    repeat = repeat || !op.streamed || !(op.isEncode ? encodeVerdict(ctx, op) : decodeVerdict(ctx, op));
+    if (repeat) { if (op.isEncode) encodeAgain(ctx, op); else decodeAgain(ctx, op); }
     op.done = true;
   }
 }
 
-unsigned pushOp(lerc_amd_context* h, AsyncOp& op)
+// Queues the operation under a new ticket -> the queued operation, whose pinned result slot is ctx.asyncSlot(ticket).
+AsyncOp& pushOp(lerc_amd_context* h, const AsyncOp& op)
 {
   // results nobody asked for do not pile up: beyond the pinned slots' number the oldest are brought to their end and dropped
   if (h->ops.size() >= (size_t)Context::kAsyncSlots - 1) { completeAll(h); while (h->ops.size() >= (size_t)Context::kAsyncSlots / 2) h->ops.pop_front(); }
-  op.ticket = h->nextTicket++;
-  if (h->nextTicket == 0) h->nextTicket = 1;
   h->ops.push_back(op);
-  return op.ticket;
+  AsyncOp& q = h->ops.back();
+  q.ticket = h->nextTicket++;
+  if (h->nextTicket == 0) h->nextTicket = 1;
+  return q;
 }
 
 }    // namespace
@@ -561,19 +663,14 @@ lerc_status lerc_amd_encode_device_async(lerc_amd_context* h, const void* dData,
 {
   if (!h || !ticket) return kWrongParam;
   *ticket = 0;
-  if (!dData || dataType >= DT_Undefined || nDepth <= 0 || nCols <= 0 || nRows <= 0 || nBands <= 0 || maxZErr < 0) return kWrongParam;
-  if (!masksArgOk(nMasks, nBands, dValidBytes)) return kWrongParam;
-  if (!dimsOk(nDepth, nCols, nRows, (size_t)dtSize((int)dataType))) return kDimsTooLarge;
+  if (const lerc_status bad = deviceRasterArgs(dData, dataType, nDepth, nCols, nRows, nBands, nMasks, dValidBytes, maxZErr)) return bad;
   AsyncOp op;
   op.isEncode = true;
-  EncodeRequest& rq = op.er;
-  rq.dData = dData; rq.dValidBytes = dValidBytes; rq.dt = (int)dataType; rq.nDepth = nDepth; rq.nCols = nCols; rq.nRows = nRows;
-  rq.nBands = nBands; rq.nMasks = nMasks; rq.maxZErr = maxZErr; rq.dOut = dOutBuffer; rq.outCapacity = outBufferSize;
-  const unsigned t = pushOp(h, op);
-  AsyncOp& q = h->ops.back();
-  q.streamed = encodeEnqueueStreaming(h->ctx, q.er, h->ctx.asyncSlot(t));
+  op.er = encodeRequest(dData, dataType, nDepth, nCols, nRows, nBands, nMasks, dValidBytes, maxZErr, dOutBuffer, outBufferSize);
+  AsyncOp& q = pushOp(h, op);
+  q.streamed = encodeEnqueueStreaming(h->ctx, q.er, h->ctx.asyncSlot(q.ticket));
   if (!q.streamed) completeAll(h);    // not a request the streaming kernels take: done on the spot (in order, behind what is in flight)
-  *ticket = t;
+  *ticket = q.ticket;
   return kOk;
 }
 
@@ -582,19 +679,14 @@ lerc_status lerc_amd_decode_device_async(lerc_amd_context* h, const unsigned cha
 {
   if (!h || !ticket) return kWrongParam;
   *ticket = 0;
-  if (!dLercBlob || !blobSizeBound || !dData || dataType >= DT_Undefined || nDepth <= 0 || nCols <= 0 || nRows <= 0 || nBands <= 0)
-    return kWrongParam;
-  if (!masksArgOk(nMasks, nBands, dValidBytes)) return kWrongParam;
-  if (!dimsOk(nDepth, nCols, nRows, (size_t)dtSize((int)dataType))) return kDimsTooLarge;
+  if (!dLercBlob || !blobSizeBound) return kWrongParam;
+  if (const lerc_status bad = deviceRasterArgs(dData, dataType, nDepth, nCols, nRows, nBands, nMasks, dValidBytes)) return bad;
   AsyncOp op;
-  DecodeRequest& rq = op.dr;
-  rq.dBlob = dLercBlob; rq.blobSize = blobSizeBound; rq.dt = (int)dataType; rq.nDepth = nDepth; rq.nCols = nCols; rq.nRows = nRows;
-  rq.nBands = nBands; rq.nMasks = nMasks; rq.dOut = dData; rq.dValidBytes = dValidBytes;
-  const unsigned t = pushOp(h, op);
-  AsyncOp& q = h->ops.back();
-  q.streamed = decodeEnqueueStreaming(h->ctx, q.dr, h->ctx.asyncSlot(t), q.launch);
+  op.dr = decodeRequest(nullptr, dLercBlob, blobSizeBound, nMasks, dValidBytes, nDepth, nCols, nRows, nBands, dataType, dData);
+  AsyncOp& q = pushOp(h, op);
+  q.streamed = decodeEnqueueStreaming(h->ctx, q.dr, h->ctx.asyncSlot(q.ticket), q.launch);
   if (!q.streamed) completeAll(h);
-  *ticket = t;
+  *ticket = q.ticket;
   return kOk;
 }
 
@@ -615,166 +707,110 @@ lerc_status lerc_amd_finish(lerc_amd_context* h, unsigned int ticket, unsigned i
   return kWrongParam;    // no such operation (handed out before, or dropped behind more than kAsyncSlots / 2 newer ones)
 }
 
+// ---- tile batches (codec_tiles_batch.cpp): these calls check their pointers themselves
 lerc_status lerc_amd_encode_tiles_device(lerc_amd_context* h, const void* dTiles, unsigned int dataType, int nCols, int nRows, int nTiles,
   double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity, unsigned long long* offsets, unsigned int* sizes,
   unsigned long long* arenaUsed)
 {
-  if (!h || !dTiles || !dArena || !offsets || !sizes || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || nTiles <= 0 || maxZErr < 0)
-    return kWrongParam;
-  if (!dimsOk(1, nCols, nRows, (size_t)dtSize((int)dataType))) return kDimsTooLarge;
-  TilesEncodeRequest rq;
-  rq.dData = dTiles; rq.dt = (int)dataType; rq.nCols = nCols; rq.nRows = nRows; rq.nTiles = nTiles; rq.maxZErr = maxZErr;
-  rq.dArena = dArena; rq.arenaCapacity = arenaCapacity; rq.hOffsets = offsets; rq.hSizes = sizes;
+  if (const lerc_status bad = tileBatchArgs(h, dataType, nCols, nRows, nTiles, dTiles && dArena && offsets && sizes && !(maxZErr < 0))) return bad;
   u64 used = 0;
-  const u32 rc = encodeTilesDevice(h->ctx, rq, used);
-  if (arenaUsed) *arenaUsed = used;
-  return rc;
+  const u32 rc = encodeTilesDevice(h->ctx, tilesEncodeRequest(dTiles, dataType, nCols, nRows, nTiles, maxZErr, dArena, arenaCapacity, offsets, sizes), used);
+  return finishTilesEncode(rc, used, 0, nTiles, offsets, arenaUsed);
 }
 
 lerc_status lerc_amd_encode_tiles_device_slots(lerc_amd_context* h, const void* dTiles, unsigned int dataType, int nCols, int nRows, int nTiles,
   double maxZErr, unsigned char* dSlots, unsigned long long slotBytes, unsigned int* sizes)
 {
-  if (!h || !dTiles || !dSlots || !sizes || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || nTiles <= 0 || maxZErr < 0
-    || slotBytes == 0 || (slotBytes & 15u) != 0)
-    return kWrongParam;
-  if (!dimsOk(1, nCols, nRows, (size_t)dtSize((int)dataType))) return kDimsTooLarge;
+  if (const lerc_status bad = tileBatchArgs(h, dataType, nCols, nRows, nTiles, dTiles && dSlots && sizes && !(maxZErr < 0) && slotBytesOk(slotBytes, false)))
+    return bad;
   std::vector<u64> offsets((size_t)nTiles);
-  TilesEncodeRequest rq;
-  rq.dData = dTiles; rq.dt = (int)dataType; rq.nCols = nCols; rq.nRows = nRows; rq.nTiles = nTiles; rq.maxZErr = maxZErr;
-  rq.dArena = dSlots; rq.arenaCapacity = (u64)nTiles * slotBytes; rq.hOffsets = offsets.data(); rq.hSizes = sizes; rq.slotBytes = slotBytes;
-  u64 used = 0;
-  return encodeTilesDevice(h->ctx, rq, used);
+  u64 used = 0;    // (not reported: every slot is the caller's, t * slotBytes is where tile t lies)
+  return encodeTilesDevice(h->ctx, tilesEncodeRequest(dTiles, dataType, nCols, nRows, nTiles, maxZErr, dSlots, (u64)nTiles * slotBytes, offsets.data(),
+                                                      sizes, slotBytes), used);
 }
 
 lerc_status lerc_amd_decode_tiles_device_slots(lerc_amd_context* h, const unsigned char* dSlots, unsigned long long slotBytes,
   const unsigned int* sizes, int nTiles, int nCols, int nRows, unsigned int dataType, void* dTiles)
 {
-  if (!h || !dSlots || !sizes || !dTiles || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || nTiles <= 0 || slotBytes == 0 || (slotBytes & 15u) != 0)
-    return kWrongParam;
-  if (!dimsOk(1, nCols, nRows, (size_t)dtSize((int)dataType))) return kDimsTooLarge;
+  if (const lerc_status bad = tileBatchArgs(h, dataType, nCols, nRows, nTiles, dSlots && sizes && dTiles && slotBytesOk(slotBytes, false))) return bad;
   std::vector<u64> offsets((size_t)nTiles);
   for (int t = 0; t < nTiles; t++) offsets[(size_t)t] = (u64)t * slotBytes;
-  TilesDecodeRequest rq;
-  rq.dArena = dSlots; rq.hOffsets = offsets.data(); rq.hSizes = sizes; rq.dt = (int)dataType; rq.nCols = nCols; rq.nRows = nRows; rq.nTiles = nTiles;
-  rq.dOut = dTiles;
-  return decodeTilesDevice(h->ctx, rq);
+  return decodeTilesDevice(h->ctx, tilesDecodeRequest(dSlots, offsets.data(), sizes, nTiles, nCols, nRows, dataType, dTiles));
 }
 
 lerc_status lerc_amd_decode_tiles_device(lerc_amd_context* h, const unsigned char* dArena, const unsigned long long* offsets,
   const unsigned int* sizes, int nTiles, int nCols, int nRows, unsigned int dataType, void* dTiles)
 {
-  if (!h || !dArena || !offsets || !sizes || !dTiles || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || nTiles <= 0) return kWrongParam;
-  if (!dimsOk(1, nCols, nRows, (size_t)dtSize((int)dataType))) return kDimsTooLarge;
-  TilesDecodeRequest rq;
-  rq.dArena = dArena; rq.hOffsets = offsets; rq.hSizes = sizes; rq.dt = (int)dataType; rq.nCols = nCols; rq.nRows = nRows; rq.nTiles = nTiles;
-  rq.dOut = dTiles;
-  return decodeTilesDevice(h->ctx, rq);
+  if (const lerc_status bad = tileBatchArgs(h, dataType, nCols, nRows, nTiles, dArena && offsets && sizes && dTiles)) return bad;
+  return decodeTilesDevice(h->ctx, tilesDecodeRequest(dArena, offsets, sizes, nTiles, nCols, nRows, dataType, dTiles));
 }
 
 lerc_status lerc_amd_encode_tiles_device_masked(lerc_amd_context* h, const void* dTiles, unsigned int dataType, int nCols, int nRows, int nTiles,
   const unsigned char* dValidBytes, double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity, unsigned long long slotBytes,
   unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed)
 {
-  if (!h || !dTiles || !dArena || !offsets || !sizes || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || nTiles <= 0 || maxZErr < 0
-    || (slotBytes & 15u) != 0)
-    return kWrongParam;
-  if (!dimsOk(1, nCols, nRows, (size_t)dtSize((int)dataType))) return kDimsTooLarge;
-  TilesEncodeRequest rq;
-  rq.dData = dTiles; rq.dt = (int)dataType; rq.nCols = nCols; rq.nRows = nRows; rq.nTiles = nTiles; rq.maxZErr = maxZErr;
-  rq.dArena = dArena; rq.arenaCapacity = arenaCapacity; rq.hOffsets = offsets; rq.hSizes = sizes; rq.slotBytes = slotBytes;
-  rq.dValidBytes = dValidBytes;
+  if (const lerc_status bad = tileBatchArgs(h, dataType, nCols, nRows, nTiles,
+                                            dTiles && dArena && offsets && sizes && !(maxZErr < 0) && slotBytesOk(slotBytes, true)))
+    return bad;
   u64 used = 0;
-  const u32 rc = encodeTilesDeviceMasked(h->ctx, rq, used);
-  if (rc == kOk && slotBytes) for (int t = 0; t < nTiles; t++) offsets[t] = (u64)t * slotBytes;
-  if (arenaUsed) *arenaUsed = used;
-  return rc;
+  const u32 rc = encodeTilesDeviceMasked(h->ctx, tilesEncodeRequest(dTiles, dataType, nCols, nRows, nTiles, maxZErr, dArena, arenaCapacity, offsets, sizes,
+                                                                    slotBytes, dValidBytes), used);
+  return finishTilesEncode(rc, used, slotBytes, nTiles, offsets, arenaUsed);
 }
 
 lerc_status lerc_amd_decode_tiles_device_masked(lerc_amd_context* h, const unsigned char* dArena, const unsigned long long* offsets,
   const unsigned int* sizes, int nTiles, int nCols, int nRows, unsigned int dataType, void* dTiles, unsigned char* dValidBytes)
 {
-  if (!h || !dArena || !offsets || !sizes || !dTiles || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || nTiles <= 0) return kWrongParam;
-  if (!dimsOk(1, nCols, nRows, (size_t)dtSize((int)dataType))) return kDimsTooLarge;
-  TilesDecodeRequest rq;
-  rq.dArena = dArena; rq.hOffsets = offsets; rq.hSizes = sizes; rq.dt = (int)dataType; rq.nCols = nCols; rq.nRows = nRows; rq.nTiles = nTiles;
-  rq.dOut = dTiles; rq.dValidBytes = dValidBytes;
-  return decodeTilesDeviceMasked(h->ctx, rq);
+  if (const lerc_status bad = tileBatchArgs(h, dataType, nCols, nRows, nTiles, dArena && offsets && sizes && dTiles)) return bad;
+  return decodeTilesDeviceMasked(h->ctx, tilesDecodeRequest(dArena, offsets, sizes, nTiles, nCols, nRows, dataType, dTiles, dValidBytes));
 }
 
 lerc_status lerc_amd_encode_tiles_device_bands(lerc_amd_context* h, const void* dTiles, unsigned int dataType, int nCols, int nRows, int nBands,
   int nTiles, int nMasks, const unsigned char* dValidBytes, double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity,
   unsigned long long slotBytes, unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed)
 {
-  if (!h || !dTiles || !dArena || !offsets || !sizes || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || nBands <= 0 || nTiles <= 0 || maxZErr < 0
-    || (slotBytes & 15u) != 0 || (nMasks != 0 && nMasks != 1 && nMasks != nBands) || (nMasks == 0) != (dValidBytes == nullptr))
-    return kWrongParam;
-  if (!dimsOk(1, nCols, nRows, (size_t)dtSize((int)dataType))) return kDimsTooLarge;
-  TilesEncodeRequest rq;
-  rq.dData = dTiles; rq.dt = (int)dataType; rq.nCols = nCols; rq.nRows = nRows; rq.nTiles = nTiles; rq.maxZErr = maxZErr;
-  rq.dArena = dArena; rq.arenaCapacity = arenaCapacity; rq.hOffsets = offsets; rq.hSizes = sizes; rq.slotBytes = slotBytes;
-  rq.dValidBytes = dValidBytes; rq.nBands = nBands; rq.nMasks = nMasks;
+  if (const lerc_status bad = tileBatchArgs(h, dataType, nCols, nRows, nTiles, dTiles && dArena && offsets && sizes && nBands > 0 && !(maxZErr < 0)
+                                            && slotBytesOk(slotBytes, true) && bandStackMasksOk(nMasks, nBands, dValidBytes)))
+    return bad;
   u64 used = 0;
-  const u32 rc = encodeTilesDeviceBands(h->ctx, rq, used);
-  if (rc == kOk && slotBytes) for (int t = 0; t < nTiles; t++) offsets[t] = (u64)t * slotBytes;
-  if (arenaUsed) *arenaUsed = used;
-  return rc;
+  const u32 rc = encodeTilesDeviceBands(h->ctx, tilesEncodeRequest(dTiles, dataType, nCols, nRows, nTiles, maxZErr, dArena, arenaCapacity, offsets, sizes,
+                                                                   slotBytes, dValidBytes, nBands, nMasks), used);
+  return finishTilesEncode(rc, used, slotBytes, nTiles, offsets, arenaUsed);
 }
 
 lerc_status lerc_amd_decode_tiles_device_bands(lerc_amd_context* h, const unsigned char* dArena, const unsigned long long* offsets,
   const unsigned int* sizes, int nTiles, int nCols, int nRows, int nBands, unsigned int dataType, void* dTiles, int nMasks, unsigned char* dValidBytes)
 {
-  if (!h || !dArena || !offsets || !sizes || !dTiles || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || nBands <= 0 || nTiles <= 0
-    || (nMasks != 0 && nMasks != 1 && nMasks != nBands) || (nMasks == 0) != (dValidBytes == nullptr))
-    return kWrongParam;
-  if (!dimsOk(1, nCols, nRows, (size_t)dtSize((int)dataType))) return kDimsTooLarge;
-  TilesDecodeRequest rq;
-  rq.dArena = dArena; rq.hOffsets = offsets; rq.hSizes = sizes; rq.dt = (int)dataType; rq.nCols = nCols; rq.nRows = nRows; rq.nTiles = nTiles;
-  rq.dOut = dTiles; rq.dValidBytes = dValidBytes; rq.nBands = nBands; rq.nMasks = nMasks;
-  return decodeTilesDeviceBands(h->ctx, rq);
+  if (const lerc_status bad = tileBatchArgs(h, dataType, nCols, nRows, nTiles,
+                                            dArena && offsets && sizes && dTiles && nBands > 0 && bandStackMasksOk(nMasks, nBands, dValidBytes)))
+    return bad;
+  return decodeTilesDeviceBands(h->ctx, tilesDecodeRequest(dArena, offsets, sizes, nTiles, nCols, nRows, dataType, dTiles, dValidBytes, nBands, nMasks));
 }
 
 void lerc_amd_tile_batch_counters(lerc_amd_context* h, unsigned long long out[4])
 {
-  for (int i = 0; i < 4; i++) out[i] = h ? h->ctx.tileBatchCount[i] : 0;
+  readCounters(h, [](Context& c) -> Counters { return c.tileBatchCount; }, out);
 }
 
 // ---- a pitched raster cut into a grid of tiles (codec_raster_tiles.cpp)
-static bool rasterTileDimsOk(int nCols, int nRows, int tileCols, int tileRows, unsigned int dataType)
-{
-  return dimsOk(1, std::min(nCols, tileCols), std::min(nRows, tileRows), (size_t)dtSize((int)dataType));
-}
-
 lerc_status lerc_amd_encode_raster_tiles_device(lerc_amd_context* h, const void* dRaster, unsigned int dataType, int nCols, int nRows, int nBands,
   unsigned long long rowPitch, unsigned long long bandPitch, int tileCols, int tileRows, int nMasks, const unsigned char* dValidBytes,
   unsigned long long maskRowPitch, double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity, unsigned long long slotBytes,
   unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed)
 {
   if (arenaUsed) *arenaUsed = 0;
-  if (!h || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || tileCols <= 0 || tileRows <= 0) return kWrongParam;
-  if (!rasterTileDimsOk(nCols, nRows, tileCols, tileRows, dataType)) return kDimsTooLarge;
-  RasterTilesRequest rq;
-  rq.dRaster = const_cast<void*>(dRaster); rq.dValidBytes = const_cast<unsigned char*>(dValidBytes); rq.dt = (int)dataType;
-  rq.nCols = nCols; rq.nRows = nRows; rq.nBands = nBands; rq.nMasks = nMasks; rq.tileCols = tileCols; rq.tileRows = tileRows;
-  rq.rowPitch = rowPitch; rq.bandPitch = bandPitch; rq.maskRowPitch = maskRowPitch;
-  rq.dArena = dArena; rq.hOffsets = offsets; rq.hSizes = sizes; rq.maxZErr = maxZErr; rq.arenaCapacity = arenaCapacity; rq.slotBytes = slotBytes;
-  u64 used = 0;
-  const u32 rc = encodeRasterTilesDevice(h->ctx, rq, used);
-  if (arenaUsed) *arenaUsed = used;
-  return rc;
+  if (const lerc_status bad = rasterTilesArgs(h, dataType, nCols, nRows, tileCols, tileRows)) return bad;
+  return encodeRasterTiles(h, rasterTilesRequest(dRaster, dataType, nCols, nRows, nBands, planes(rowPitch, bandPitch, maskRowPitch), tileCols, tileRows,
+                                                 nMasks, dValidBytes, dArena, offsets, sizes, maxZErr, arenaCapacity, slotBytes), arenaUsed);
 }
 
 lerc_status lerc_amd_decode_raster_tiles_device(lerc_amd_context* h, const unsigned char* dArena, const unsigned long long* offsets,
   const unsigned int* sizes, unsigned int dataType, int nCols, int nRows, int nBands, unsigned long long rowPitch, unsigned long long bandPitch,
   int tileCols, int tileRows, void* dRaster, int nMasks, unsigned char* dValidBytes, unsigned long long maskRowPitch)
 {
-  if (!h || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || tileCols <= 0 || tileRows <= 0) return kWrongParam;
-  if (!rasterTileDimsOk(nCols, nRows, tileCols, tileRows, dataType)) return kDimsTooLarge;
-  RasterTilesRequest rq;
-  rq.dRaster = dRaster; rq.dValidBytes = dValidBytes; rq.dt = (int)dataType;
-  rq.nCols = nCols; rq.nRows = nRows; rq.nBands = nBands; rq.nMasks = nMasks; rq.tileCols = tileCols; rq.tileRows = tileRows;
-  rq.rowPitch = rowPitch; rq.bandPitch = bandPitch; rq.maskRowPitch = maskRowPitch;
-  rq.dArena = const_cast<unsigned char*>(dArena); rq.hOffsets = const_cast<unsigned long long*>(offsets); rq.hSizes = const_cast<unsigned int*>(sizes);
-  return decodeRasterTilesDevice(h->ctx, rq);
+  if (const lerc_status bad = rasterTilesArgs(h, dataType, nCols, nRows, tileCols, tileRows)) return bad;
+  return decodeRasterTilesDevice(h->ctx, rasterTilesRequest(dRaster, dataType, nCols, nRows, nBands, planes(rowPitch, bandPitch, maskRowPitch), tileCols,
+                                                            tileRows, nMasks, dValidBytes, dArena, offsets, sizes));
 }
 
 // ---- the same with a pixel pitch: line- and pixel-interleaved rasters (pixelPitch 1 and band-sequential: the calls above)
@@ -784,31 +820,18 @@ lerc_status lerc_amd_encode_raster_tiles_device_strided(lerc_amd_context* h, con
   unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed)
 {
   if (arenaUsed) *arenaUsed = 0;
-  if (!h || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || tileCols <= 0 || tileRows <= 0) return kWrongParam;
-  if (!rasterTileDimsOk(nCols, nRows, tileCols, tileRows, dataType)) return kDimsTooLarge;
-  RasterTilesRequest rq;
-  rq.dRaster = const_cast<void*>(dRaster); rq.dValidBytes = const_cast<unsigned char*>(dValidBytes); rq.dt = (int)dataType;
-  rq.nCols = nCols; rq.nRows = nRows; rq.nBands = nBands; rq.nMasks = nMasks; rq.tileCols = tileCols; rq.tileRows = tileRows;
-  rq.pixelPitch = pixelPitch; rq.anyLayout = true; rq.rowPitch = rowPitch; rq.bandPitch = bandPitch; rq.maskRowPitch = maskRowPitch;
-  rq.dArena = dArena; rq.hOffsets = offsets; rq.hSizes = sizes; rq.maxZErr = maxZErr; rq.arenaCapacity = arenaCapacity; rq.slotBytes = slotBytes;
-  u64 used = 0;
-  const u32 rc = encodeRasterTilesDevice(h->ctx, rq, used);
-  if (arenaUsed) *arenaUsed = used;
-  return rc;
+  if (const lerc_status bad = rasterTilesArgs(h, dataType, nCols, nRows, tileCols, tileRows)) return bad;
+  return encodeRasterTiles(h, rasterTilesRequest(dRaster, dataType, nCols, nRows, nBands, strided(pixelPitch, rowPitch, bandPitch, maskRowPitch), tileCols,
+                                                 tileRows, nMasks, dValidBytes, dArena, offsets, sizes, maxZErr, arenaCapacity, slotBytes), arenaUsed);
 }
 
 lerc_status lerc_amd_decode_raster_tiles_device_strided(lerc_amd_context* h, const unsigned char* dArena, const unsigned long long* offsets,
   const unsigned int* sizes, unsigned int dataType, int nCols, int nRows, int nBands, unsigned long long pixelPitch, unsigned long long rowPitch, unsigned long long bandPitch,
   int tileCols, int tileRows, void* dRaster, int nMasks, unsigned char* dValidBytes, unsigned long long maskRowPitch)
 {
-  if (!h || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || tileCols <= 0 || tileRows <= 0) return kWrongParam;
-  if (!rasterTileDimsOk(nCols, nRows, tileCols, tileRows, dataType)) return kDimsTooLarge;
-  RasterTilesRequest rq;
-  rq.dRaster = dRaster; rq.dValidBytes = dValidBytes; rq.dt = (int)dataType;
-  rq.nCols = nCols; rq.nRows = nRows; rq.nBands = nBands; rq.nMasks = nMasks; rq.tileCols = tileCols; rq.tileRows = tileRows;
-  rq.pixelPitch = pixelPitch; rq.anyLayout = true; rq.rowPitch = rowPitch; rq.bandPitch = bandPitch; rq.maskRowPitch = maskRowPitch;
-  rq.dArena = const_cast<unsigned char*>(dArena); rq.hOffsets = const_cast<unsigned long long*>(offsets); rq.hSizes = const_cast<unsigned int*>(sizes);
-  return decodeRasterTilesDevice(h->ctx, rq);
+  if (const lerc_status bad = rasterTilesArgs(h, dataType, nCols, nRows, tileCols, tileRows)) return bad;
+  return decodeRasterTilesDevice(h->ctx, rasterTilesRequest(dRaster, dataType, nCols, nRows, nBands, strided(pixelPitch, rowPitch, bandPitch, maskRowPitch),
+                                                            tileCols, tileRows, nMasks, dValidBytes, dArena, offsets, sizes));
 }
 
 // ---- a range of the grid's tiles coded, and a window of the mosaic decoded into a buffer of its own
@@ -818,19 +841,12 @@ lerc_status lerc_amd_encode_raster_tiles_device_range(lerc_amd_context* h, const
   unsigned long long arenaCapacity, unsigned long long slotBytes, unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed)
 {
   if (arenaUsed) *arenaUsed = 0;
-  if (!h || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || tileCols <= 0 || tileRows <= 0) return kWrongParam;
-  if (tileCol0 < 0 || tileRow0 < 0 || nTileCols <= 0 || nTileRows <= 0) return kWrongParam;    // (inside the grid: the driver's check)
-  if (!rasterTileDimsOk(nCols, nRows, tileCols, tileRows, dataType)) return kDimsTooLarge;
-  RasterTilesRequest rq;
-  rq.dRaster = const_cast<void*>(dRaster); rq.dValidBytes = const_cast<unsigned char*>(dValidBytes); rq.dt = (int)dataType;
-  rq.nCols = nCols; rq.nRows = nRows; rq.nBands = nBands; rq.nMasks = nMasks; rq.tileCols = tileCols; rq.tileRows = tileRows;
+  const bool rangeOk = !(tileCol0 < 0 || tileRow0 < 0 || nTileCols <= 0 || nTileRows <= 0);    // (inside the grid: the driver's check)
+  if (const lerc_status bad = rasterTilesArgs(h, dataType, nCols, nRows, tileCols, tileRows, rangeOk)) return bad;
+  RasterTilesRequest rq = rasterTilesRequest(dRaster, dataType, nCols, nRows, nBands, strided(pixelPitch, rowPitch, bandPitch, maskRowPitch), tileCols,
+                                             tileRows, nMasks, dValidBytes, dArena, offsets, sizes, maxZErr, arenaCapacity, slotBytes);
   rq.tileCol0 = tileCol0; rq.tileRow0 = tileRow0; rq.nTileCols = nTileCols; rq.nTileRows = nTileRows;
-  rq.pixelPitch = pixelPitch; rq.anyLayout = true; rq.rowPitch = rowPitch; rq.bandPitch = bandPitch; rq.maskRowPitch = maskRowPitch;
-  rq.dArena = dArena; rq.hOffsets = offsets; rq.hSizes = sizes; rq.maxZErr = maxZErr; rq.arenaCapacity = arenaCapacity; rq.slotBytes = slotBytes;
-  u64 used = 0;
-  const u32 rc = encodeRasterTilesDevice(h->ctx, rq, used);
-  if (arenaUsed) *arenaUsed = used;
-  return rc;
+  return encodeRasterTiles(h, rq, arenaUsed);
 }
 
 lerc_status lerc_amd_decode_raster_window_device(lerc_amd_context* h, const unsigned char* dArena, const unsigned long long* offsets,
@@ -838,21 +854,16 @@ lerc_status lerc_amd_decode_raster_window_device(lerc_amd_context* h, const unsi
   int winCols, int winRows, void* dWindow, unsigned long long pixelPitch, unsigned long long rowPitch, unsigned long long bandPitch, int nMasks,
   unsigned char* dValidBytes, unsigned long long maskRowPitch)
 {
-  if (!h || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || tileCols <= 0 || tileRows <= 0) return kWrongParam;
-  if (!rasterTileDimsOk(nCols, nRows, tileCols, tileRows, dataType)) return kDimsTooLarge;
-  RasterTilesRequest rq;
-  rq.dRaster = dWindow; rq.dValidBytes = dValidBytes; rq.dt = (int)dataType;
-  rq.nCols = nCols; rq.nRows = nRows; rq.nBands = nBands; rq.nMasks = nMasks; rq.tileCols = tileCols; rq.tileRows = tileRows;
-  rq.pixelPitch = pixelPitch; rq.anyLayout = true; rq.rowPitch = rowPitch; rq.bandPitch = bandPitch; rq.maskRowPitch = maskRowPitch;
-  rq.dArena = const_cast<unsigned char*>(dArena); rq.hOffsets = const_cast<unsigned long long*>(offsets); rq.hSizes = const_cast<unsigned int*>(sizes);
+  if (const lerc_status bad = rasterTilesArgs(h, dataType, nCols, nRows, tileCols, tileRows)) return bad;
   RasterWindow win;
   win.col0 = winCol0; win.row0 = winRow0; win.cols = winCols; win.rows = winRows;
-  return decodeRasterWindowDevice(h->ctx, rq, win);
+  return decodeRasterWindowDevice(h->ctx, rasterTilesRequest(dWindow, dataType, nCols, nRows, nBands, strided(pixelPitch, rowPitch, bandPitch, maskRowPitch),
+                                                             tileCols, tileRows, nMasks, dValidBytes, dArena, offsets, sizes), win);
 }
 
 void lerc_amd_raster_tiles_counters(lerc_amd_context* h, unsigned long long out[4])
 {
-  for (int i = 0; i < 4; i++) out[i] = h ? h->ctx.rasterTilesCount[i] : 0;
+  readCounters(h, [](Context& c) -> Counters { return c.rasterTilesCount; }, out);
 }
 
 void lerc_amd_profile_enable(lerc_amd_context* h, int on) { if (h) h->ctx.profEnable(on != 0); }
@@ -869,20 +880,18 @@ int lerc_amd_profile_read(lerc_amd_context* h, char* buf, int cap, int reset)
 
 const char* lerc_amd_last_note(lerc_amd_context* h)
 {
-  if (!h) h = threadHandle();
+  h = orThisThreads(h);
   return h ? h->ctx.lastNote.c_str() : "";
 }
 
 void lerc_amd_path_counters(lerc_amd_context* h, unsigned long long out[4])
 {
-  if (!h) h = threadHandle();    // the context behind the stock host-pointer entry points of this thread
-  for (int i = 0; i < 4; i++) out[i] = h ? h->ctx.pathCount[i] : 0;
+  readCounters(orThisThreads(h), [](Context& c) -> Counters { return c.pathCount; }, out);
 }
 
 void lerc_amd_decode_forms(lerc_amd_context* h, unsigned long long out[4])
 {
-  if (!h) h = threadHandle();
-  for (int i = 0; i < 4; i++) out[i] = h ? h->ctx.tiers.formCount[i] : 0;
+  readCounters(orThisThreads(h), [](Context& c) -> Counters { return c.tiers.formCount; }, out);
 }
 
 unsigned int lerc_amd_gather_blobs(lerc_amd_context* h, void* ncclComm, int root, const void* dMessage, unsigned long long nBytes,
@@ -898,8 +907,7 @@ unsigned int lerc_amd_gather_blobs(lerc_amd_context* h, void* ncclComm, int root
 
 void lerc_amd_decode_refusals(lerc_amd_context* h, unsigned long long out[4])
 {
-  if (!h) h = threadHandle();
-  for (int i = 0; i < 4; i++) out[i] = h ? h->ctx.tiers.refusalCount[i] : 0;
+  readCounters(orThisThreads(h), [](Context& c) -> Counters { return c.tiers.refusalCount; }, out);
 }
 
 unsigned int lerc_amd_mask_rle_device(lerc_amd_context* h, const unsigned char* dBits, unsigned int nBytes, unsigned char* dOut,

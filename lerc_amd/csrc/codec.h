@@ -300,6 +300,8 @@ bool encodeEnqueueStreaming(Context& ctx, const EncodeRequest& rq, u8* slot);
 void encodeStreamingVerdict(Context& ctx, const EncodeRequest& rq, const u8* slot, bool& redo, u32& status, u32& numBytesNeeded, u32& numBytesWritten);
 bool decodeEnqueueStreaming(Context& ctx, const DecodeRequest& rq, u8* slot, StreamTicket& ticket);
 bool decodeStreamingVerdict(Context& ctx, const u8* slot, const StreamTicket& ticket, u32* bits = nullptr);    // true: decoded, checksum good (bits: why not)
+// may a host-pointer decode go through decodeSpeculativeToHost?  hd: the blob's first header; rq: the call (shape, type, blobSize, noData arrays)
+bool speculativeDecodeEligible(const Header& hd, const DecodeRequest& rq);
 // host-pointer calls: streaming kernels + the results' way back to the host enqueued together, one wait (rq holds a device copy of the blob)
 u32 decodeSpeculativeToHost(Context& ctx, const DecodeRequest& rq, void* hOut, size_t outBytes, u8* hMask, size_t maskBytes, bool& handled, StreamTicket& ticket);    // ticket.form > 0: the streaming kernels were enqueued (and may have written pixels)
 u32 encodeTilesDevice(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed);

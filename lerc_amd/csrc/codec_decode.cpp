@@ -266,6 +266,16 @@ static u32 decodeSpeculative(Context& ctx, const DecodeRequest& rq, bool& handle
   return kOk;
 }
 
+// What a host-pointer call may send through decodeSpeculativeToHost -- the header says so: one band, every pixel valid, 8 x 8
+// blocks, nDepth 1, the call's own shape and type, neither constant nor lossless-raw.
+bool speculativeDecodeEligible(const Header& hd, const DecodeRequest& rq)
+{
+  const size_t nPix = (size_t)rq.nRows * rq.nCols;
+  return rq.nBands == 1 && rq.nDepth == 1 && !rq.hUsesNoData && hd.version >= 3 && hd.nRows == rq.nRows
+    && hd.nCols == rq.nCols && hd.nDepth == 1 && hd.dt == rq.dt && hd.mbSize == 8 && hd.nBlobsMore == 0
+    && (size_t)hd.numValid == nPix && (unsigned)hd.blobSize <= rq.blobSize && hd.maxZErr > 0 && hd.zMin != hd.zMax;
+}
+
 // Host-pointer calls on a device copy of the blob: the same, with the pixels' (and the mask bytes') way back to the host
 // enqueued behind the kernels, so that the calling thread waits once.  handled == false: the device did not vouch for
 // what it wrote (the caller goes the long way and overwrites it).
