@@ -111,6 +111,20 @@ def load_library():
         lib.lerc_amd_decode_raster_window_device.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int, ct.c_int,
                                                              ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_void_p,
                                                              ct.c_ulonglong, ct.c_ulonglong, ct.c_ulonglong, ct.c_int, ct.c_void_p, ct.c_ulonglong]
+    # (the depth tile calls, include/lerc_amd_depth.h: the same rule)
+    have_depth = not os.environ.get("LERC_AMD_LIBRARY") or hasattr(lib, "lerc_amd_encode_tiles_device_depth")
+    if have_depth:
+        lib.lerc_amd_encode_tiles_device_depth.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_void_p,
+                                                           ct.c_double, ct.c_void_p, ct.c_ulonglong, ct.c_ulonglong, ct.c_void_p, ct.c_void_p,
+                                                           ct.c_void_p]
+        lib.lerc_amd_decode_tiles_device_depth.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_int,
+                                                           ct.c_uint, ct.c_void_p, ct.c_void_p]
+        lib.lerc_amd_encode_raster_tiles_device_depth.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int, ct.c_int, ct.c_int, ct.c_ulonglong,
+                                                                  ct.c_ulonglong, ct.c_int, ct.c_int, ct.c_int, ct.c_void_p, ct.c_ulonglong, ct.c_double,
+                                                                  ct.c_void_p, ct.c_ulonglong, ct.c_ulonglong, ct.c_void_p, ct.c_void_p, ct.c_void_p]
+        lib.lerc_amd_decode_raster_tiles_device_depth.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int, ct.c_int,
+                                                                  ct.c_int, ct.c_ulonglong, ct.c_ulonglong, ct.c_int, ct.c_int, ct.c_void_p, ct.c_int,
+                                                                  ct.c_void_p, ct.c_ulonglong]
     lib.lerc_amd_tile_batch_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_ulonglong)]
     lib.lerc_amd_tile_batch_counters.restype = None
     lib.lerc_amd_encode_device_async.argtypes = [ct.c_void_p] + enc + [ct.c_void_p, ct.c_uint, u32p]
@@ -124,7 +138,9 @@ def load_library():
             (("lerc_amd_encode_tiles_device_bands", "lerc_amd_decode_tiles_device_bands") if have_bands else ()) + \
             (("lerc_amd_encode_raster_tiles_device", "lerc_amd_decode_raster_tiles_device") if have_raster else ()) + \
             (("lerc_amd_encode_raster_tiles_device_strided", "lerc_amd_decode_raster_tiles_device_strided") if have_strided else ()) + \
-            (("lerc_amd_encode_raster_tiles_device_range", "lerc_amd_decode_raster_window_device") if have_window else ()):
+            (("lerc_amd_encode_raster_tiles_device_range", "lerc_amd_decode_raster_window_device") if have_window else ()) + \
+            (("lerc_amd_encode_tiles_device_depth", "lerc_amd_decode_tiles_device_depth", "lerc_amd_encode_raster_tiles_device_depth",
+              "lerc_amd_decode_raster_tiles_device_depth") if have_depth else ()):
         getattr(lib, n).restype = ct.c_uint
     _LIB = lib
     return lib
@@ -313,6 +329,46 @@ class DeviceCodec:
         sizes = np.ascontiguousarray(sizes, np.uint32)
         return self.lib.lerc_amd_decode_tiles_device_bands(self.h, d_arena, offsets.ctypes.data, sizes.ctypes.data, n_tiles, n_cols, n_rows,
                                                            n_bands, dt_code, d_tiles, n_masks, d_valid or None)
+
+    def encode_tiles_depth(self, d_tiles, dt_code, n_cols, n_rows, n_depth, n_tiles, d_valid, max_z_err, d_arena, arena_cap, slot_bytes=0):
+        """depth tiles, raw device addresses: d_tiles [nTiles][nRows][nCols][nDepth], d_valid [nTiles][nRows][nCols] or 0 / None
+        -> (status, offsets uint64[nTiles], sizes uint32[nTiles], arena bytes used), one blob with the header's nDepth a tile"""
+        offsets = np.zeros(n_tiles, np.uint64)
+        sizes = np.zeros(n_tiles, np.uint32)
+        used = ct.c_ulonglong(0)
+        rc = self.lib.lerc_amd_encode_tiles_device_depth(self.h, d_tiles, dt_code, n_cols, n_rows, n_depth, n_tiles, d_valid or None, float(max_z_err),
+                                                         d_arena, int(arena_cap), int(slot_bytes), offsets.ctypes.data, sizes.ctypes.data,
+                                                         ct.byref(used))
+        return rc, offsets, sizes, int(used.value)
+
+    def decode_tiles_depth(self, d_arena, offsets, sizes, n_tiles, n_cols, n_rows, n_depth, dt_code, d_tiles, d_valid):
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        sizes = np.ascontiguousarray(sizes, np.uint32)
+        return self.lib.lerc_amd_decode_tiles_device_depth(self.h, d_arena, offsets.ctypes.data, sizes.ctypes.data, n_tiles, n_cols, n_rows, n_depth,
+                                                           dt_code, d_tiles, d_valid or None)
+
+    def encode_raster_tiles_depth(self, d_raster, dt_code, n_cols, n_rows, n_depth, pixel_pitch, row_pitch, tile, d_valid, mask_row_pitch, max_z_err,
+                                  d_arena, arena_cap, slot_bytes=0):
+        """a raster of packed pixels of n_depth elements (pixel_pitch must equal n_depth; the library's check decides: status 2), coded as
+        depth tiles in the order of raster_tile_grid -> (status, offsets, sizes, arena bytes used)"""
+        n_tiles = len(raster_tile_grid(n_rows, n_cols, tile))
+        offsets = np.zeros(n_tiles, np.uint64)
+        sizes = np.zeros(n_tiles, np.uint32)
+        used = ct.c_ulonglong(0)
+        rc = self.lib.lerc_amd_encode_raster_tiles_device_depth(self.h, d_raster, dt_code, n_cols, n_rows, n_depth, int(pixel_pitch), int(row_pitch),
+                                                                int(tile[1]), int(tile[0]), 1 if d_valid else 0, d_valid or None, int(mask_row_pitch),
+                                                                float(max_z_err), d_arena, int(arena_cap), int(slot_bytes), offsets.ctypes.data,
+                                                                sizes.ctypes.data, ct.byref(used))
+        return rc, offsets, sizes, int(used.value)
+
+    def decode_raster_tiles_depth(self, d_arena, offsets, sizes, dt_code, n_cols, n_rows, n_depth, pixel_pitch, row_pitch, tile, d_raster, d_valid,
+                                  mask_row_pitch):
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        sizes = np.ascontiguousarray(sizes, np.uint32)
+        assert len(offsets) == len(sizes) == len(raster_tile_grid(n_rows, n_cols, tile))
+        return self.lib.lerc_amd_decode_raster_tiles_device_depth(self.h, d_arena, offsets.ctypes.data, sizes.ctypes.data, dt_code, n_cols, n_rows,
+                                                                  n_depth, int(pixel_pitch), int(row_pitch), int(tile[1]), int(tile[0]), d_raster,
+                                                                  1 if d_valid else 0, d_valid or None, int(mask_row_pitch))
 
     def raster_tiles_counters(self):
         """tiles of the raster tile calls of this context: [cut through the staging buffer, encoded where they lie, pasted from the staging
@@ -564,6 +620,59 @@ def decode_tiles_device_bands(codec, arena, offsets, sizes, out, valid_out):
     n_masks, d_valid = _band_masks(valid_out, n_tiles, n_bands, n_rows, n_cols)
     return codec.decode_tiles_bands(arena.data_ptr(), offsets, sizes, n_tiles, n_cols, n_rows, n_bands, _torch_dt_code(out), out.data_ptr(),
                                     n_masks, d_valid)
+
+
+def encode_tiles_device_depth(codec, tiles, valid, max_z_err, arena, slot_bytes=0):
+    """tiles: CUDA(HIP) tensor [nTiles, nRows, nCols, nDepth]; valid: uint8 CUDA tensor [nTiles, nRows, nCols] (0 = invalid) or None;
+    arena: uint8 CUDA tensor.  One blob per tile, each exactly what encode() makes of that tile with nValuesPerPixel = nDepth and its
+    mask.  -> (status, offsets uint64[nTiles], sizes uint32[nTiles], arena bytes used)"""
+    n_tiles, n_rows, n_cols, n_depth = (int(v) for v in tiles.shape)
+    assert tiles.is_contiguous()
+    if valid is not None:
+        assert tuple(valid.shape) == (n_tiles, n_rows, n_cols) and valid.element_size() == 1 and valid.is_contiguous()
+    return codec.encode_tiles_depth(tiles.data_ptr(), _torch_dt_code(tiles), n_cols, n_rows, n_depth, n_tiles, valid.data_ptr() if valid is not None else 0,
+                                    max_z_err, arena.data_ptr(), arena.numel(), slot_bytes)
+
+
+def decode_tiles_device_depth(codec, arena, offsets, sizes, out, valid_out):
+    """out: CUDA(HIP) tensor [nTiles, nRows, nCols, nDepth]; valid_out: uint8 CUDA tensor [nTiles, nRows, nCols], written 1 / 0 for every
+    tile, or None (a blob with an invalid pixel is then refused).  A tile whose blob fails is left zeroed, mask too."""
+    n_tiles, n_rows, n_cols, n_depth = (int(v) for v in out.shape)
+    assert out.is_contiguous()
+    if valid_out is not None:
+        assert tuple(valid_out.shape) == (n_tiles, n_rows, n_cols) and valid_out.element_size() == 1 and valid_out.is_contiguous()
+    return codec.decode_tiles_depth(arena.data_ptr(), offsets, sizes, n_tiles, n_cols, n_rows, n_depth, _torch_dt_code(out), out.data_ptr(),
+                                    valid_out.data_ptr() if valid_out is not None else 0)
+
+
+def _raster_depth_view(raster, valid):
+    """-> (nRows, nCols, nDepth, pixelPitch, rowPitch, mask address, mask row pitch) of an [H, W, C] tensor or a view of one whose
+    channels are contiguous; which pitches are taken is the library's to say (status 2)"""
+    assert raster.dim() == 3, "raster: [H, W, C]"
+    n_rows, n_cols, n_depth = (int(v) for v in raster.shape)
+    assert n_depth == 1 or raster.stride(2) == 1, "raster: contiguous channels"
+    pixel_pitch = int(raster.stride(1)) if n_cols > 1 else n_depth
+    row_pitch = int(raster.stride(0)) if n_rows > 1 else n_cols * pixel_pitch
+    if valid is None:
+        return n_rows, n_cols, n_depth, pixel_pitch, row_pitch, 0, 0
+    assert valid.element_size() == 1 and tuple(valid.shape) == (n_rows, n_cols) and valid.stride(-1) == 1, "valid: uint8 [H, W] with dense rows"
+    return n_rows, n_cols, n_depth, pixel_pitch, row_pitch, valid.data_ptr(), int(valid.stride(0)) if n_rows > 1 else n_cols
+
+
+def encode_raster_tiles_device_depth(codec, raster, valid, max_z_err, tile, arena, slot_bytes=0):
+    """raster: CUDA(HIP) tensor [H, W, C] or a view of one with contiguous channels and packed pixels (big[:, a:b]); valid: uint8 tensor
+    [H, W] with dense rows or None; tile: (tileRows, tileCols).  The raster is cut into the grid of raster_tile_grid and every tile becomes
+    one blob of nValuesPerPixel = C.  -> (status, offsets uint64[nTiles], sizes uint32[nTiles], arena bytes used)"""
+    n_rows, n_cols, n_depth, pixel_pitch, row_pitch, d_valid, mask_pitch = _raster_depth_view(raster, valid)
+    return codec.encode_raster_tiles_depth(raster.data_ptr(), _torch_dt_code(raster), n_cols, n_rows, n_depth, pixel_pitch, row_pitch, tile, d_valid,
+                                           mask_pitch, max_z_err, arena.data_ptr(), arena.numel(), slot_bytes)
+
+
+def decode_raster_tiles_device_depth(codec, arena, offsets, sizes, out, valid_out, tile):
+    """the way back: out as `raster` above, valid_out as `valid` (written 1 / 0) or None; everything beside a view is left alone"""
+    n_rows, n_cols, n_depth, pixel_pitch, row_pitch, d_valid, mask_pitch = _raster_depth_view(out, valid_out)
+    return codec.decode_raster_tiles_depth(arena.data_ptr(), offsets, sizes, _torch_dt_code(out), n_cols, n_rows, n_depth, pixel_pitch, row_pitch, tile,
+                                           out.data_ptr(), d_valid, mask_pitch)
 
 
 def raster_tile_grid(n_rows, n_cols, tile):

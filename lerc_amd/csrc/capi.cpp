@@ -4,6 +4,7 @@
 // An entry point is: what it zeroes, one argument check of its family, one request builder, the driver's call.
 #include "../../include/lerc_amd.h"
 #include "../../include/lerc_amd_device.h"
+#include "../../include/lerc_amd_depth.h"
 #include "codec.h"
 
 #include <sys/syscall.h>
@@ -134,6 +135,13 @@ lerc_status tileBatchArgs(const lerc_amd_context* h, unsigned dataType, int nCol
   return dimsOk(1, nCols, nRows, (size_t)dtSize((int)dataType)) ? kOk : kDimsTooLarge;
 }
 
+// depth tiles: the tile batch checks plus nDepth >= 1; the size counts nDepth values a pixel
+lerc_status depthTileArgs(const lerc_amd_context* h, unsigned dataType, int nCols, int nRows, int nDepth, int nTiles, bool alsoOk)
+{
+  if (!h || dataType >= DT_Undefined || nCols <= 0 || nRows <= 0 || nDepth <= 0 || nTiles <= 0 || !alsoOk) return kWrongParam;
+  return dimsOk(nDepth, nCols, nRows, (size_t)dtSize((int)dataType)) ? kOk : kDimsTooLarge;
+}
+
 // ---- a pitched raster cut into a grid of tiles (codec_raster_tiles.cpp): pointers, pitches, masks and slots are the driver's to check
 bool rasterTileDimsOk(int nCols, int nRows, int tileCols, int tileRows, unsigned int dataType)
 {
@@ -176,21 +184,21 @@ DecodeRequest decodeRequest(const unsigned char* hBlob, const unsigned char* dBl
 
 TilesEncodeRequest tilesEncodeRequest(const void* dTiles, unsigned dataType, int nCols, int nRows, int nTiles, double maxZErr, unsigned char* dArena,
                                       u64 arenaCapacity, u64* offsets, unsigned* sizes, u64 slotBytes = 0, const unsigned char* dValidBytes = nullptr,
-                                      int nBands = 1, int nMasks = -1)
+                                      int nBands = 1, int nMasks = -1, int nDepth = 1)
 {
   TilesEncodeRequest rq;
   rq.dData = dTiles; rq.dt = (int)dataType; rq.nCols = nCols; rq.nRows = nRows; rq.nTiles = nTiles; rq.maxZErr = maxZErr;
   rq.dArena = dArena; rq.arenaCapacity = arenaCapacity; rq.hOffsets = offsets; rq.hSizes = sizes; rq.slotBytes = slotBytes;
-  rq.dValidBytes = dValidBytes; rq.nBands = nBands; rq.nMasks = nMasks;
+  rq.dValidBytes = dValidBytes; rq.nBands = nBands; rq.nMasks = nMasks; rq.nDepth = nDepth;
   return rq;
 }
 
 TilesDecodeRequest tilesDecodeRequest(const unsigned char* dArena, const u64* offsets, const unsigned* sizes, int nTiles, int nCols, int nRows,
-                                      unsigned dataType, void* dTiles, unsigned char* dValidBytes = nullptr, int nBands = 1, int nMasks = -1)
+                                      unsigned dataType, void* dTiles, unsigned char* dValidBytes = nullptr, int nBands = 1, int nMasks = -1, int nDepth = 1)
 {
   TilesDecodeRequest rq;
   rq.dArena = dArena; rq.hOffsets = offsets; rq.hSizes = sizes; rq.dt = (int)dataType; rq.nCols = nCols; rq.nRows = nRows; rq.nTiles = nTiles;
-  rq.dOut = dTiles; rq.dValidBytes = dValidBytes; rq.nBands = nBands; rq.nMasks = nMasks;
+  rq.dOut = dTiles; rq.dValidBytes = dValidBytes; rq.nBands = nBands; rq.nMasks = nMasks; rq.nDepth = nDepth;
   return rq;
 }
 
@@ -787,6 +795,27 @@ lerc_status lerc_amd_decode_tiles_device_bands(lerc_amd_context* h, const unsign
   return decodeTilesDeviceBands(h->ctx, tilesDecodeRequest(dArena, offsets, sizes, nTiles, nCols, nRows, dataType, dTiles, dValidBytes, nBands, nMasks));
 }
 
+// ---- depth tiles (lerc_amd_depth.h): one blob with the header's nDepth a tile
+lerc_status lerc_amd_encode_tiles_device_depth(lerc_amd_context* h, const void* dTiles, unsigned int dataType, int nCols, int nRows, int nDepth,
+  int nTiles, const unsigned char* dValidBytes, double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity, unsigned long long slotBytes,
+  unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed)
+{
+  if (const lerc_status bad = depthTileArgs(h, dataType, nCols, nRows, nDepth, nTiles,
+                                            dTiles && dArena && offsets && sizes && !(maxZErr < 0) && slotBytesOk(slotBytes, true)))
+    return bad;
+  u64 used = 0;
+  const u32 rc = encodeTilesDeviceDepth(h->ctx, tilesEncodeRequest(dTiles, dataType, nCols, nRows, nTiles, maxZErr, dArena, arenaCapacity, offsets, sizes,
+                                                                   slotBytes, dValidBytes, 1, -1, nDepth), used);
+  return finishTilesEncode(rc, used, slotBytes, nTiles, offsets, arenaUsed);
+}
+
+lerc_status lerc_amd_decode_tiles_device_depth(lerc_amd_context* h, const unsigned char* dArena, const unsigned long long* offsets,
+  const unsigned int* sizes, int nTiles, int nCols, int nRows, int nDepth, unsigned int dataType, void* dTiles, unsigned char* dValidBytes)
+{
+  if (const lerc_status bad = depthTileArgs(h, dataType, nCols, nRows, nDepth, nTiles, dArena && offsets && sizes && dTiles)) return bad;
+  return decodeTilesDeviceDepth(h->ctx, tilesDecodeRequest(dArena, offsets, sizes, nTiles, nCols, nRows, dataType, dTiles, dValidBytes, 1, -1, nDepth));
+}
+
 void lerc_amd_tile_batch_counters(lerc_amd_context* h, unsigned long long out[4])
 {
   readCounters(h, [](Context& c) -> Counters { return c.tileBatchCount; }, out);
@@ -832,6 +861,34 @@ lerc_status lerc_amd_decode_raster_tiles_device_strided(lerc_amd_context* h, con
   if (const lerc_status bad = rasterTilesArgs(h, dataType, nCols, nRows, tileCols, tileRows)) return bad;
   return decodeRasterTilesDevice(h->ctx, rasterTilesRequest(dRaster, dataType, nCols, nRows, nBands, strided(pixelPitch, rowPitch, bandPitch, maskRowPitch),
                                                             tileCols, tileRows, nMasks, dValidBytes, dArena, offsets, sizes));
+}
+
+// ---- the same for packed pixels of nDepth elements, every tile one blob with the header's nDepth (lerc_amd_depth.h).  The driver sees
+// a row as a run of elements (pixelPitch 1); any other pitch description than packed pixels is refused here.
+lerc_status lerc_amd_encode_raster_tiles_device_depth(lerc_amd_context* h, const void* dRaster, unsigned int dataType, int nCols, int nRows, int nDepth,
+  unsigned long long pixelPitch, unsigned long long rowPitch, int tileCols, int tileRows, int nMasks, const unsigned char* dValidBytes,
+  unsigned long long maskRowPitch, double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity, unsigned long long slotBytes,
+  unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed)
+{
+  if (arenaUsed) *arenaUsed = 0;
+  if (const lerc_status bad = rasterTilesArgs(h, dataType, nCols, nRows, tileCols, tileRows, nDepth >= 1 && pixelPitch == (u64)nDepth)) return bad;
+  if (!dimsOk(nDepth, std::min(nCols, tileCols), std::min(nRows, tileRows), (size_t)dtSize((int)dataType))) return kDimsTooLarge;
+  RasterTilesRequest rq = rasterTilesRequest(dRaster, dataType, nCols, nRows, 1, planes(rowPitch, 0, maskRowPitch), tileCols, tileRows, nMasks, dValidBytes,
+                                             dArena, offsets, sizes, maxZErr, arenaCapacity, slotBytes);
+  rq.nDepth = nDepth;
+  return encodeRasterTiles(h, rq, arenaUsed);
+}
+
+lerc_status lerc_amd_decode_raster_tiles_device_depth(lerc_amd_context* h, const unsigned char* dArena, const unsigned long long* offsets,
+  const unsigned int* sizes, unsigned int dataType, int nCols, int nRows, int nDepth, unsigned long long pixelPitch, unsigned long long rowPitch,
+  int tileCols, int tileRows, void* dRaster, int nMasks, unsigned char* dValidBytes, unsigned long long maskRowPitch)
+{
+  if (const lerc_status bad = rasterTilesArgs(h, dataType, nCols, nRows, tileCols, tileRows, nDepth >= 1 && pixelPitch == (u64)nDepth)) return bad;
+  if (!dimsOk(nDepth, std::min(nCols, tileCols), std::min(nRows, tileRows), (size_t)dtSize((int)dataType))) return kDimsTooLarge;
+  RasterTilesRequest rq = rasterTilesRequest(dRaster, dataType, nCols, nRows, 1, planes(rowPitch, 0, maskRowPitch), tileCols, tileRows, nMasks, dValidBytes,
+                                             dArena, offsets, sizes);
+  rq.nDepth = nDepth;
+  return decodeRasterTilesDevice(h->ctx, rq);
 }
 
 // ---- a range of the grid's tiles coded, and a window of the mosaic decoded into a buffer of its own

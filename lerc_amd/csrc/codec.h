@@ -235,6 +235,7 @@ struct TilesEncodeRequest
   // band stacks (encodeTilesDeviceBands): dData [nTiles][nBands][nRows][nCols], dValidBytes [nTiles][nMasks][nRows][nCols]; nMasks < 0: the
   // single-band calls' meaning (a mask per tile where the call takes masks)
   int nBands = 1, nMasks = -1;
+  int nDepth = 1;                     // depth tiles (encodeTilesDeviceDepth): dData [nTiles][nRows][nCols][nDepth], one blob with nDepth a tile
 };
 struct TilesDecodeRequest
 {
@@ -245,6 +246,7 @@ struct TilesDecodeRequest
   void* dOut = nullptr;               // device: [nTiles][nRows][nCols]
   u8* dValidBytes = nullptr;          // device [nTiles][nRows][nCols], written 1 / 0 for every tile (decodeTilesDeviceMasked); nullptr: blobs with a mask are refused
   int nBands = 1, nMasks = -1;        // band stacks (decodeTilesDeviceBands), as in TilesEncodeRequest
+  int nDepth = 1;                     // depth tiles (decodeTilesDeviceDepth): dOut [nTiles][nRows][nCols][nDepth]
 };
 
 struct DecodeRequest
@@ -312,6 +314,9 @@ u32 decodeTilesDeviceMasked(Context& ctx, const TilesDecodeRequest& rq);
 // tiles that are band stacks, one blob a tile (codec_tiles_batch.cpp); with one band they ARE the calls above
 u32 encodeTilesDeviceBands(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed);
 u32 decodeTilesDeviceBands(Context& ctx, const TilesDecodeRequest& rq);
+// depth tiles: [nTiles][nRows][nCols][nDepth], a mask [nRows][nCols] per tile or none, one blob with the header's nDepth a tile
+u32 encodeTilesDeviceDepth(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed);
+u32 decodeTilesDeviceDepth(Context& ctx, const TilesDecodeRequest& rq);
 
 // 8-bit tiles, every pixel valid, lossless (codec_tiles_batch.cpp, tile_byte_batch.hip): encodeTilesDevice / decodeTilesDevice hand such requests on
 bool tilesBytesEncodeEligible(const TilesEncodeRequest& rq);
@@ -338,6 +343,9 @@ struct RasterTilesRequest
   // the tiles of the grid the call is about, [tileRow0, tileRow0 + nTileRows) x [tileCol0, tileCol0 + nTileCols); a negative count: all
   // from the first on (the default: the whole grid).  hOffsets / hSizes stay full-grid tables, only the range's entries are touched
   int tileCol0 = 0, tileRow0 = 0, nTileCols = -1, nTileRows = -1;
+  // depth tiles (the _depth entry points): > 1: one band of packed pixels, nDepth elements each (rowPitch >= nCols * nDepth, pixelPitch
+  // 1: a row is a run of elements); every tile is one blob with the header's nDepth
+  int nDepth = 1;
 };
 u32 encodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq, u64& arenaUsed);
 u32 decodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq);

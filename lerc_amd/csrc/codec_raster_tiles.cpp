@@ -70,6 +70,10 @@ bool rtArgsOk(const RasterTilesRequest& rq, bool encode, const RasterWindow* win
     || rq.tileCols <= 0 || rq.tileRows <= 0 || (rq.nMasks != 0 && rq.nMasks != 1) || (rq.nMasks == 0) != (rq.dValidBytes == nullptr))
     return false;
   if (rq.nMasks && rq.maskRowPitch < bufCols) return false;
+  // (depth tiles: pixels packed, nDepth elements each -- a row is a run of nCols * nDepth elements, which is what the checks below see of it)
+  if (rq.nDepth < 1 || (rq.nDepth > 1 && (win || rq.nBands != 1 || rq.pixelPitch != 1 || rq.rowPitch / (u64)rq.nDepth < bufCols
+    || (u64)std::min(rq.tileCols, rq.nCols) * (u64)rq.nDepth > 0x7FFFFFFFull)))
+    return false;
   if (!rtLayoutOk(rq, bufCols, bufRows)) return false;
   if (((uintptr_t)rq.dRaster & (uintptr_t)(dtSize(rq.dt) - 1)) != 0) return false;    // (elements lie on their own boundaries)
   if (encode && (rq.maxZErr < 0 || (rq.slotBytes & 15u) != 0)) return false;
@@ -97,7 +101,7 @@ RtGrid rtGrid(const RasterTilesRequest& rq)
   if (fullY && remC) add(0, fullX, fullY, 1, tr, remC);
   if (remR && fullX) add(fullY, 0, 1, fullX, remR, tc);
   if (remR && remC) add(fullY, fullX, 1, 1, remR, remC);
-  g.inPlace = rq.pixelPitch == 1 && rq.nBands == 1 && tc >= nC && rq.rowPitch == (u64)nC && (!rq.nMasks || rq.maskRowPitch == (u64)nC);
+  g.inPlace = rq.pixelPitch == 1 && rq.nBands == 1 && rq.nDepth == 1 && tc >= nC && rq.rowPitch == (u64)nC && (!rq.nMasks || rq.maskRowPitch == (u64)nC);
   return g;
 }
 
@@ -108,7 +112,7 @@ RtStagePlan rtPlan(const RasterTilesRequest& rq, const RtClass& k)
 {
   RtStagePlan p;
   const size_t pix = (size_t)k.r * k.c;
-  p.dataPerTile = pix * (size_t)rq.nBands * (size_t)dtSize(rq.dt);
+  p.dataPerTile = pix * (size_t)rq.nBands * (size_t)rq.nDepth * (size_t)dtSize(rq.dt);
   p.maskPerTile = rq.nMasks ? pix : 0;
   size_t most = std::max<size_t>(1, kRtStageBytes / (p.dataPerTile + p.maskPerTile));
   const char* e = getenv("LERC_AMD_TEST_RASTER_CHUNK");
@@ -138,6 +142,10 @@ RtChunk rtChunk(const RasterTilesRequest& rq, const RtClass& k, u32 k0, u32 n, b
   ch.rowPitch = mask ? rq.maskRowPitch : rq.rowPitch; ch.bandPitch = mask ? 0 : rq.bandPitch;
   ch.tileRows = (u32)rq.tileRows; ch.tileCols = (u32)rq.tileCols; ch.r = k.r; ch.c = k.c;
   ch.ty0 = k.ty0; ch.tx0 = k.tx0; ch.classW = k.nTX; ch.k0 = k0; ch.n = n; ch.nBands = mask ? 1u : (u32)rq.nBands;
+  // (depth tiles: a tile's rows are runs of c * nDepth elements, a tile column is tileCols * nDepth elements wide; the mask stays at pixel width)
+  // (a tile wider than the raster is clipped to it first -- its column index is 0 then, so nothing changes --: rtArgsOk has bounded
+  // min(tileCols, nCols) * nDepth, and that is the product taken here)
+  if (!mask && rq.nDepth > 1) { ch.tileCols = (u32)std::min(rq.tileCols, rq.nCols) * (u32)rq.nDepth; ch.c *= (u32)rq.nDepth; }
   return ch;
 }
 
@@ -215,7 +223,8 @@ u32 encodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq, u64& are
       sub.dArena = rq.dArena + base;
       u64 used = 0;
       u32 rc;
-      if (rq.nBands == 1) rc = rq.nMasks ? encodeTilesDeviceMasked(ctx, sub, used) : encodeTilesDevice(ctx, sub, used);
+      if (rq.nDepth > 1) { sub.nDepth = rq.nDepth; rc = encodeTilesDeviceDepth(ctx, sub, used); }
+      else if (rq.nBands == 1) rc = rq.nMasks ? encodeTilesDeviceMasked(ctx, sub, used) : encodeTilesDevice(ctx, sub, used);
       else { sub.nBands = rq.nBands; sub.nMasks = rq.nMasks; rc = encodeTilesDeviceBands(ctx, sub, used); }
       if (rc != kOk) return rc;
       for (u32 i = 0; i < n; i++)
@@ -274,7 +283,8 @@ static u32 rtDecode(Context& ctx, const RasterTilesRequest& rq, const RasterWind
         ctx.rasterTilesCount[2] += n;
       }
       u32 rc;
-      if (rq.nBands > 1) { sub.nBands = rq.nBands; sub.nMasks = rq.nMasks; rc = decodeTilesDeviceBands(ctx, sub); }
+      if (rq.nDepth > 1) { sub.nDepth = rq.nDepth; rc = decodeTilesDeviceDepth(ctx, sub); }
+      else if (rq.nBands > 1) { sub.nBands = rq.nBands; sub.nMasks = rq.nMasks; rc = decodeTilesDeviceBands(ctx, sub); }
       else if (rq.nMasks) rc = decodeTilesDeviceMasked(ctx, sub);
       else
       {

@@ -9,6 +9,7 @@
 #include "codec.h"
 #include "tile_mask_batch.h"
 #include "tile_byte_batch.h"
+#include "tile_depth_batch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -31,7 +32,7 @@ static G tileGeom(int dt, int nRows, int nCols)
 }
 
 // how many bands and masks a tile has: every family is constructed with it, the single-band ones leave it unread
-struct TbStack { int nBands, nMasks; };
+struct TbStack { int nBands, nMasks; int nDepth = 1; };
 
 // ================================================================================================
 // the masked family
@@ -41,20 +42,16 @@ static bool tmbShapeOk(int dt, int nRows, int nCols)
   return dt >= DT_Short && dt <= DT_Double && tbShapeFits(nRows, nCols);
 }
 
-struct MaskedBatch
+// What the families that keep a tile's mask the masked family's way share (MaskedBatch, DepthBatch): the geometry with the mask's
+// strides, the workspace per tile and its carving for a record type of their own (Rec: TmbTile, TdbTile; the buffer structs have the
+// same members), the band parameters, the words for a reason.
+struct MaskedGeometry
 {
   static constexpr bool kMasked = true;    // a tile done by itself carries its mask
-  static constexpr const char* kName = "masked";
-  static constexpr const char* kLaunchError = "lerc_amd: a masked tile batch kernel could not be launched";
-  static constexpr const char* kEncodeScope = "tiles_masked_encode";
-  static constexpr const char* kDecodeScope = "tiles_masked_decode";
-  static constexpr size_t kRecBytes = sizeof(TmbTile);
 
   TmbGeom g;
-  TmbEncodeBuffers eb;
-  TmbDecodeBuffers db;
 
-  MaskedBatch(int dt, int nRows, int nCols, TbStack = { 1, 1 }) : g(tileGeom<TmbGeom>(dt, nRows, nCols))
+  MaskedGeometry(int dt, int nRows, int nCols) : g(tileGeom<TmbGeom>(dt, nRows, nCols))
   {
     const u32 nBytes = (u32)((g.tileElems + 7) >> 3);
     g.bitStride = (nBytes + 16u + 15u) & ~15u;
@@ -62,23 +59,22 @@ struct MaskedBatch
     g.pos16Stride = ((u32)(((nRows + 15) / 16) * ((nCols + 15) / 16)) + 1u + 3u) & ~3u;
   }
 
-  size_t encodeBytesPerTile() const { return sizeof(TmbTile) + g.bitStride + g.rleStride + ((size_t)g.posStride + g.pos16Stride) * 4; }
-  size_t encodeBytesPerBatch() const { return 0; }    // (workspace a sub-batch needs once, whatever its tile count)
-  size_t decodeBytesPerTile() const { return sizeof(TmbTile) + g.bitStride + (size_t)g.posStride * 4 + 16; }
+  template<class Rec> size_t encodeBytesOf() const { return sizeof(Rec) + g.bitStride + g.rleStride + ((size_t)g.posStride + g.pos16Stride) * 4; }
+  template<class Rec> size_t decodeBytesOf() const { return sizeof(Rec) + g.bitStride + (size_t)g.posStride * 4 + 16; }
 
   // the workspace of n tiles -> their records, nullptr: no room
-  void* carveEncode(Context& ctx, size_t n)
+  template<class Rec, class EB> void* carveEncodeInto(Context& ctx, size_t n, EB& eb) const
   {
-    eb.tiles = ctx.allocT<TmbTile>(n);
+    eb.tiles = ctx.allocT<Rec>(n);
     eb.bits = ctx.allocT<u8>(n * g.bitStride);
     eb.rle = ctx.allocT<u8>(n * g.rleStride);
     eb.blockOff = ctx.allocT<u32>(n * g.posStride);
     eb.blockOff16 = ctx.allocT<u32>(n * g.pos16Stride);
     return (eb.bits && eb.rle && eb.blockOff && eb.blockOff16) ? eb.tiles : nullptr;
   }
-  void* carveDecode(Context& ctx, size_t n)
+  template<class Rec, class DB> void* carveDecodeInto(Context& ctx, size_t n, DB& db) const
   {
-    db.tiles = ctx.allocT<TmbTile>(n);
+    db.tiles = ctx.allocT<Rec>(n);
     db.bits = ctx.allocT<u8>(n * g.bitStride);
     db.blockOff = ctx.allocT<u32>(n * g.posStride);
     return (db.bits && db.blockOff) ? db.tiles : nullptr;
@@ -101,19 +97,6 @@ struct MaskedBatch
     bp.intLossless = (!isFlt && bp.maxZErr == 0.5) ? 1 : 0;
     return bp;
   }
-  void launchEncode(u32 n, double maxZErr, const void* dTiles, const u8* dValid, u8* dArena, u64 arenaBase, u64 arenaCapacity, u64 slotBytes, u64 firstTile,
-                    hipStream_t st)
-  {
-    g.nTiles = n;
-    u32 cand = 0;    // TryRaiseMaxZError candidates whose error bound beats maxZErr
-    const BandParams bp = encodeParams(maxZErr, cand);
-    launchTmbEncode(g, bp, bp.maxZErr, cand, dTiles, dValid, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, eb, st);
-  }
-  void launchDecode(u32 n, const u8* dArena, const u64* dOff, const u32* dSize, void* dTiles, u8* dValid, hipStream_t st)
-  {
-    g.nTiles = n;
-    launchTmbDecode(g, dArena, dOff, dSize, dTiles, dValid, db, st);
-  }
 
   static const char* reason(u32 flags)
   {
@@ -126,6 +109,40 @@ struct MaskedBatch
     if (flags & kTmbMaskStream) return "the mask's run-length stream is damaged";
     if (flags & (kTbBlocks | kTbSibling)) return "the block stream";
     return "unknown";
+  }
+};
+
+struct MaskedBatch : MaskedGeometry
+{
+  static constexpr const char* kName = "masked";
+  static constexpr const char* kLaunchError = "lerc_amd: a masked tile batch kernel could not be launched";
+  static constexpr const char* kEncodeScope = "tiles_masked_encode";
+  static constexpr const char* kDecodeScope = "tiles_masked_decode";
+  static constexpr size_t kRecBytes = sizeof(TmbTile);
+
+  TmbEncodeBuffers eb;
+  TmbDecodeBuffers db;
+
+  MaskedBatch(int dt, int nRows, int nCols, TbStack = { 1, 1 }) : MaskedGeometry(dt, nRows, nCols) {}
+
+  size_t encodeBytesPerTile() const { return encodeBytesOf<TmbTile>(); }
+  size_t encodeBytesPerBatch() const { return 0; }    // (workspace a sub-batch needs once, whatever its tile count)
+  size_t decodeBytesPerTile() const { return decodeBytesOf<TmbTile>(); }
+  void* carveEncode(Context& ctx, size_t n) { return carveEncodeInto<TmbTile>(ctx, n, eb); }
+  void* carveDecode(Context& ctx, size_t n) { return carveDecodeInto<TmbTile>(ctx, n, db); }
+
+  void launchEncode(u32 n, double maxZErr, const void* dTiles, const u8* dValid, u8* dArena, u64 arenaBase, u64 arenaCapacity, u64 slotBytes, u64 firstTile,
+                    hipStream_t st)
+  {
+    g.nTiles = n;
+    u32 cand = 0;    // TryRaiseMaxZError candidates whose error bound beats maxZErr
+    const BandParams bp = encodeParams(maxZErr, cand);
+    launchTmbEncode(g, bp, bp.maxZErr, cand, dTiles, dValid, dArena, arenaBase, arenaCapacity, slotBytes, firstTile, eb, st);
+  }
+  void launchDecode(u32 n, const u8* dArena, const u64* dOff, const u32* dSize, void* dTiles, u8* dValid, hipStream_t st)
+  {
+    g.nTiles = n;
+    launchTmbDecode(g, dArena, dOff, dSize, dTiles, dValid, db, st);
   }
 };
 
@@ -182,6 +199,53 @@ struct MaskedBandsBatch : MaskedBatch
   {
     if (flags == kTbBand) return "another band of the tile";
     return MaskedBatch::reason(flags & ~kTbBand);
+  }
+};
+
+// ================================================================================================
+// the depth family: tiles [nRows][nCols][nDepth] under one mask, one blob with the header's nDepth a tile (tile_depth_batch.hip).  The
+// geometry, the mask's workspace and the error bounds are the masked family's; the records carry the slices' ranges.
+// ================================================================================================
+struct DepthBatch : MaskedGeometry
+{
+  static constexpr const char* kName = "depth";
+  static constexpr const char* kLaunchError = "lerc_amd: a depth tile batch kernel could not be launched";
+  static constexpr const char* kEncodeScope = "tiles_depth_encode";
+  static constexpr const char* kDecodeScope = "tiles_depth_decode";
+  static constexpr size_t kRecBytes = sizeof(TdbTile);
+
+  int nDepth, nMasks;
+  TdbEncodeBuffers deb = {};    // (the depth family's records, TdbTile: the slices' ranges ride in them)
+  TdbDecodeBuffers ddb = {};
+  u8* ones = nullptr;         // encode without masks: tileElems bytes of 1
+
+  DepthBatch(int dt, int nRows, int nCols, TbStack s) : MaskedGeometry(dt, nRows, nCols), nDepth(s.nDepth), nMasks(s.nMasks) {}
+
+  size_t encodeBytesPerTile() const { return encodeBytesOf<TdbTile>(); }
+  size_t encodeBytesPerBatch() const { return nMasks ? 0 : (size_t)g.tileElems + 64; }    // (the all-ones mask, one for the sub-batch, as the band stacks have it)
+  size_t decodeBytesPerTile() const { return decodeBytesOf<TdbTile>(); }
+
+  void* carveEncode(Context& ctx, size_t n)
+  {
+    void* rec = carveEncodeInto<TdbTile>(ctx, n, deb);
+    if (!nMasks) { ones = ctx.allocT<u8>((size_t)g.tileElems); if (!ones) return nullptr; }
+    return rec;
+  }
+  void* carveDecode(Context& ctx, size_t n) { return carveDecodeInto<TdbTile>(ctx, n, ddb); }
+  void launchEncode(u32 n, double maxZErr, const void* dTiles, const u8* dValid, u8* dArena, u64 arenaBase, u64 arenaCapacity, u64 slotBytes, u64 firstTile,
+                    hipStream_t st)
+  {
+    g.nTiles = n;
+    u32 cand = 0;
+    const BandParams bp = encodeParams(maxZErr, cand);
+    if (!nMasks) hipMemsetAsync(ones, 1, (size_t)g.tileElems, st);
+    launchTdbEncode(g, nDepth, bp, bp.maxZErr, cand, dTiles, nMasks ? dValid : ones, nMasks ? g.tileElems : 0, dArena, arenaBase, arenaCapacity, slotBytes,
+                    firstTile, deb, st);
+  }
+  void launchDecode(u32 n, const u8* dArena, const u64* dOff, const u32* dSize, void* dTiles, u8* dValid, hipStream_t st)
+  {
+    g.nTiles = n;
+    launchTdbDecode(g, nDepth, dArena, dOff, dSize, dTiles, nMasks ? dValid : nullptr, ddb, st);
   }
 };
 
@@ -463,7 +527,7 @@ static u32 tbEncode(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed, 
   const bool slotted = rq.slotBytes != 0;
   const int tb = dtSize(rq.dt);
   const int nB = rq.nBands, nM = rq.nMasks >= 0 ? rq.nMasks : (F::kMasked ? 1 : 0);
-  const u64 tileElems = (u64)rq.nRows * (u64)rq.nCols, tileBytes = tileElems * (u64)tb * (u64)nB, maskBytes = tileElems * (u64)nM;
+  const u64 tileElems = (u64)rq.nRows * (u64)rq.nCols, tileBytes = tileElems * (u64)tb * (u64)nB * (u64)rq.nDepth, maskBytes = tileElems * (u64)nM;
   u64 end = 0;    // arena bytes in use
 
   auto encodeOne = [&](int t) -> u32
@@ -471,7 +535,7 @@ static u32 tbEncode(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed, 
     end = slotted ? (u64)t * rq.slotBytes : (end + 15) & ~15ull;
     EncodeRequest one;
     one.dData = (const u8*)rq.dData + (size_t)t * tileBytes;
-    one.dt = rq.dt; one.nDepth = 1; one.nCols = rq.nCols; one.nRows = rq.nRows; one.nBands = nB; one.nMasks = nM;
+    one.dt = rq.dt; one.nDepth = rq.nDepth; one.nCols = rq.nCols; one.nRows = rq.nRows; one.nBands = nB; one.nMasks = nM;
     one.dValidBytes = nM ? rq.dValidBytes + (size_t)t * maskBytes : nullptr;
     one.maxZErr = rq.maxZErr;
     one.dOut = rq.dArena + end;
@@ -500,7 +564,7 @@ static u32 tbEncode(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed, 
   }
 
   hipStream_t st = ctx.activeStream();
-  F f(rq.dt, rq.nRows, rq.nCols, TbStack{ nB, nM });
+  F f(rq.dt, rq.nRows, rq.nCols, TbStack{ nB, nM, rq.nDepth });
   const size_t perTile = f.encodeBytesPerTile(), perBatch = f.encodeBytesPerBatch();
   if (!tbTileFits(perTile, perBatch, nB)) return oneByOne();
   const int maxBatch = tbMaxBatch(rq.nTiles, perTile, perBatch, nB);
@@ -559,14 +623,14 @@ static u32 tbDecode(Context& ctx, const TilesDecodeRequest& rq, bool batchOk)
 {
   const int tb = dtSize(rq.dt);
   const int nB = rq.nBands, nM = rq.nMasks >= 0 ? rq.nMasks : (F::kMasked ? 1 : 0);
-  const u64 tileElems = (u64)rq.nRows * (u64)rq.nCols, tileBytes = tileElems * (u64)tb * (u64)nB, maskBytes = tileElems * (u64)nM;
+  const u64 tileElems = (u64)rq.nRows * (u64)rq.nCols, tileBytes = tileElems * (u64)tb * (u64)nB * (u64)rq.nDepth, maskBytes = tileElems * (u64)nM;
   hipStream_t st = ctx.activeStream();
   u32 firstError = kOk;
   // a tile by itself; one that fails is left zeroed, mask too, and the call goes on with the tiles behind it
   auto decodeOne = [&](int t)
   {
     DecodeRequest one;
-    one.dBlob = rq.dArena + rq.hOffsets[t]; one.blobSize = rq.hSizes[t]; one.dt = rq.dt; one.nDepth = 1; one.nCols = rq.nCols;
+    one.dBlob = rq.dArena + rq.hOffsets[t]; one.blobSize = rq.hSizes[t]; one.dt = rq.dt; one.nDepth = rq.nDepth; one.nCols = rq.nCols;
     one.nRows = rq.nRows; one.nBands = nB; one.nMasks = nM;
     one.dValidBytes = nM ? rq.dValidBytes + (size_t)t * maskBytes : nullptr;
     one.dOut = (u8*)rq.dOut + (size_t)t * tileBytes;
@@ -593,7 +657,7 @@ static u32 tbDecode(Context& ctx, const TilesDecodeRequest& rq, bool batchOk)
     return rc;
   }
 
-  F f(rq.dt, rq.nRows, rq.nCols, TbStack{ nB, nM });
+  F f(rq.dt, rq.nRows, rq.nCols, TbStack{ nB, nM, rq.nDepth });
   const size_t perTile = f.decodeBytesPerTile();
   if (!tbTileFits(perTile, 0, nB)) return oneByOne();
   const int maxBatch = tbMaxBatch(rq.nTiles, perTile, 0, nB);
@@ -702,6 +766,65 @@ u32 decodeTilesDeviceBands(Context& ctx, const TilesDecodeRequest& rq)
   }
   if (rq.nMasks <= 1 && tbbShapeOk(rq.dt, rq.nRows, rq.nCols)) return tbDecode<BytesBandsBatch>(ctx, rq, true);
   return tbDecode<MaskedBandsBatch>(ctx, rq, rq.nMasks <= 1 && tmbShapeOk(rq.dt, rq.nRows, rq.nCols));
+}
+
+// ---- depth tiles.  One value a pixel: the masked calls.  The batch's own launches take the wide types with 2 .. kTdbMaxDepth values a
+// pixel and no mask or one mask a tile; 8-bit tiles (their Huffman modes over depth), deeper tiles, and the error bounds and sizes the
+// masked family leaves alone go one by one, a tile per encodeDevice / decodeDevice call with its nDepth.
+static const char* tdbWhyNot(int dt, int nDepth, int nRows, int nCols, double maxZErr, bool encode)
+{
+  if (dt == DT_Char || dt == DT_Byte) return "8-bit values";
+  if (nDepth > kTdbMaxDepth) return "more values a pixel than the depth batches take";
+  if (!tbShapeFits(nRows, nCols)) return "the size";
+  if (encode && maxZErr == 777) return "the bit plane mode's error bound";
+  if (encode && dt >= DT_Float && maxZErr == 0) return "an error bound of 0 on float values";
+  return nullptr;
+}
+
+static void tdbNoteAll(Context& ctx, const char* what, const char* why)
+{
+  char msg[224];
+  snprintf(msg, sizeof(msg), "every tile of the depth batch is %s by itself, from tile 0 on: %s", what, why);
+  ctx.lastNote = msg;
+}
+
+u32 encodeTilesDeviceDepth(Context& ctx, const TilesEncodeRequest& rq, u64& arenaUsed)
+{
+  arenaUsed = 0;
+  if (!rq.dData || !rq.dArena || !rq.hOffsets || !rq.hSizes || rq.nTiles <= 0 || rq.nRows <= 0 || rq.nCols <= 0 || rq.dt < 0 || rq.dt > DT_Double
+    || rq.maxZErr < 0 || (rq.slotBytes & 15u) != 0 || rq.nDepth <= 0)
+    return kWrongParam;
+  TilesEncodeRequest one = rq;
+  one.nBands = 1;
+  if (rq.nDepth == 1)
+  {
+    one.nMasks = -1;
+    return encodeTilesDeviceMasked(ctx, one, arenaUsed);
+  }
+  one.nMasks = rq.dValidBytes ? 1 : 0;
+  const char* why = tdbWhyNot(rq.dt, rq.nDepth, rq.nRows, rq.nCols, rq.maxZErr, true);
+  const u32 rc = tbEncode<DepthBatch>(ctx, one, arenaUsed, why == nullptr);
+  if (why && rc == kOk) tdbNoteAll(ctx, "encoded", why);
+  return rc;
+}
+
+u32 decodeTilesDeviceDepth(Context& ctx, const TilesDecodeRequest& rq)
+{
+  if (!rq.dArena || !rq.hOffsets || !rq.hSizes || !rq.dOut || rq.nTiles <= 0 || rq.nRows <= 0 || rq.nCols <= 0 || rq.dt < 0 || rq.dt > DT_Double
+    || rq.nDepth <= 0)
+    return kWrongParam;
+  TilesDecodeRequest one = rq;
+  one.nBands = 1;
+  if (rq.nDepth == 1)
+  {
+    one.nMasks = -1;
+    return decodeTilesDeviceMasked(ctx, one);
+  }
+  one.nMasks = rq.dValidBytes ? 1 : 0;
+  const char* why = tdbWhyNot(rq.dt, rq.nDepth, rq.nRows, rq.nCols, 0, false);
+  const u32 rc = tbDecode<DepthBatch>(ctx, one, why == nullptr);
+  if (why && rc == kOk) tdbNoteAll(ctx, "decoded", why);
+  return rc;
 }
 
 // (encodeTilesDevice / decodeTilesDevice have checked the arguments and the eligibility)
