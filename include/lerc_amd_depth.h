@@ -42,7 +42,7 @@ LERC_AMD_API lerc_status lerc_amd_decode_tiles_device_depth(lerc_amd_context* ct
  *   dValidBytes  device byte mask [nRows][maskRowPitch] (nMasks 1) or NULL (nMasks 0)
  * Offsets, sizes, slots, shape classes, chunks through the staging buffer and lerc_amd_raster_tiles_counters are those of
  * lerc_amd_encode_raster_tiles_device.  Every other pitch description -- pixelPitch > nDepth (RGB out of RGBA) included -- is
- * WrongParam. */
+ * WrongParam for these two calls; the _strided calls below take them. */
 LERC_AMD_API lerc_status lerc_amd_encode_raster_tiles_device_depth(lerc_amd_context* ctx, const void* dRaster, unsigned int dataType, int nCols,
     int nRows, int nDepth, unsigned long long pixelPitch, unsigned long long rowPitch, int tileCols, int tileRows, int nMasks,
     const unsigned char* dValidBytes, unsigned long long maskRowPitch, double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity,
@@ -51,6 +51,49 @@ LERC_AMD_API lerc_status lerc_amd_encode_raster_tiles_device_depth(lerc_amd_cont
 LERC_AMD_API lerc_status lerc_amd_decode_raster_tiles_device_depth(lerc_amd_context* ctx, const unsigned char* dArena, const unsigned long long* offsets,
     const unsigned int* sizes, unsigned int dataType, int nCols, int nRows, int nDepth, unsigned long long pixelPitch, unsigned long long rowPitch,
     int tileCols, int tileRows, void* dRaster, int nMasks, unsigned char* dValidBytes, unsigned long long maskRowPitch);
+
+/* The same for a depth raster in ANY of four layouts, described by three pitches in elements: element (row, col, d) lies at
+ * row * rowPitch + col * pixelPitch + d * depthPitch.
+ *   packed pixels   depthPitch == 1, pixelPitch == nDepth, rowPitch >= nCols * nDepth                  the two calls above
+ *   gapped pixels   depthPitch == 1, pixelPitch > nDepth,  rowPitch >= (nCols - 1) * pixelPitch + nDepth
+ *                   RGB out of RGBA, two channels of an interleaved frame; a gap's elements are neither read nor written
+ *   planes          pixelPitch == 1, rowPitch >= nCols, depthPitch >= (nRows - 1) * rowPitch + nCols
+ *                   [C, H, W], also a view chw[:, a:b, c:d]
+ *   lines           pixelPitch == 1, depthPitch >= nCols, rowPitch >= (nDepth - 1) * depthPitch + nCols   GDAL's INTERLEAVE=LINE
+ * Every other description -- both of pixelPitch and depthPitch above 1, rows, lines or planes that overlap -- is WrongParam.  The
+ * blobs are those of the packed call on a packed copy of the raster, byte for byte; nothing is copied to get them: the staging pass
+ * reads (writes) the raster where it lies.  nDepth == 1 ignores depthPitch and is lerc_amd_encode_raster_tiles_device_strided /
+ * lerc_amd_decode_raster_tiles_device_strided with one band.  Masks, slots, counters, statuses and size limits: the packed calls'. */
+LERC_AMD_API lerc_status lerc_amd_encode_raster_tiles_device_depth_strided(lerc_amd_context* ctx, const void* dRaster, unsigned int dataType,
+    int nCols, int nRows, int nDepth, unsigned long long pixelPitch, unsigned long long rowPitch, unsigned long long depthPitch, int tileCols,
+    int tileRows, int nMasks, const unsigned char* dValidBytes, unsigned long long maskRowPitch, double maxZErr, unsigned char* dArena,
+    unsigned long long arenaCapacity, unsigned long long slotBytes, unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed);
+
+LERC_AMD_API lerc_status lerc_amd_decode_raster_tiles_device_depth_strided(lerc_amd_context* ctx, const unsigned char* dArena,
+    const unsigned long long* offsets, const unsigned int* sizes, unsigned int dataType, int nCols, int nRows, int nDepth,
+    unsigned long long pixelPitch, unsigned long long rowPitch, unsigned long long depthPitch, int tileCols, int tileRows, void* dRaster, int nMasks,
+    unsigned char* dValidBytes, unsigned long long maskRowPitch);
+
+/* The strided encode for a rectangle of the grid's tiles, [tileRow0, tileRow0 + nTileRows) x [tileCol0, tileCol0 + nTileCols), as
+ * lerc_amd_encode_raster_tiles_device_range: dRaster and the mask are the WHOLE raster, offsets and sizes the full grid's tables of
+ * which only the range's entries are written, every blob is what the whole-raster call makes of that tile, and with slotBytes != 0 the
+ * range takes the first nTileRows * nTileCols rooms of the arena.  WrongParam: a range that is empty or not inside the grid. */
+LERC_AMD_API lerc_status lerc_amd_encode_raster_tiles_device_depth_range(lerc_amd_context* ctx, const void* dRaster, unsigned int dataType,
+    int nCols, int nRows, int nDepth, unsigned long long pixelPitch, unsigned long long rowPitch, unsigned long long depthPitch, int tileCols,
+    int tileRows, int tileCol0, int tileRow0, int nTileCols, int nTileRows, int nMasks, const unsigned char* dValidBytes,
+    unsigned long long maskRowPitch, double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity, unsigned long long slotBytes,
+    unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed);
+
+/* A window of a depth mosaic, as lerc_amd_decode_raster_window_device: nCols, nRows, nDepth, the tile size and the full-grid tables
+ * describe the mosaic; rows [winRow0, winRow0 + winRows) by columns [winCol0, winCol0 + winCols) of it go into the buffer at dWindow,
+ * which holds the window ONLY and is described by the three pitches (any of the four layouts, the rules applied to the window's size),
+ * with a mask plane [winRows][maskRowPitch] or none.  Only the tiles the window touches are read and decoded; nothing beside the
+ * window's elements is written.  A tile whose blob fails leaves its part of the window zeroed, and the first failing tile's status
+ * is returned.  WrongParam: a window that is empty or not inside the raster. */
+LERC_AMD_API lerc_status lerc_amd_decode_raster_window_device_depth(lerc_amd_context* ctx, const unsigned char* dArena,
+    const unsigned long long* offsets, const unsigned int* sizes, unsigned int dataType, int nCols, int nRows, int nDepth, int tileCols,
+    int tileRows, int winCol0, int winRow0, int winCols, int winRows, void* dWindow, unsigned long long pixelPitch, unsigned long long rowPitch,
+    unsigned long long depthPitch, int nMasks, unsigned char* dValidBytes, unsigned long long maskRowPitch);
 
 #ifdef __cplusplus
 }

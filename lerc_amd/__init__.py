@@ -12,8 +12,12 @@ from .api import (  # noqa: F401
     computeCompressedSize,
     decode,
     decode_device,
+    decode_raster_tiles_device_depth_strided,
+    decode_raster_window_device_depth,
     encode,
     encode_device,
+    encode_raster_tile_range_device_depth,
+    encode_raster_tiles_device_depth_strided,
     getLercBlobInfo,
     getLercDataRanges,
     library_path,
@@ -21,4 +25,5 @@ from .api import (  # noqa: F401
 )
 
 __all__ = ["encode", "decode", "computeCompressedSize", "getLercBlobInfo", "getLercDataRanges", "encode_device",
-           "decode_device", "load_library", "library_path", "build_info", "LercError"]
+           "decode_device", "load_library", "library_path", "build_info", "LercError", "encode_raster_tiles_device_depth_strided",
+           "decode_raster_tiles_device_depth_strided", "encode_raster_tile_range_device_depth", "decode_raster_window_device_depth"]

@@ -125,6 +125,25 @@ def load_library():
         lib.lerc_amd_decode_raster_tiles_device_depth.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int, ct.c_int,
                                                                   ct.c_int, ct.c_ulonglong, ct.c_ulonglong, ct.c_int, ct.c_int, ct.c_void_p, ct.c_int,
                                                                   ct.c_void_p, ct.c_ulonglong]
+    # (the depth raster calls that take a layout, a tile range or a window: the same rule)
+    have_depth_layouts = not os.environ.get("LERC_AMD_LIBRARY") or hasattr(lib, "lerc_amd_encode_raster_tiles_device_depth_strided")
+    if have_depth_layouts:
+        lib.lerc_amd_encode_raster_tiles_device_depth_strided.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int, ct.c_int, ct.c_int,
+                                                                          ct.c_ulonglong, ct.c_ulonglong, ct.c_ulonglong, ct.c_int, ct.c_int, ct.c_int,
+                                                                          ct.c_void_p, ct.c_ulonglong, ct.c_double, ct.c_void_p, ct.c_ulonglong,
+                                                                          ct.c_ulonglong, ct.c_void_p, ct.c_void_p, ct.c_void_p]
+        lib.lerc_amd_decode_raster_tiles_device_depth_strided.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int,
+                                                                          ct.c_int, ct.c_int, ct.c_ulonglong, ct.c_ulonglong, ct.c_ulonglong, ct.c_int,
+                                                                          ct.c_int, ct.c_void_p, ct.c_int, ct.c_void_p, ct.c_ulonglong]
+        lib.lerc_amd_encode_raster_tiles_device_depth_range.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int, ct.c_int, ct.c_int,
+                                                                        ct.c_ulonglong, ct.c_ulonglong, ct.c_ulonglong, ct.c_int, ct.c_int, ct.c_int,
+                                                                        ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_void_p, ct.c_ulonglong, ct.c_double,
+                                                                        ct.c_void_p, ct.c_ulonglong, ct.c_ulonglong, ct.c_void_p, ct.c_void_p,
+                                                                        ct.c_void_p]
+        lib.lerc_amd_decode_raster_window_device_depth.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int, ct.c_int,
+                                                                   ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_void_p,
+                                                                   ct.c_ulonglong, ct.c_ulonglong, ct.c_ulonglong, ct.c_int, ct.c_void_p,
+                                                                   ct.c_ulonglong]
     lib.lerc_amd_tile_batch_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_ulonglong)]
     lib.lerc_amd_tile_batch_counters.restype = None
     lib.lerc_amd_encode_device_async.argtypes = [ct.c_void_p] + enc + [ct.c_void_p, ct.c_uint, u32p]
@@ -140,7 +159,9 @@ def load_library():
             (("lerc_amd_encode_raster_tiles_device_strided", "lerc_amd_decode_raster_tiles_device_strided") if have_strided else ()) + \
             (("lerc_amd_encode_raster_tiles_device_range", "lerc_amd_decode_raster_window_device") if have_window else ()) + \
             (("lerc_amd_encode_tiles_device_depth", "lerc_amd_decode_tiles_device_depth", "lerc_amd_encode_raster_tiles_device_depth",
-              "lerc_amd_decode_raster_tiles_device_depth") if have_depth else ()):
+              "lerc_amd_decode_raster_tiles_device_depth") if have_depth else ()) + \
+            (("lerc_amd_encode_raster_tiles_device_depth_strided", "lerc_amd_decode_raster_tiles_device_depth_strided",
+              "lerc_amd_encode_raster_tiles_device_depth_range", "lerc_amd_decode_raster_window_device_depth") if have_depth_layouts else ()):
         getattr(lib, n).restype = ct.c_uint
     _LIB = lib
     return lib
@@ -369,6 +390,54 @@ class DeviceCodec:
         return self.lib.lerc_amd_decode_raster_tiles_device_depth(self.h, d_arena, offsets.ctypes.data, sizes.ctypes.data, dt_code, n_cols, n_rows,
                                                                   n_depth, int(pixel_pitch), int(row_pitch), int(tile[1]), int(tile[0]), d_raster,
                                                                   1 if d_valid else 0, d_valid or None, int(mask_row_pitch))
+
+    def encode_raster_tiles_depth_strided(self, d_raster, dt_code, n_cols, n_rows, n_depth, pixel_pitch, row_pitch, depth_pitch, tile, d_valid,
+                                          mask_row_pitch, max_z_err, d_arena, arena_cap, slot_bytes=0, tile_range=None):
+        """encode_raster_tiles_depth for a depth raster in any of the layouts of include/lerc_amd_depth.h: element (i, j, d) at i * row_pitch
+        + j * pixel_pitch + d * depth_pitch -- packed or gapped pixels (depth_pitch 1), planes or lines (pixel_pitch 1); the library's
+        check decides (status 2).  tile_range = (tileRow0, tileCol0, nTileRows, nTileCols): those tiles only, the tables full-grid and
+        zero outside the range"""
+        n_tiles = len(raster_tile_grid(n_rows, n_cols, tile))
+        offsets = np.zeros(n_tiles, np.uint64)
+        sizes = np.zeros(n_tiles, np.uint32)
+        used = ct.c_ulonglong(0)
+        head = (self.h, d_raster, dt_code, n_cols, n_rows, n_depth, int(pixel_pitch), int(row_pitch), int(depth_pitch), int(tile[1]), int(tile[0]))
+        tail = (1 if d_valid else 0, d_valid or None, int(mask_row_pitch), float(max_z_err), d_arena, int(arena_cap), int(slot_bytes),
+                offsets.ctypes.data, sizes.ctypes.data, ct.byref(used))
+        if tile_range is None:
+            rc = self.lib.lerc_amd_encode_raster_tiles_device_depth_strided(*head, *tail)
+        else:
+            rc = self.lib.lerc_amd_encode_raster_tiles_device_depth_range(*head, int(tile_range[1]), int(tile_range[0]), int(tile_range[3]),
+                                                                          int(tile_range[2]), *tail)
+        return rc, offsets, sizes, int(used.value)
+
+    def encode_raster_tiles_depth_range(self, d_raster, dt_code, n_cols, n_rows, n_depth, pixel_pitch, row_pitch, depth_pitch, tile, tile_range,
+                                        d_valid, mask_row_pitch, max_z_err, d_arena, arena_cap, slot_bytes=0):
+        return self.encode_raster_tiles_depth_strided(d_raster, dt_code, n_cols, n_rows, n_depth, pixel_pitch, row_pitch, depth_pitch, tile, d_valid,
+                                                      mask_row_pitch, max_z_err, d_arena, arena_cap, slot_bytes, tile_range=tile_range)
+
+    def decode_raster_tiles_depth_strided(self, d_arena, offsets, sizes, dt_code, n_cols, n_rows, n_depth, pixel_pitch, row_pitch, depth_pitch, tile,
+                                          d_raster, d_valid, mask_row_pitch):
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        sizes = np.ascontiguousarray(sizes, np.uint32)
+        assert len(offsets) == len(sizes) == len(raster_tile_grid(n_rows, n_cols, tile))
+        return self.lib.lerc_amd_decode_raster_tiles_device_depth_strided(self.h, d_arena, offsets.ctypes.data, sizes.ctypes.data, dt_code, n_cols,
+                                                                          n_rows, n_depth, int(pixel_pitch), int(row_pitch), int(depth_pitch),
+                                                                          int(tile[1]), int(tile[0]), d_raster, 1 if d_valid else 0, d_valid or None,
+                                                                          int(mask_row_pitch))
+
+    def decode_raster_window_depth(self, d_arena, offsets, sizes, dt_code, n_cols, n_rows, n_depth, tile, window_rect, d_window, pixel_pitch,
+                                   row_pitch, depth_pitch, d_valid, mask_row_pitch):
+        """window_rect = (row0, col0, rows, cols) of the depth mosaic n_rows x n_cols x n_depth into the buffer at d_window, which holds the
+        window only, in any of the layouts; offsets / sizes: the full grid's tables, read at the window's tiles (raster_window_tiles)"""
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        sizes = np.ascontiguousarray(sizes, np.uint32)
+        assert len(offsets) == len(sizes) == len(raster_tile_grid(n_rows, n_cols, tile))
+        return self.lib.lerc_amd_decode_raster_window_device_depth(self.h, d_arena, offsets.ctypes.data, sizes.ctypes.data, dt_code, n_cols, n_rows,
+                                                                   n_depth, int(tile[1]), int(tile[0]), int(window_rect[1]), int(window_rect[0]),
+                                                                   int(window_rect[3]), int(window_rect[2]), d_window, int(pixel_pitch),
+                                                                   int(row_pitch), int(depth_pitch), 1 if d_valid else 0, d_valid or None,
+                                                                   int(mask_row_pitch))
 
     def raster_tiles_counters(self):
         """tiles of the raster tile calls of this context: [cut through the staging buffer, encoded where they lie, pasted from the staging
@@ -673,6 +742,64 @@ def decode_raster_tiles_device_depth(codec, arena, offsets, sizes, out, valid_ou
     n_rows, n_cols, n_depth, pixel_pitch, row_pitch, d_valid, mask_pitch = _raster_depth_view(out, valid_out)
     return codec.decode_raster_tiles_depth(arena.data_ptr(), offsets, sizes, _torch_dt_code(out), n_cols, n_rows, n_depth, pixel_pitch, row_pitch, tile,
                                            out.data_ptr(), d_valid, mask_pitch)
+
+
+def _raster_depth_strides(raster, valid):
+    """-> (nRows, nCols, nDepth, pixelPitch, rowPitch, depthPitch, mask address, mask row pitch) of an [H, W, C] tensor with ANY strides:
+    the pitches are its strides -- chw.permute(1, 2, 0) (planes), rgba[..., :3] (gapped pixels), big[a:b, c:d] (packed pixels, longer
+    rows), a line-interleaved buffer.  Which layouts are taken is the library's to say (status 2); an axis of one element, whose
+    stride says nothing, gets the pitch a dense tensor would have"""
+    assert raster.dim() == 3, "raster: [H, W, C]"
+    n_rows, n_cols, n_depth = (int(v) for v in raster.shape)
+    depth_pitch = int(raster.stride(2)) if n_depth > 1 else 1
+    pixel_pitch = int(raster.stride(1)) if n_cols > 1 else (n_depth if depth_pitch == 1 else 1)
+    if n_rows > 1:
+        row_pitch = int(raster.stride(0))
+    else:
+        row_pitch = (n_cols - 1) * pixel_pitch + n_depth if depth_pitch == 1 else n_cols
+    if valid is None:
+        return n_rows, n_cols, n_depth, pixel_pitch, row_pitch, depth_pitch, 0, 0
+    assert valid.element_size() == 1 and tuple(valid.shape) == (n_rows, n_cols) and valid.stride(-1) == 1, "valid: uint8 [H, W] with dense rows"
+    return n_rows, n_cols, n_depth, pixel_pitch, row_pitch, depth_pitch, valid.data_ptr(), int(valid.stride(0)) if n_rows > 1 else n_cols
+
+
+def encode_raster_tiles_device_depth_strided(codec, raster, valid, max_z_err, tile, arena, slot_bytes=0):
+    """encode_raster_tiles_device_depth for an [H, W, C] tensor with any strides, without a copy: chw.permute(1, 2, 0), rgba[..., :3],
+    big[a:b, c:d], a line-interleaved buffer; a layout the library does not take comes back as status 2.  The blobs are those of the
+    packed call on raster.contiguous().  -> (status, offsets uint64[nTiles], sizes uint32[nTiles], arena bytes used)"""
+    n_rows, n_cols, n_depth, pixel_pitch, row_pitch, depth_pitch, d_valid, mask_pitch = _raster_depth_strides(raster, valid)
+    return codec.encode_raster_tiles_depth_strided(raster.data_ptr(), _torch_dt_code(raster), n_cols, n_rows, n_depth, pixel_pitch, row_pitch,
+                                                   depth_pitch, tile, d_valid, mask_pitch, max_z_err, arena.data_ptr(), arena.numel(), slot_bytes)
+
+
+def decode_raster_tiles_device_depth_strided(codec, arena, offsets, sizes, out, valid_out, tile):
+    """the way back: out as `raster` above, written where it lies -- the channels a gapped view leaves out (alpha) and everything
+    beside a view untouched --, valid_out as `valid` (written 1 / 0) or None"""
+    n_rows, n_cols, n_depth, pixel_pitch, row_pitch, depth_pitch, d_valid, mask_pitch = _raster_depth_strides(out, valid_out)
+    return codec.decode_raster_tiles_depth_strided(arena.data_ptr(), offsets, sizes, _torch_dt_code(out), n_cols, n_rows, n_depth, pixel_pitch,
+                                                   row_pitch, depth_pitch, tile, out.data_ptr(), d_valid, mask_pitch)
+
+
+def encode_raster_tile_range_device_depth(codec, raster, valid, max_z_err, tile, tile_range, arena, slot_bytes=0):
+    """encode_raster_tiles_device_depth_strided for a rectangle of the grid's tiles, tile_range = (tileRow0, tileCol0, nTileRows,
+    nTileCols), as encode_raster_tile_range_device: raster and valid are the WHOLE raster, every blob is what the whole-raster call
+    makes of that tile, and slotted the range takes the first rooms of the arena.
+    -> (status, offsets, sizes, arena bytes used): full-grid tables, zero outside the range"""
+    n_rows, n_cols, n_depth, pixel_pitch, row_pitch, depth_pitch, d_valid, mask_pitch = _raster_depth_strides(raster, valid)
+    return codec.encode_raster_tiles_depth_range(raster.data_ptr(), _torch_dt_code(raster), n_cols, n_rows, n_depth, pixel_pitch, row_pitch,
+                                                 depth_pitch, tile, tile_range, d_valid, mask_pitch, max_z_err, arena.data_ptr(), arena.numel(),
+                                                 slot_bytes)
+
+
+def decode_raster_window_device_depth(codec, arena, offsets, sizes, raster_shape, tile, window, out, valid_out):
+    """a window of a depth mosaic, as decode_raster_window_device: raster_shape = (nRows, nCols) of the raster the grid of `tile` was cut
+    from, offsets / sizes its full-grid tables, window = (row0, col0) the raster position of out's first pixel; out an [h, w, C] tensor
+    with any strides whose size is the window's, valid_out uint8 [h, w] with dense rows or None.  Only the tiles of
+    raster_window_tiles are read and decoded; nothing beside out's elements is written; a tile whose blob fails leaves its part zeroed"""
+    rows, cols, n_depth, pixel_pitch, row_pitch, depth_pitch, d_valid, mask_pitch = _raster_depth_strides(out, valid_out)
+    return codec.decode_raster_window_depth(arena.data_ptr(), offsets, sizes, _torch_dt_code(out), int(raster_shape[1]), int(raster_shape[0]),
+                                            n_depth, tile, (int(window[0]), int(window[1]), rows, cols), out.data_ptr(), pixel_pitch, row_pitch,
+                                            depth_pitch, d_valid, mask_pitch)
 
 
 def raster_tile_grid(n_rows, n_cols, tile):

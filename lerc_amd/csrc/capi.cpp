@@ -155,6 +155,13 @@ lerc_status rasterTilesArgs(const lerc_amd_context* h, unsigned dataType, int nC
   return rasterTileDimsOk(nCols, nRows, tileCols, tileRows, dataType) ? kOk : kDimsTooLarge;
 }
 
+// the depth rasters of lerc_amd_depth.h: the raster tile calls' check, a depth >= 1, and a tile with its depth within INT_MAX
+lerc_status rasterDepthArgs(const lerc_amd_context* h, unsigned dataType, int nCols, int nRows, int nDepth, int tileCols, int tileRows, bool alsoOk = true)
+{
+  if (const lerc_status bad = rasterTilesArgs(h, dataType, nCols, nRows, tileCols, tileRows, nDepth >= 1 && alsoOk)) return bad;
+  return dimsOk(nDepth, std::min(nCols, tileCols), std::min(nRows, tileRows), (size_t)dtSize((int)dataType)) ? kOk : kDimsTooLarge;
+}
+
 bool usesNoData(const unsigned char* pUsesNoData, int nBands)
 {
   if (!pUsesNoData) return false;
@@ -222,6 +229,20 @@ RasterTilesRequest rasterTilesRequest(const void* dRaster, unsigned dataType, in
   rq.pixelPitch = lay.pixelPitch; rq.anyLayout = lay.any; rq.rowPitch = lay.rowPitch; rq.bandPitch = lay.bandPitch; rq.maskRowPitch = lay.maskRowPitch;
   rq.dArena = const_cast<unsigned char*>(dArena); rq.hOffsets = const_cast<u64*>(offsets); rq.hSizes = const_cast<unsigned*>(sizes);
   rq.maxZErr = maxZErr; rq.arenaCapacity = arenaCapacity; rq.slotBytes = slotBytes;
+  return rq;
+}
+
+// a depth raster (or a window's buffer): element (row, col, d) at row * rowPitch + col * pixelPitch + d * depthPitch
+struct DepthLayout { u64 pixelPitch, rowPitch, depthPitch, maskRowPitch; };
+
+// (nDepth 1: depthPitch is not looked at, and the request is the strided calls' with one band)
+RasterTilesRequest rasterDepthRequest(const void* dRaster, unsigned dataType, int nCols, int nRows, int nDepth, const DepthLayout& lay, int tileCols,
+                                      int tileRows, int nMasks, const unsigned char* dValidBytes, const unsigned char* dArena, const u64* offsets,
+                                      const unsigned* sizes, double maxZErr = 0, u64 arenaCapacity = 0, u64 slotBytes = 0)
+{
+  RasterTilesRequest rq = rasterTilesRequest(dRaster, dataType, nCols, nRows, 1, strided(lay.pixelPitch, lay.rowPitch, 0, lay.maskRowPitch), tileCols, tileRows,
+                                             nMasks, dValidBytes, dArena, offsets, sizes, maxZErr, arenaCapacity, slotBytes);
+  rq.nDepth = nDepth; rq.depthPitch = nDepth > 1 ? lay.depthPitch : 1;
   return rq;
 }
 
@@ -863,32 +884,73 @@ lerc_status lerc_amd_decode_raster_tiles_device_strided(lerc_amd_context* h, con
                                                             tileCols, tileRows, nMasks, dValidBytes, dArena, offsets, sizes));
 }
 
-// ---- the same for packed pixels of nDepth elements, every tile one blob with the header's nDepth (lerc_amd_depth.h).  The driver sees
-// a row as a run of elements (pixelPitch 1); any other pitch description than packed pixels is refused here.
+// ---- depth rasters, every tile one blob with the header's nDepth (lerc_amd_depth.h): the layouts are the driver's to check; the two
+// calls without a depthPitch take packed pixels only and refuse every other description here
 lerc_status lerc_amd_encode_raster_tiles_device_depth(lerc_amd_context* h, const void* dRaster, unsigned int dataType, int nCols, int nRows, int nDepth,
   unsigned long long pixelPitch, unsigned long long rowPitch, int tileCols, int tileRows, int nMasks, const unsigned char* dValidBytes,
   unsigned long long maskRowPitch, double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity, unsigned long long slotBytes,
   unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed)
 {
   if (arenaUsed) *arenaUsed = 0;
-  if (const lerc_status bad = rasterTilesArgs(h, dataType, nCols, nRows, tileCols, tileRows, nDepth >= 1 && pixelPitch == (u64)nDepth)) return bad;
-  if (!dimsOk(nDepth, std::min(nCols, tileCols), std::min(nRows, tileRows), (size_t)dtSize((int)dataType))) return kDimsTooLarge;
-  RasterTilesRequest rq = rasterTilesRequest(dRaster, dataType, nCols, nRows, 1, planes(rowPitch, 0, maskRowPitch), tileCols, tileRows, nMasks, dValidBytes,
-                                             dArena, offsets, sizes, maxZErr, arenaCapacity, slotBytes);
-  rq.nDepth = nDepth;
-  return encodeRasterTiles(h, rq, arenaUsed);
+  if (const lerc_status bad = rasterDepthArgs(h, dataType, nCols, nRows, nDepth, tileCols, tileRows, pixelPitch == (u64)nDepth)) return bad;
+  return encodeRasterTiles(h, rasterDepthRequest(dRaster, dataType, nCols, nRows, nDepth, { pixelPitch, rowPitch, 1, maskRowPitch }, tileCols, tileRows, nMasks,
+                                                 dValidBytes, dArena, offsets, sizes, maxZErr, arenaCapacity, slotBytes), arenaUsed);
 }
 
 lerc_status lerc_amd_decode_raster_tiles_device_depth(lerc_amd_context* h, const unsigned char* dArena, const unsigned long long* offsets,
   const unsigned int* sizes, unsigned int dataType, int nCols, int nRows, int nDepth, unsigned long long pixelPitch, unsigned long long rowPitch,
   int tileCols, int tileRows, void* dRaster, int nMasks, unsigned char* dValidBytes, unsigned long long maskRowPitch)
 {
-  if (const lerc_status bad = rasterTilesArgs(h, dataType, nCols, nRows, tileCols, tileRows, nDepth >= 1 && pixelPitch == (u64)nDepth)) return bad;
-  if (!dimsOk(nDepth, std::min(nCols, tileCols), std::min(nRows, tileRows), (size_t)dtSize((int)dataType))) return kDimsTooLarge;
-  RasterTilesRequest rq = rasterTilesRequest(dRaster, dataType, nCols, nRows, 1, planes(rowPitch, 0, maskRowPitch), tileCols, tileRows, nMasks, dValidBytes,
-                                             dArena, offsets, sizes);
-  rq.nDepth = nDepth;
-  return decodeRasterTilesDevice(h->ctx, rq);
+  if (const lerc_status bad = rasterDepthArgs(h, dataType, nCols, nRows, nDepth, tileCols, tileRows, pixelPitch == (u64)nDepth)) return bad;
+  return decodeRasterTilesDevice(h->ctx, rasterDepthRequest(dRaster, dataType, nCols, nRows, nDepth, { pixelPitch, rowPitch, 1, maskRowPitch }, tileCols, tileRows,
+                                                            nMasks, dValidBytes, dArena, offsets, sizes));
+}
+
+lerc_status lerc_amd_encode_raster_tiles_device_depth_strided(lerc_amd_context* h, const void* dRaster, unsigned int dataType, int nCols, int nRows,
+  int nDepth, unsigned long long pixelPitch, unsigned long long rowPitch, unsigned long long depthPitch, int tileCols, int tileRows, int nMasks,
+  const unsigned char* dValidBytes, unsigned long long maskRowPitch, double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity,
+  unsigned long long slotBytes, unsigned long long* offsets, unsigned int* sizes, unsigned long long* arenaUsed)
+{
+  if (arenaUsed) *arenaUsed = 0;
+  if (const lerc_status bad = rasterDepthArgs(h, dataType, nCols, nRows, nDepth, tileCols, tileRows)) return bad;
+  return encodeRasterTiles(h, rasterDepthRequest(dRaster, dataType, nCols, nRows, nDepth, { pixelPitch, rowPitch, depthPitch, maskRowPitch }, tileCols, tileRows,
+                                                 nMasks, dValidBytes, dArena, offsets, sizes, maxZErr, arenaCapacity, slotBytes), arenaUsed);
+}
+
+lerc_status lerc_amd_decode_raster_tiles_device_depth_strided(lerc_amd_context* h, const unsigned char* dArena, const unsigned long long* offsets,
+  const unsigned int* sizes, unsigned int dataType, int nCols, int nRows, int nDepth, unsigned long long pixelPitch, unsigned long long rowPitch,
+  unsigned long long depthPitch, int tileCols, int tileRows, void* dRaster, int nMasks, unsigned char* dValidBytes, unsigned long long maskRowPitch)
+{
+  if (const lerc_status bad = rasterDepthArgs(h, dataType, nCols, nRows, nDepth, tileCols, tileRows)) return bad;
+  return decodeRasterTilesDevice(h->ctx, rasterDepthRequest(dRaster, dataType, nCols, nRows, nDepth, { pixelPitch, rowPitch, depthPitch, maskRowPitch }, tileCols,
+                                                            tileRows, nMasks, dValidBytes, dArena, offsets, sizes));
+}
+
+lerc_status lerc_amd_encode_raster_tiles_device_depth_range(lerc_amd_context* h, const void* dRaster, unsigned int dataType, int nCols, int nRows,
+  int nDepth, unsigned long long pixelPitch, unsigned long long rowPitch, unsigned long long depthPitch, int tileCols, int tileRows, int tileCol0,
+  int tileRow0, int nTileCols, int nTileRows, int nMasks, const unsigned char* dValidBytes, unsigned long long maskRowPitch, double maxZErr,
+  unsigned char* dArena, unsigned long long arenaCapacity, unsigned long long slotBytes, unsigned long long* offsets, unsigned int* sizes,
+  unsigned long long* arenaUsed)
+{
+  if (arenaUsed) *arenaUsed = 0;
+  const bool rangeOk = !(tileCol0 < 0 || tileRow0 < 0 || nTileCols <= 0 || nTileRows <= 0);    // (inside the grid: the driver's check)
+  if (const lerc_status bad = rasterDepthArgs(h, dataType, nCols, nRows, nDepth, tileCols, tileRows, rangeOk)) return bad;
+  RasterTilesRequest rq = rasterDepthRequest(dRaster, dataType, nCols, nRows, nDepth, { pixelPitch, rowPitch, depthPitch, maskRowPitch }, tileCols, tileRows,
+                                             nMasks, dValidBytes, dArena, offsets, sizes, maxZErr, arenaCapacity, slotBytes);
+  rq.tileCol0 = tileCol0; rq.tileRow0 = tileRow0; rq.nTileCols = nTileCols; rq.nTileRows = nTileRows;
+  return encodeRasterTiles(h, rq, arenaUsed);
+}
+
+lerc_status lerc_amd_decode_raster_window_device_depth(lerc_amd_context* h, const unsigned char* dArena, const unsigned long long* offsets,
+  const unsigned int* sizes, unsigned int dataType, int nCols, int nRows, int nDepth, int tileCols, int tileRows, int winCol0, int winRow0,
+  int winCols, int winRows, void* dWindow, unsigned long long pixelPitch, unsigned long long rowPitch, unsigned long long depthPitch, int nMasks,
+  unsigned char* dValidBytes, unsigned long long maskRowPitch)
+{
+  if (const lerc_status bad = rasterDepthArgs(h, dataType, nCols, nRows, nDepth, tileCols, tileRows)) return bad;
+  RasterWindow win;
+  win.col0 = winCol0; win.row0 = winRow0; win.cols = winCols; win.rows = winRows;
+  return decodeRasterWindowDevice(h->ctx, rasterDepthRequest(dWindow, dataType, nCols, nRows, nDepth, { pixelPitch, rowPitch, depthPitch, maskRowPitch }, tileCols,
+                                                             tileRows, nMasks, dValidBytes, dArena, offsets, sizes), win);
 }
 
 // ---- a range of the grid's tiles coded, and a window of the mosaic decoded into a buffer of its own

@@ -343,9 +343,11 @@ struct RasterTilesRequest
   // the tiles of the grid the call is about, [tileRow0, tileRow0 + nTileRows) x [tileCol0, tileCol0 + nTileCols); a negative count: all
   // from the first on (the default: the whole grid).  hOffsets / hSizes stay full-grid tables, only the range's entries are touched
   int tileCol0 = 0, tileRow0 = 0, nTileCols = -1, nTileRows = -1;
-  // depth tiles (the _depth entry points): > 1: one band of packed pixels, nDepth elements each (rowPitch >= nCols * nDepth, pixelPitch
-  // 1: a row is a run of elements); every tile is one blob with the header's nDepth
+  // depth tiles (the _depth entry points): > 1: one band (nBands 1) whose element (row, col, d) lies at row * rowPitch + col * pixelPitch
+  // + d * depthPitch, in one of the four layouts of lerc_amd_depth.h -- packed or gapped pixels (depthPitch 1), planes or lines
+  // (pixelPitch 1) --; every tile is one blob with the header's nDepth.  nDepth 1: depthPitch is not looked at
   int nDepth = 1;
+  u64 depthPitch = 1;
 };
 u32 encodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq, u64& arenaUsed);
 u32 decodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq);

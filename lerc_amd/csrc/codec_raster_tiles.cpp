@@ -18,6 +18,11 @@
 // and the slots' count.  lerc_amd_decode_raster_window_device is the decode of the range of tiles a window touches into a buffer that
 // holds the window only: the same chunks, tables gathered at those tiles alone, the same tile calls into the staging buffer -- and a
 // clipped paste behind them, k_rw_paste / k_rw_paste_px (raster_window.hip).
+//
+// A DEPTH raster (nDepth > 1, lerc_amd_depth.h) is one band whose tiles are staged as [n][r][c][nDepth] and handed to
+// encodeTilesDeviceDepth / decodeTilesDeviceDepth; it differs in how it is cut and pasted, and in nothing else, ranges and windows
+// included.  Packed pixels are runs of elements: the band kernels with the column counts scaled by nDepth (a window's too).  Gapped
+// pixels, planes and lines go through k_rtd_cut / k_rtd_paste (raster_tiles_depth.hip), whose paste is clipped to a window always.
 #include "codec.h"
 #include "raster_tiles.h"
 
@@ -60,6 +65,27 @@ bool rtLayoutOk(const RasterTilesRequest& rq, u64 nCols, u64 nRows)
   return rq.rowPitch >= nBands && (nCols == 1 || (rq.rowPitch - nBands) / (nCols - 1) >= rq.pixelPitch);
 }
 
+// The layouts of a depth raster (nDepth > 1; lerc_amd_depth.h): element (row, col, d) at row * rowPitch + col * pixelPitch + d * depthPitch.
+// Packed pixels are runs of elements and go through the band kernels with the column counts scaled by nDepth; the others through
+// k_rtd_cut / k_rtd_paste (raster_tiles_depth.hip).  Rows, lines or planes that overlap are no layout.  (The products of the header's
+// table are never taken: the pitches are any 64-bit numbers.)
+enum RtDepthLayout { kRtdNone, kRtdPacked, kRtdGapped, kRtdPlanes, kRtdLines };
+
+RtDepthLayout rtDepthLayout(const RasterTilesRequest& rq, u64 nCols, u64 nRows)
+{
+  const u64 D = (u64)rq.nDepth, pp = rq.pixelPitch, rp = rq.rowPitch, dp = rq.depthPitch;
+  if (dp == 1 && pp >= D)
+  {
+    // (rowPitch >= (nCols - 1) * pixelPitch + nDepth)
+    if (rp >= D && (nCols == 1 || (rp - D) / (nCols - 1) >= pp)) return pp == D ? kRtdPacked : kRtdGapped;
+    return kRtdNone;
+  }
+  if (pp != 1 || rp < nCols || dp < nCols) return kRtdNone;
+  if (nRows == 1 || (dp - nCols) / (nRows - 1) >= rp) return kRtdPlanes;    // (depthPitch >= (nRows - 1) * rowPitch + nCols)
+  if ((rp - nCols) / (D - 1) >= dp) return kRtdLines;                       // (rowPitch >= (nDepth - 1) * depthPitch + nCols)
+  return kRtdNone;
+}
+
 // (win: the buffer at dRaster and the mask hold that window of the raster, and the layout's rules apply to its size)
 bool rtArgsOk(const RasterTilesRequest& rq, bool encode, const RasterWindow* win = nullptr)
 {
@@ -70,11 +96,10 @@ bool rtArgsOk(const RasterTilesRequest& rq, bool encode, const RasterWindow* win
     || rq.tileCols <= 0 || rq.tileRows <= 0 || (rq.nMasks != 0 && rq.nMasks != 1) || (rq.nMasks == 0) != (rq.dValidBytes == nullptr))
     return false;
   if (rq.nMasks && rq.maskRowPitch < bufCols) return false;
-  // (depth tiles: pixels packed, nDepth elements each -- a row is a run of nCols * nDepth elements, which is what the checks below see of it)
-  if (rq.nDepth < 1 || (rq.nDepth > 1 && (win || rq.nBands != 1 || rq.pixelPitch != 1 || rq.rowPitch / (u64)rq.nDepth < bufCols
-    || (u64)std::min(rq.tileCols, rq.nCols) * (u64)rq.nDepth > 0x7FFFFFFFull)))
+  // (depth tiles: one band in a layout of its own; a tile's row of elements is counted in 32 bits)
+  if (rq.nDepth < 1 || (rq.nDepth > 1 && (rq.nBands != 1 || (u64)std::min(rq.tileCols, rq.nCols) * (u64)rq.nDepth > 0x7FFFFFFFull)))
     return false;
-  if (!rtLayoutOk(rq, bufCols, bufRows)) return false;
+  if (rq.nDepth > 1 ? rtDepthLayout(rq, bufCols, bufRows) == kRtdNone : !rtLayoutOk(rq, bufCols, bufRows)) return false;
   if (((uintptr_t)rq.dRaster & (uintptr_t)(dtSize(rq.dt) - 1)) != 0) return false;    // (elements lie on their own boundaries)
   if (encode && (rq.maxZErr < 0 || (rq.slotBytes & 15u) != 0)) return false;
   return true;
@@ -142,24 +167,67 @@ RtChunk rtChunk(const RasterTilesRequest& rq, const RtClass& k, u32 k0, u32 n, b
   ch.rowPitch = mask ? rq.maskRowPitch : rq.rowPitch; ch.bandPitch = mask ? 0 : rq.bandPitch;
   ch.tileRows = (u32)rq.tileRows; ch.tileCols = (u32)rq.tileCols; ch.r = k.r; ch.c = k.c;
   ch.ty0 = k.ty0; ch.tx0 = k.tx0; ch.classW = k.nTX; ch.k0 = k0; ch.n = n; ch.nBands = mask ? 1u : (u32)rq.nBands;
-  // (depth tiles: a tile's rows are runs of c * nDepth elements, a tile column is tileCols * nDepth elements wide; the mask stays at pixel width)
-  // (a tile wider than the raster is clipped to it first -- its column index is 0 then, so nothing changes --: rtArgsOk has bounded
-  // min(tileCols, nCols) * nDepth, and that is the product taken here)
-  if (!mask && rq.nDepth > 1) { ch.tileCols = (u32)std::min(rq.tileCols, rq.nCols) * (u32)rq.nDepth; ch.c *= (u32)rq.nDepth; }
   return ch;
 }
 
-// the data of a chunk: planes through k_rt_cut / k_rt_paste, an interleaved raster through k_rt_cut_px / k_rt_paste_px
+// the whole raster as a window of itself
+RasterWindow rtWholeRaster(const RasterTilesRequest& rq) { RasterWindow w; w.cols = rq.nCols; w.rows = rq.nRows; return w; }
+
+// Packed depth pixels seen as a run of elements, one band: a tile's rows are runs of c * nDepth elements, a tile column is tileCols *
+// nDepth elements wide, and so is a window's rectangle; the mask stays at pixel width.  (A tile wider than the raster is clipped to it
+// first -- its column index is 0 then, so nothing changes --: rtArgsOk has bounded min(tileCols, nCols) * nDepth, and that is the
+// product taken here.)
+RwChunk rtPackedChunk(const RasterTilesRequest& rq, const RtClass& k, u32 k0, u32 n, const RasterWindow& win)
+{
+  const u32 D = (u32)rq.nDepth;
+  RwChunk cw{ rtChunk(rq, k, k0, n, false), 1, (u32)win.row0, (u32)win.col0 * D, (u32)win.rows, (u32)win.cols * D };
+  cw.ch.tileCols = (u32)std::min(rq.tileCols, rq.nCols) * D; cw.ch.c *= D;
+  return cw;
+}
+// (a raster whose rows of elements leave 32 bits: the window's columns cannot be scaled, and the depth kernels take the pixels as they are)
+bool rtPackedAsRuns(const RasterTilesRequest& rq, const RasterWindow* win)
+{
+  return rtDepthLayout(rq, (u64)(win ? win->cols : rq.nCols), (u64)(win ? win->rows : rq.nRows)) == kRtdPacked && (!win || (u64)rq.nCols * (u64)rq.nDepth <= 0x7FFFFFFFull);
+}
+
+RtdChunk rtDepthChunk(const RasterTilesRequest& rq, const RtClass& k, u32 k0, u32 n, const RasterWindow& win)
+{
+  RtdChunk cd{ rtChunk(rq, k, k0, n, false), rq.pixelPitch, rq.depthPitch, (u32)win.row0, (u32)win.col0, (u32)win.rows, (u32)win.cols };
+  cd.ch.nBands = (u32)rq.nDepth;
+  return cd;
+}
+
+// the data of a chunk: planes through k_rt_cut / k_rt_paste, an interleaved raster through k_rt_cut_px / k_rt_paste_px, a depth raster
+// as runs of elements through the former or through k_rtd_cut / k_rtd_paste; win: the clipped paste of each
 void rtCutData(const RasterTilesRequest& rq, const RtClass& k, u32 k0, u32 n, u8* stage, u32 eb, hipStream_t st)
 {
+  if (rq.nDepth > 1)
+  {
+    if (rtPackedAsRuns(rq, nullptr)) launchRasterCut(rq.dRaster, stage, rtPackedChunk(rq, k, k0, n, rtWholeRaster(rq)).ch, eb, st);
+    else launchRasterCutDepth(rq.dRaster, stage, rtDepthChunk(rq, k, k0, n, rtWholeRaster(rq)), eb, st);
+    return;
+  }
   const RtChunk ch = rtChunk(rq, k, k0, n, false);
   if (rq.pixelPitch == 1) launchRasterCut(rq.dRaster, stage, ch, eb, st);
   else launchRasterCutPx(rq.dRaster, stage, RtChunkPx{ ch, rq.pixelPitch }, eb, st);
 }
-void rtPasteData(const RasterTilesRequest& rq, const RtClass& k, u32 k0, u32 n, const u8* stage, u32 eb, hipStream_t st)
+void rtPasteData(const RasterTilesRequest& rq, const RtClass& k, u32 k0, u32 n, const u8* stage, u32 eb, hipStream_t st, const RasterWindow* win)
 {
+  if (rq.nDepth > 1)
+  {
+    if (!rtPackedAsRuns(rq, win)) launchRasterPasteDepth(stage, rq.dRaster, rtDepthChunk(rq, k, k0, n, win ? *win : rtWholeRaster(rq)), eb, st);
+    else if (win) launchWindowPaste(stage, rq.dRaster, rtPackedChunk(rq, k, k0, n, *win), eb, st);
+    else launchRasterPaste(stage, rq.dRaster, rtPackedChunk(rq, k, k0, n, rtWholeRaster(rq)).ch, eb, st);
+    return;
+  }
   const RtChunk ch = rtChunk(rq, k, k0, n, false);
-  if (rq.pixelPitch == 1) launchRasterPaste(stage, rq.dRaster, ch, eb, st);
+  if (win)
+  {
+    const RwChunk cw{ ch, rq.pixelPitch, (u32)win->row0, (u32)win->col0, (u32)win->rows, (u32)win->cols };
+    if (rq.pixelPitch == 1) launchWindowPaste(stage, rq.dRaster, cw, eb, st);
+    else launchWindowPastePx(stage, rq.dRaster, cw, eb, st);
+  }
+  else if (rq.pixelPitch == 1) launchRasterPaste(stage, rq.dRaster, ch, eb, st);
   else launchRasterPastePx(stage, rq.dRaster, RtChunkPx{ ch, rq.pixelPitch }, eb, st);
 }
 
@@ -312,18 +380,9 @@ static u32 rtDecode(Context& ctx, const RasterTilesRequest& rq, const RasterWind
       {
         hipStream_t st = ctx.activeStream();
         (void)hipGetLastError();
-        if (win)
-        {
-          const RwChunk cw{ rtChunk(rq, k, k0, n, false), rq.pixelPitch, (u32)win->row0, (u32)win->col0, (u32)win->rows, (u32)win->cols };
-          if (rq.pixelPitch == 1) launchWindowPaste(stage, rq.dRaster, cw, eb, st);
-          else launchWindowPastePx(stage, rq.dRaster, cw, eb, st);
-          if (rq.nMasks) launchWindowPaste(stage + rtMaskAt(p, n), rq.dValidBytes, RwChunk{ rtChunk(rq, k, k0, n, true), 1, cw.winRow0, cw.winCol0, cw.winRows, cw.winCols }, 1, st);
-        }
-        else
-        {
-          rtPasteData(rq, k, k0, n, stage, eb, st);
-          if (rq.nMasks) launchRasterPaste(stage + rtMaskAt(p, n), rq.dValidBytes, rtChunk(rq, k, k0, n, true), 1, st);
-        }
+        rtPasteData(rq, k, k0, n, stage, eb, st, win);
+        if (rq.nMasks && win) launchWindowPaste(stage + rtMaskAt(p, n), rq.dValidBytes, RwChunk{ rtChunk(rq, k, k0, n, true), 1, (u32)win->row0, (u32)win->col0, (u32)win->rows, (u32)win->cols }, 1, st);
+        else if (rq.nMasks) launchRasterPaste(stage + rtMaskAt(p, n), rq.dValidBytes, rtChunk(rq, k, k0, n, true), 1, st);
         if (hipGetLastError() != hipSuccess) { ctx.lastError = "lerc_amd: the raster paste kernel could not be launched"; return kFailed; }
       }
     }

@@ -67,4 +67,21 @@ struct RwChunk
 void launchWindowPaste(const void* dStage, void* dWindow, const RwChunk& cw, u32 elemBytes, hipStream_t st);
 void launchWindowPastePx(const void* dStage, void* dWindow, const RwChunk& cw, u32 elemBytes, hipStream_t st);
 
+// ---- depth rasters (raster_tiles_depth.hip): element (i, j, d) lies at i * rowPitch + j * pixelPitch + d * depthPitch, the staged form
+// is [n][r][c][nDepth].  ch: the grid and the class in PIXELS, nBands = nDepth, rowPitch the raster's; ch.bandPitch is not used.  One of
+// pixelPitch (planes, lines) and depthPitch (gapped pixels; packed ones, pixelPitch == nDepth, are taken too) is 1.  The window is
+// RwChunk's: the buffer at dRaster holds rows [winRow0, winRow0 + winRows) by columns [winCol0, winCol0 + winCols) of the raster and
+// the pitches are its own; the whole raster: 0, 0, nRows, nCols.  The segment buffer of the pixel-interleaved kernels serves a pixel
+// of up to kRtPxMaxPitch elements (nDepth; pixelPitch where it has gaps); beyond that a lane moves an element, with the same results.
+struct RtdChunk
+{
+  RtChunk ch;
+  u64 pixelPitch, depthPitch;
+  u32 winRow0, winCol0, winRows, winCols;
+};
+
+// staging <- raster (of the tiles' parts inside the window; the encode's: everything) and raster <- staging, data only.  One launch.
+void launchRasterCutDepth(const void* dRaster, void* dStage, const RtdChunk& cd, u32 elemBytes, hipStream_t st);
+void launchRasterPasteDepth(const void* dStage, void* dRaster, const RtdChunk& cd, u32 elemBytes, hipStream_t st);
+
 }    // namespace lerc

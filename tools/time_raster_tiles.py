@@ -36,6 +36,20 @@ rocprofv3 --kernel-trace --stats (k_rt_cut_px, k_rt_paste_px against k_rt_cut, k
 whole-raster decode and a device copy of the slice.  The shifted whole-raster window (8189 x 8187 from (3, 5)) against the whole-raster
 decode is what the clipped paste costs over k_rt_paste.  Every window is checked bit for bit against the slice first.  No pass mark;
 the numbers are recorded in DESIGN.md 8.3 and profiles/raster_window_time.txt.
+
+`python tools/time_raster_tiles.py depth [FILE]` times the depth raster calls that take a layout (include/lerc_amd_depth.h) on
+8192 x 8192 x 3 uint16 lossless and 4096 x 4096 x 4 float32 at 0.01, tiles of 256 x 256, blobs of nDepth = C:
+
+  (a) lerc_amd_*_raster_tiles_device_depth_strided on chw.permute(1, 2, 0) (planes) and on the C channels of an [H, W, C + 1]
+      tensor (gapped pixels: RGB out of RGBA), no copy: k_rtd_cut / k_rtd_paste read and write the raster where it lies
+  (b) what a caller did before: view.contiguous() and the packed depth call, the copy inside the timed region; back: the packed
+      decode and the copy into the view
+  and the window decode into packed pixels against the whole-raster decode and a copy of the slice, for windows of one tile, 1/16,
+  1/4 and the whole, with a least-squares line through them: a fixed cost and a cost per thousand tiles.
+
+(a) and (b) alternate inside one loop of REPS; the arenas of (a) and (b) are compared byte for byte before anything is timed, every
+window against the slice.  No pass mark: the report says where (a) is slower than (b) or a window slower than the whole decode.  It
+goes to FILE (default profiles/raster_depth_layouts_time.txt) and to stdout; the table is recorded in DESIGN.md 8.4.
 """
 import os
 import statistics
@@ -173,6 +187,166 @@ def window():
     return 0
 
 
+def depth(out_path):
+    import torch
+    from lerc_amd import api, synth
+    assert torch.cuda.is_available(), "needs a GPU"
+    tile = (TILE, TILE)
+    codec = api.DeviceCodec(torch.cuda.current_stream().cuda_stream)
+    lines = []
+
+    def say(text):
+        lines.append(text)
+        print(text, flush=True)
+
+    say("depth raster calls with a layout against contiguous() + the packed calls -- %s; tiles of %d x %d, packed arenas; the two ways "
+        "alternating, median [interquartile range] of %d, ms" % (torch.cuda.get_device_name(0), TILE, TILE, REPS))
+    verdicts = []
+    for name, size, c, e in (("uint16", 8192, 3, 0.0), ("float32", 4096, 4, E)):
+        terrain = synth.c2_float32(size, size, device="cuda:0")
+        chans = [terrain.roll(37 * b, 0).roll(91 * b, 1) + 3.0 * b for b in range(c)]
+        if name == "uint16":
+            lo, hi = float(terrain.min()), float(terrain.max())
+            chans = [((ch - lo) * (60000.0 / (hi - lo + 3.0 * c))).to(torch.int32).to(torch.uint16) for ch in chans]
+        hwc = torch.stack(chans, dim=2).contiguous()
+        del chans, terrain
+        item = hwc.element_size()
+        mib = hwc.numel() * item / 2 ** 20
+        n = len(api.raster_tile_grid(size, size, tile))
+        cap = n * (TILE * TILE * c * item + TILE * TILE // 4 + 2048)
+        arena_a = torch.zeros(cap, dtype=torch.uint8, device="cuda")
+        arena_b = torch.zeros(cap, dtype=torch.uint8, device="cuda")
+        hwc_back = torch.zeros_like(hwc)
+        say("%s x %d, %d x %d (%.0f MiB), maxZErr %g, %d tiles" % (name, c, size, size, mib, e, n))
+        for what in ("planes [C, H, W]", "gapped: %d channels of %d" % (c, c + 1)):
+            if what.startswith("planes"):
+                holder = hwc.permute(2, 0, 1).contiguous()
+                view, holder_back = holder.permute(1, 2, 0), torch.zeros_like(holder)
+                view_back = holder_back.permute(1, 2, 0)
+            else:
+                holder = torch.zeros((size, size, c + 1), dtype=hwc.dtype, device="cuda")
+                holder[..., :c] = hwc
+                view, holder_back = holder[..., :c], torch.zeros_like(holder)
+                view_back = holder_back[..., :c]
+            state = {}
+
+            def enc_a():
+                rc, offs, sizes, used = api.encode_raster_tiles_device_depth_strided(codec, view, None, e, tile, arena_a)
+                assert rc == 0, (rc, codec.last_error())
+                state["a"] = (offs, sizes, used)
+
+            def enc_b():
+                rc, offs, sizes, used = api.encode_raster_tiles_device_depth(codec, view.contiguous(), None, e, tile, arena_b)
+                assert rc == 0, (rc, codec.last_error())
+                state["b"] = (offs, sizes, used)
+
+            def dec_a():
+                assert api.decode_raster_tiles_device_depth_strided(codec, arena_a, state["a"][0], state["a"][1], view_back, None, tile) == 0
+
+            def dec_b():
+                assert api.decode_raster_tiles_device_depth(codec, arena_a, state["a"][0], state["a"][1], hwc_back, None, tile) == 0
+                view_back.copy_(hwc_back)
+
+            b0 = codec.tile_batch_counters()
+            enc_a()
+            b1 = codec.tile_batch_counters()
+            enc_b()
+            torch.cuda.synchronize()
+            used = state["a"][2]
+            assert used == state["b"][2] and (state["a"][0] == state["b"][0]).all() and (state["a"][1] == state["b"][1]).all(), "the tables differ"
+            assert torch.equal(arena_a[:used], arena_b[:used]), "the blobs differ from the packed call's"
+            dec_b()
+            torch.cuda.synchronize()
+            want = view_back.clone()
+            view_back.zero_()
+            dec_a()
+            torch.cuda.synchronize()
+            assert torch.equal(view_back.contiguous().view(torch.uint8), want.contiguous().view(torch.uint8)), "the decodes differ"
+            err = float((view_back.double() - view.double()).abs().max())
+            assert err <= e + 1e-4, err
+            (ea, eb), (da, db) = timed_pair(torch, enc_a, enc_b), timed_pair(torch, dec_a, dec_b)
+            say("  %-28s %d blob bytes, tile batch counters of one encode %s, max error %.6f" % (what, used, [int(y - x) for x, y in zip(b0, b1)], err))
+            say("    (a) strided call, no copy            encode %8.3f [%6.3f]   decode %8.3f [%6.3f]" % (ea + da))
+            say("    (b) contiguous() + packed call       encode %8.3f [%6.3f]   decode %8.3f [%6.3f]" % (eb + db))
+            say("    (b) - (a)                            encode %8.3f            decode %8.3f" % (eb[0] - ea[0], db[0] - da[0]))
+            for way, a, b in (("encode", ea, eb), ("decode", da, db)):
+                if a[0] > b[0]:
+                    verdicts.append("%s x %d, %s, %s: (a) %.3f ms is SLOWER than (b) %.3f ms" % (name, c, what, way, a[0], b[0]))
+            del holder, holder_back, view, view_back, want
+            torch.cuda.empty_cache()
+        # ---- windows of the mosaic into packed pixels
+        rc, offs, sizes, used = api.encode_raster_tiles_device_depth(codec, hwc, None, e, tile, arena_a)
+        assert rc == 0
+
+        def whole():
+            assert api.decode_raster_tiles_device_depth(codec, arena_a, offs, sizes, hwc_back, None, tile) == 0
+
+        whole()
+        torch.cuda.synchronize()
+        ref = hwc_back.clone()
+        say("  window (row0, col0, rows x cols)        tiles   window decode        whole decode + copy of the slice")
+        points = []
+        for wname, side in (("one tile", TILE), ("1/16", size // 4), ("1/4", size // 2), ("whole", size)):
+            r0 = c0 = 0 if side == size else TILE * 3
+            out = torch.zeros((side, side, c), dtype=hwc.dtype, device="cuda")
+            touched = len(api.raster_window_tiles(size, size, tile, (r0, c0, side, side)))
+
+            def win():
+                assert api.decode_raster_window_device_depth(codec, arena_a, offs, sizes, (size, size), tile, (r0, c0), out, None) == 0
+
+            def old():
+                assert api.decode_raster_tiles_device_depth(codec, arena_a, offs, sizes, hwc_back, None, tile) == 0
+                out.copy_(hwc_back[r0:r0 + side, c0:c0 + side])
+
+            k0 = codec.raster_tiles_counters()
+            win()
+            torch.cuda.synchronize()
+            assert [int(y - x) for x, y in zip(k0, codec.raster_tiles_counters())] == [0, 0, touched, 0]
+            assert torch.equal(out.view(torch.uint8), ref[r0:r0 + side, c0:c0 + side].contiguous().view(torch.uint8)), "the window is not the slice"
+            t_win, t_old = timed_pair(torch, win, old)
+            points.append((touched, t_win[0]))
+            say("  %-8s (%4d, %4d, %4d x %4d)   %5d   %8.3f [%6.3f]   %8.3f [%6.3f]" % ((wname, r0, c0, side, side, touched) + t_win + t_old))
+            if 2 * touched < n and t_win[0] > t_old[0]:
+                verdicts.append("%s x %d, window %s: %.3f ms is SLOWER than the whole decode and a slice, %.3f ms" % (name, c, wname, t_win[0], t_old[0]))
+            del out
+        mx, my = sum(p[0] for p in points) / len(points), sum(p[1] for p in points) / len(points)
+        slope = sum((p[0] - mx) * (p[1] - my) for p in points) / sum((p[0] - mx) ** 2 for p in points)
+        say("  window decode ~ %.3f ms + %.3f ms per thousand tiles (least squares through the four windows)" % (my - slope * mx, 1000 * slope))
+        del hwc, hwc_back, arena_a, arena_b, ref
+        torch.cuda.empty_cache()
+    say("expectation: (a) no slower than (b), a window of under half the tiles faster than the whole decode and a slice -- %s"
+        % ("met everywhere" if not verdicts else "NOT met:"))
+    for v in verdicts:
+        say("  " + v)
+    codec.close()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return 0
+
+
+def timed_pair(torch, fa, fb, reps=REPS, warm=3):
+    """fa and fb alternating inside one loop -> ((median, interquartile range) of fa, of fb)"""
+    for _ in range(warm):
+        fa()
+        fb()
+    ms = ([], [])
+    for _ in range(reps):
+        for k, fn in enumerate((fa, fb)):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            ms[k].append(a.elapsed_time(b))
+    out = []
+    for m in ms:
+        q = statistics.quantiles(m, n=4)
+        out.append((statistics.median(m), q[2] - q[0]))
+    return out[0], out[1]
+
+
 def timed_on(torch, fn, reps=REPS, warm=3):
     for _ in range(warm):
         fn()
@@ -278,4 +452,6 @@ def main():
 
 
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["depth"]:
+        sys.exit(depth(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "raster_depth_layouts_time.txt")))
     sys.exit(interleaved() if sys.argv[1:] == ["interleaved"] else window() if sys.argv[1:] == ["window"] else main())
