@@ -13,11 +13,14 @@ from .api import (  # noqa: F401
     decode,
     decode_device,
     decode_raster_tiles_device_depth_strided,
+    decode_raster_tiles_device_nodata,
     decode_raster_window_device_depth,
+    decode_raster_window_device_nodata,
     encode,
     encode_device,
     encode_raster_tile_range_device_depth,
     encode_raster_tiles_device_depth_strided,
+    encode_raster_tiles_device_nodata,
     getLercBlobInfo,
     getLercDataRanges,
     library_path,
@@ -26,4 +29,5 @@ from .api import (  # noqa: F401
 
 __all__ = ["encode", "decode", "computeCompressedSize", "getLercBlobInfo", "getLercDataRanges", "encode_device",
            "decode_device", "load_library", "library_path", "build_info", "LercError", "encode_raster_tiles_device_depth_strided",
-           "decode_raster_tiles_device_depth_strided", "encode_raster_tile_range_device_depth", "decode_raster_window_device_depth"]
+           "decode_raster_tiles_device_depth_strided", "encode_raster_tile_range_device_depth", "decode_raster_window_device_depth",
+           "encode_raster_tiles_device_nodata", "decode_raster_window_device_nodata", "decode_raster_tiles_device_nodata"]

@@ -144,6 +144,18 @@ def load_library():
                                                                    ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_void_p,
                                                                    ct.c_ulonglong, ct.c_ulonglong, ct.c_ulonglong, ct.c_int, ct.c_void_p,
                                                                    ct.c_ulonglong]
+    # (the noData raster calls, include/lerc_amd_nodata.h: the same rule)
+    have_nodata = not os.environ.get("LERC_AMD_LIBRARY") or hasattr(lib, "lerc_amd_encode_raster_tiles_device_nodata")
+    if have_nodata:
+        lib.lerc_amd_encode_raster_tiles_device_nodata.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int, ct.c_int, ct.c_ulonglong,
+                                                                   ct.c_ulonglong, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int,
+                                                                   ct.c_double, ct.c_double, ct.c_void_p, ct.c_ulonglong, ct.c_ulonglong, ct.c_void_p,
+                                                                   ct.c_void_p, ct.c_void_p]
+        lib.lerc_amd_decode_raster_window_device_nodata.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_uint, ct.c_int, ct.c_int,
+                                                                    ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_void_p,
+                                                                    ct.c_ulonglong, ct.c_ulonglong, ct.c_double, ct.c_void_p, ct.c_ulonglong]
+        for n in ("lerc_amd_encode_raster_tiles_device_nodata", "lerc_amd_decode_raster_window_device_nodata"):
+            getattr(lib, n).restype = ct.c_uint
     lib.lerc_amd_tile_batch_counters.argtypes = [ct.c_void_p, ct.POINTER(ct.c_ulonglong)]
     lib.lerc_amd_tile_batch_counters.restype = None
     lib.lerc_amd_encode_device_async.argtypes = [ct.c_void_p] + enc + [ct.c_void_p, ct.c_uint, u32p]
@@ -521,6 +533,32 @@ class DeviceCodec:
                                                              int(row_pitch), int(band_pitch), 1 if d_valid else 0, d_valid or None,
                                                              int(mask_row_pitch))
 
+    def encode_raster_tiles_nodata(self, d_raster, dt_code, n_cols, n_rows, pixel_pitch, row_pitch, tile, tile_range, no_data, max_z_err, d_arena,
+                                   arena_cap, slot_bytes=0):
+        """one band whose validity is the value no_data (include/lerc_amd_nodata.h); tile_range = (tileRow0, tileCol0, nTileRows, nTileCols),
+        (0, 0, -1, -1): the whole grid; offsets / sizes are the full grid's tables, zero outside the range"""
+        n_tiles = len(raster_tile_grid(n_rows, n_cols, tile))
+        offsets = np.zeros(n_tiles, np.uint64)
+        sizes = np.zeros(n_tiles, np.uint32)
+        used = ct.c_ulonglong(0)
+        rc = self.lib.lerc_amd_encode_raster_tiles_device_nodata(self.h, d_raster, dt_code, n_cols, n_rows, int(pixel_pitch), int(row_pitch),
+                                                                 int(tile[1]), int(tile[0]), int(tile_range[1]), int(tile_range[0]),
+                                                                 int(tile_range[3]), int(tile_range[2]), float(no_data), float(max_z_err), d_arena,
+                                                                 int(arena_cap), int(slot_bytes), offsets.ctypes.data, sizes.ctypes.data,
+                                                                 ct.byref(used))
+        return rc, offsets, sizes, int(used.value)
+
+    def decode_raster_window_nodata(self, d_arena, offsets, sizes, dt_code, n_cols, n_rows, tile, window_rect, d_window, pixel_pitch, row_pitch,
+                                    no_data, d_valid, mask_row_pitch):
+        """decode_raster_window for one band with no_data written at invalid pixels; d_valid: the window's valid bytes, or 0 for none"""
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        sizes = np.ascontiguousarray(sizes, np.uint32)
+        assert len(offsets) == len(sizes) == len(raster_tile_grid(n_rows, n_cols, tile))
+        return self.lib.lerc_amd_decode_raster_window_device_nodata(self.h, d_arena, offsets.ctypes.data, sizes.ctypes.data, dt_code, n_cols,
+                                                                    n_rows, int(tile[1]), int(tile[0]), int(window_rect[1]), int(window_rect[0]),
+                                                                    int(window_rect[3]), int(window_rect[2]), d_window, int(pixel_pitch),
+                                                                    int(row_pitch), float(no_data), d_valid or None, int(mask_row_pitch))
+
     def raster_tile_grid(self, n_rows, n_cols, tile):
         return raster_tile_grid(n_rows, n_cols, tile)
 
@@ -896,3 +934,45 @@ def decode_raster_window_device(codec, arena, offsets, sizes, raster_shape, tile
     return codec.decode_raster_window(arena.data_ptr(), offsets, sizes, _torch_dt_code(out), int(raster_shape[1]), int(raster_shape[0]), n_bands,
                                       tile, (int(window[0]), int(window[1]), rows, cols), out.data_ptr(), pixel_pitch, row_pitch, band_pitch,
                                       d_valid, mask_pitch)
+
+
+def _nodata_view(t):
+    """-> (nRows, nCols, pixelPitch, rowPitch) of an [H, W] tensor with any strides: a pitched raster, a view into a larger tensor, one
+    channel of an interleaved image (hwc[..., k]); what the library does not take comes back as status 2"""
+    assert t.dim() == 2, "an [H, W] tensor"
+    n_rows, n_cols = int(t.shape[0]), int(t.shape[1])
+    pixel_pitch = int(t.stride(1)) if n_cols > 1 else 1
+    row_pitch = int(t.stride(0)) if n_rows > 1 else (n_cols - 1) * pixel_pitch + 1
+    return n_rows, n_cols, pixel_pitch, row_pitch
+
+
+def encode_raster_tiles_device_nodata(codec, raster, no_data, max_z_err, tile, arena, slot_bytes=0, tile_range=None):
+    """encode_raster_tiles_device for an [H, W] raster (any strides) whose validity is a VALUE (include/lerc_amd_nodata.h): a pixel is
+    invalid when it equals no_data by the type's own ==, or is a NaN where no_data is NaN; no_data must be an element of the raster's
+    type (else status 2).  Every blob is what the masked call makes of the raster and the mask `raster != no_data` (`~isnan`), which is
+    made in the staging pass and never exists as a tensor; values at invalid pixels, NaN included, never influence a byte.
+    tile_range = (tileRow0, tileCol0, nTileRows, nTileCols) or None for the whole grid, as encode_raster_tile_range_device.
+    -> (status, offsets uint64[nTiles], sizes uint32[nTiles], arena bytes used): full-grid tables, zero outside the range"""
+    n_rows, n_cols, pixel_pitch, row_pitch = _nodata_view(raster)
+    ty0, tx0, nty, ntx = (0, 0, -1, -1) if tile_range is None else (int(v) for v in tile_range)
+    return codec.encode_raster_tiles_nodata(raster.data_ptr(), _torch_dt_code(raster), n_cols, n_rows, pixel_pitch, row_pitch, tile,
+                                            (ty0, tx0, nty, ntx), no_data, max_z_err, arena.data_ptr(), arena.numel(), slot_bytes)
+
+
+def decode_raster_window_device_nodata(codec, arena, offsets, sizes, raster_shape, tile, window, out, no_data, valid_out=None):
+    """a window of a mosaic as decode_raster_window_device, into an [h, w] tensor with any strides: a valid pixel holds what that call
+    writes, an invalid one no_data (a quiet NaN where no_data is NaN), and so does the part of a tile whose blob fails (the first such
+    status comes back).  valid_out: uint8 [h, w] with dense rows, written 1 / 0, or None.  window = (row0, col0)."""
+    rows, cols, pixel_pitch, row_pitch = _nodata_view(out)
+    d_valid, mask_pitch = 0, 0
+    if valid_out is not None:
+        assert valid_out.element_size() == 1 and tuple(valid_out.shape) == (rows, cols) and valid_out.stride(-1) == 1, "valid_out: uint8 [h, w] with dense rows"
+        d_valid, mask_pitch = valid_out.data_ptr(), (int(valid_out.stride(0)) if rows > 1 else cols)
+    return codec.decode_raster_window_nodata(arena.data_ptr(), offsets, sizes, _torch_dt_code(out), int(raster_shape[1]), int(raster_shape[0]), tile,
+                                             (int(window[0]), int(window[1]), rows, cols), out.data_ptr(), pixel_pitch, row_pitch, no_data, d_valid,
+                                             mask_pitch)
+
+
+def decode_raster_tiles_device_nodata(codec, arena, offsets, sizes, out, no_data, tile, valid_out=None):
+    """the whole raster back: decode_raster_window_device_nodata with the window that covers everything"""
+    return decode_raster_window_device_nodata(codec, arena, offsets, sizes, tuple(out.shape), tile, (0, 0), out, no_data, valid_out)

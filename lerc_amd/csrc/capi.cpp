@@ -5,6 +5,7 @@
 #include "../../include/lerc_amd.h"
 #include "../../include/lerc_amd_device.h"
 #include "../../include/lerc_amd_depth.h"
+#include "../../include/lerc_amd_nodata.h"
 #include "codec.h"
 
 #include <sys/syscall.h>
@@ -978,6 +979,38 @@ lerc_status lerc_amd_decode_raster_window_device(lerc_amd_context* h, const unsi
   win.col0 = winCol0; win.row0 = winRow0; win.cols = winCols; win.rows = winRows;
   return decodeRasterWindowDevice(h->ctx, rasterTilesRequest(dWindow, dataType, nCols, nRows, nBands, strided(pixelPitch, rowPitch, bandPitch, maskRowPitch),
                                                              tileCols, tileRows, nMasks, dValidBytes, dArena, offsets, sizes), win);
+}
+
+// ---- validity by a noData value (lerc_amd_nodata.h): one band staged with a mask of the cut's making; the value must be an element of
+// the type, which is asked with the other arguments, before the size
+lerc_status lerc_amd_encode_raster_tiles_device_nodata(lerc_amd_context* h, const void* dRaster, unsigned int dataType, int nCols, int nRows,
+  unsigned long long pixelPitch, unsigned long long rowPitch, int tileCols, int tileRows, int tileCol0, int tileRow0, int nTileCols, int nTileRows,
+  double noData, double maxZErr, unsigned char* dArena, unsigned long long arenaCapacity, unsigned long long slotBytes, unsigned long long* offsets,
+  unsigned int* sizes, unsigned long long* arenaUsed)
+{
+  if (arenaUsed) *arenaUsed = 0;
+  const bool whole = tileCol0 == 0 && tileRow0 == 0 && nTileCols == -1 && nTileRows == -1;
+  const bool rangeOk = whole || !(tileCol0 < 0 || tileRow0 < 0 || nTileCols <= 0 || nTileRows <= 0);    // (inside the grid: the driver's check)
+  if (const lerc_status bad = rasterTilesArgs(h, dataType, nCols, nRows, tileCols, tileRows, rangeOk && rasterNoDataOk((int)dataType, noData))) return bad;
+  RasterTilesRequest rq = rasterTilesRequest(dRaster, dataType, nCols, nRows, 1, strided(pixelPitch, rowPitch, 0, 0), tileCols, tileRows, 1, nullptr, dArena,
+                                             offsets, sizes, maxZErr, arenaCapacity, slotBytes);
+  rq.tileCol0 = tileCol0; rq.tileRow0 = tileRow0; rq.nTileCols = nTileCols; rq.nTileRows = nTileRows;
+  rq.useNoData = true; rq.noData = noData;
+  return encodeRasterTiles(h, rq, arenaUsed);
+}
+
+lerc_status lerc_amd_decode_raster_window_device_nodata(lerc_amd_context* h, const unsigned char* dArena, const unsigned long long* offsets,
+  const unsigned int* sizes, unsigned int dataType, int nCols, int nRows, int tileCols, int tileRows, int winCol0, int winRow0, int winCols,
+  int winRows, void* dWindow, unsigned long long pixelPitch, unsigned long long rowPitch, double noData, unsigned char* dValidBytes,
+  unsigned long long maskRowPitch)
+{
+  if (const lerc_status bad = rasterTilesArgs(h, dataType, nCols, nRows, tileCols, tileRows, rasterNoDataOk((int)dataType, noData))) return bad;
+  RasterWindow win;
+  win.col0 = winCol0; win.row0 = winRow0; win.cols = winCols; win.rows = winRows;
+  RasterTilesRequest rq = rasterTilesRequest(dWindow, dataType, nCols, nRows, 1, strided(pixelPitch, rowPitch, 0, maskRowPitch), tileCols, tileRows, 1,
+                                             dValidBytes, dArena, offsets, sizes);
+  rq.useNoData = true; rq.noData = noData;
+  return decodeRasterWindowDevice(h->ctx, rq, win);
 }
 
 void lerc_amd_raster_tiles_counters(lerc_amd_context* h, unsigned long long out[4])

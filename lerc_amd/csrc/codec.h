@@ -348,7 +348,14 @@ struct RasterTilesRequest
   // (pixelPitch 1) --; every tile is one blob with the header's nDepth.  nDepth 1: depthPitch is not looked at
   int nDepth = 1;
   u64 depthPitch = 1;
+  // validity by value (the _nodata entry points, lerc_amd_nodata.h): one band, nDepth 1, staged as nMasks 1 -- the mask is made by the
+  // cut (a pixel is invalid when it equals (T)noData, or is a NaN where noData is NaN) and consumed by the paste, which writes noData
+  // at invalid pixels; dValidBytes: encode NULL, decode the window's valid bytes or NULL.  noData is exactly representable in the type
+  bool useNoData = false;
+  double noData = 0;
 };
+// whether noData is an element of type dt: (double)(T)noData == noData, or NaN for the two float types
+bool rasterNoDataOk(int dt, double noData);
 u32 encodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq, u64& arenaUsed);
 u32 decodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq);
 // A window of the mosaic, in raster coordinates.  decodeRasterWindowDevice: rq describes the mosaic (nCols, nRows, the tile sizes, the

@@ -23,11 +23,20 @@
 // encodeTilesDeviceDepth / decodeTilesDeviceDepth; it differs in how it is cut and pasted, and in nothing else, ranges and windows
 // included.  Packed pixels are runs of elements: the band kernels with the column counts scaled by nDepth (a window's too).  Gapped
 // pixels, planes and lines go through k_rtd_cut / k_rtd_paste (raster_tiles_depth.hip), whose paste is clipped to a window always.
+//
+// A NODATA raster (useNoData, lerc_amd_nodata.h) says which pixels are invalid with a value, not with a mask.  It is one band staged as
+// nMasks 1: k_rtn_cut (raster_nodata.hip) stores the staged mask beside the staged tiles in the one launch that cuts them, the chunk
+// goes to encodeTilesDeviceMasked / decodeTilesDeviceMasked untouched, and k_rtn_paste writes noData wherever the decoded valid byte is
+// 0 (a failed tile: everywhere) and the window's valid bytes where the caller wants them.  It is never coded where it lies, and the
+// way back is a window always (the whole raster: the window that covers it).
 #include "codec.h"
 #include "raster_tiles.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
+#include <cstring>
+#include <limits>
 
 namespace lerc {
 
@@ -86,6 +95,25 @@ RtDepthLayout rtDepthLayout(const RasterTilesRequest& rq, u64 nCols, u64 nRows)
   return kRtdNone;
 }
 
+// noData as an element of type dt: its raw bits, a quiet NaN where it is NaN
+u64 rtNoDataBits(int dt, double noData)
+{
+  if (dt == DT_Float) { const float f = noData != noData ? std::numeric_limits<float>::quiet_NaN() : (float)noData; u32 b; memcpy(&b, &f, 4); return b; }
+  if (dt == DT_Double) { const double d = noData != noData ? std::numeric_limits<double>::quiet_NaN() : noData; u64 b; memcpy(&b, &d, 8); return b; }
+  const long long v = (long long)noData;    // (an integer within the type's range: rtNoDataOk)
+  return (u64)v & (dtSize(dt) == 1 ? 0xFFull : dtSize(dt) == 2 ? 0xFFFFull : 0xFFFFFFFFull);
+}
+
+// (double)(T)noData == noData, or NaN for the two float types (capi.cpp asks the same before the size checks)
+bool rtNoDataOk(int dt, double noData)
+{
+  if (noData != noData) return dt == DT_Float || dt == DT_Double;
+  if (dt == DT_Double) return true;
+  if (dt == DT_Float) return std::isinf(noData) || (std::fabs(noData) <= (double)std::numeric_limits<float>::max() && (double)(float)noData == noData);
+  static const double lo[6] = { -128.0, 0.0, -32768.0, 0.0, -2147483648.0, 0.0 }, hi[6] = { 127.0, 255.0, 32767.0, 65535.0, 2147483647.0, 4294967295.0 };
+  return dt >= DT_Char && dt <= DT_UInt && noData >= lo[dt] && noData <= hi[dt] && std::trunc(noData) == noData;
+}
+
 // (win: the buffer at dRaster and the mask hold that window of the raster, and the layout's rules apply to its size)
 bool rtArgsOk(const RasterTilesRequest& rq, bool encode, const RasterWindow* win = nullptr)
 {
@@ -93,9 +121,15 @@ bool rtArgsOk(const RasterTilesRequest& rq, bool encode, const RasterWindow* win
     return false;
   const u64 bufCols = (u64)(win ? win->cols : rq.nCols), bufRows = (u64)(win ? win->rows : rq.nRows);
   if (!rq.dRaster || !rq.dArena || !rq.hOffsets || !rq.hSizes || rq.dt < 0 || rq.dt > DT_Double || rq.nCols <= 0 || rq.nRows <= 0 || rq.nBands <= 0
-    || rq.tileCols <= 0 || rq.tileRows <= 0 || (rq.nMasks != 0 && rq.nMasks != 1) || (rq.nMasks == 0) != (rq.dValidBytes == nullptr))
+    || rq.tileCols <= 0 || rq.tileRows <= 0 || (rq.nMasks != 0 && rq.nMasks != 1))
     return false;
-  if (rq.nMasks && rq.maskRowPitch < bufCols) return false;
+  if (rq.useNoData)
+  {
+    // (validity by value: one band staged with a mask of the cut's making; the caller has none on the way in and may want one back)
+    if (rq.nMasks != 1 || rq.nBands != 1 || rq.nDepth != 1 || !rq.anyLayout || (encode && rq.dValidBytes) || !rtNoDataOk(rq.dt, rq.noData)) return false;
+    if (rq.dValidBytes && rq.maskRowPitch < bufCols) return false;
+  }
+  else if ((rq.nMasks == 0) != (rq.dValidBytes == nullptr) || (rq.nMasks && rq.maskRowPitch < bufCols)) return false;
   // (depth tiles: one band in a layout of its own; a tile's row of elements is counted in 32 bits)
   if (rq.nDepth < 1 || (rq.nDepth > 1 && (rq.nBands != 1 || (u64)std::min(rq.tileCols, rq.nCols) * (u64)rq.nDepth > 0x7FFFFFFFull)))
     return false;
@@ -126,7 +160,7 @@ RtGrid rtGrid(const RasterTilesRequest& rq)
   if (fullY && remC) add(0, fullX, fullY, 1, tr, remC);
   if (remR && fullX) add(fullY, 0, 1, fullX, remR, tc);
   if (remR && remC) add(fullY, fullX, 1, 1, remR, remC);
-  g.inPlace = rq.pixelPitch == 1 && rq.nBands == 1 && rq.nDepth == 1 && tc >= nC && rq.rowPitch == (u64)nC && (!rq.nMasks || rq.maskRowPitch == (u64)nC);
+  g.inPlace = !rq.useNoData && rq.pixelPitch == 1 && rq.nBands == 1 && rq.nDepth == 1 && tc >= nC && rq.rowPitch == (u64)nC && (!rq.nMasks || rq.maskRowPitch == (u64)nC);
   return g;
 }
 
@@ -271,8 +305,10 @@ u32 encodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq, u64& are
       else
       {
         (void)hipGetLastError();
-        rtCutData(rq, k, k0, n, stage, eb, st);
-        if (rq.nMasks) launchRasterCut(rq.dValidBytes, stage + rtMaskAt(p, n), rtChunk(rq, k, k0, n, true), 1, st);
+        if (rq.useNoData)
+          launchRasterCutNoData(rq.dRaster, stage, stage + rtMaskAt(p, n), RtnCut{ rtChunk(rq, k, k0, n, false), rq.pixelPitch, rtNoDataBits(rq.dt, rq.noData), rq.noData != rq.noData ? 1u : 0u }, rq.dt, st);
+        else rtCutData(rq, k, k0, n, stage, eb, st);
+        if (rq.nMasks && !rq.useNoData) launchRasterCut(rq.dValidBytes, stage + rtMaskAt(p, n), rtChunk(rq, k, k0, n, true), 1, st);
         if (hipGetLastError() != hipSuccess) { ctx.lastError = "lerc_amd: the raster cut kernel could not be launched"; return kFailed; }
         sub.dData = stage;
         sub.dValidBytes = rq.nMasks ? stage + rtMaskAt(p, n) : nullptr;
@@ -380,9 +416,14 @@ static u32 rtDecode(Context& ctx, const RasterTilesRequest& rq, const RasterWind
       {
         hipStream_t st = ctx.activeStream();
         (void)hipGetLastError();
-        rtPasteData(rq, k, k0, n, stage, eb, st, win);
-        if (rq.nMasks && win) launchWindowPaste(stage + rtMaskAt(p, n), rq.dValidBytes, RwChunk{ rtChunk(rq, k, k0, n, true), 1, (u32)win->row0, (u32)win->col0, (u32)win->rows, (u32)win->cols }, 1, st);
-        else if (rq.nMasks) launchRasterPaste(stage + rtMaskAt(p, n), rq.dValidBytes, rtChunk(rq, k, k0, n, true), 1, st);
+        if (rq.useNoData)    // (a window always: decodeRasterWindowDevice)
+          launchWindowPasteNoData(stage, stage + rtMaskAt(p, n), rq.dRaster, rq.dValidBytes,
+                                  RtnPaste{ RwChunk{ rtChunk(rq, k, k0, n, false), rq.pixelPitch, (u32)win->row0, (u32)win->col0, (u32)win->rows, (u32)win->cols },
+                                            rtNoDataBits(rq.dt, rq.noData), rq.maskRowPitch }, eb, st);
+        else rtPasteData(rq, k, k0, n, stage, eb, st, win);
+        const bool pasteMask = rq.nMasks && !rq.useNoData;    // (noData: the valid bytes went with the pixels)
+        if (pasteMask && win) launchWindowPaste(stage + rtMaskAt(p, n), rq.dValidBytes, RwChunk{ rtChunk(rq, k, k0, n, true), 1, (u32)win->row0, (u32)win->col0, (u32)win->rows, (u32)win->cols }, 1, st);
+        else if (pasteMask) launchRasterPaste(stage + rtMaskAt(p, n), rq.dValidBytes, rtChunk(rq, k, k0, n, true), 1, st);
         if (hipGetLastError() != hipSuccess) { ctx.lastError = "lerc_amd: the raster paste kernel could not be launched"; return kFailed; }
       }
     }
@@ -391,7 +432,9 @@ static u32 rtDecode(Context& ctx, const RasterTilesRequest& rq, const RasterWind
   return firstError;
 }
 
-u32 decodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq) { return rtDecode(ctx, rq, nullptr); }
+u32 decodeRasterTilesDevice(Context& ctx, const RasterTilesRequest& rq) { return rq.useNoData ? (u32)kWrongParam : rtDecode(ctx, rq, nullptr); }
+
+bool rasterNoDataOk(int dt, double noData) { return rtNoDataOk(dt, noData); }
 
 u32 decodeRasterWindowDevice(Context& ctx, const RasterTilesRequest& rq, const RasterWindow& win)
 {

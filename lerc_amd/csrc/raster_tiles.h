@@ -84,4 +84,27 @@ struct RtdChunk
 void launchRasterCutDepth(const void* dRaster, void* dStage, const RtdChunk& cd, u32 elemBytes, hipStream_t st);
 void launchRasterPasteDepth(const void* dStage, void* dRaster, const RtdChunk& cd, u32 elemBytes, hipStream_t st);
 
+// ---- noData rasters (raster_nodata.hip; include/lerc_amd_nodata.h): one band, element (i, j) at i * rowPitch + j * pixelPitch, whose
+// validity is a VALUE.  The cut stores the staged tiles [n][r][c] and, beside them, the staged mask [n][r][c] (1: the element is not
+// the noData value) in one launch; the paste is the window's clipped one with select(staged valid byte, staged element, fill) on the
+// way, and writes the window's valid bytes [winRows][maskRowPitch] too where dWindowMask is not NULL.  ch.nBands is 1, ch.bandPitch is
+// not used; pixelPitch 1 moves 16-byte vectors, pixelPitch >= 2 (one channel of an interleaved image) a lane an element.
+struct RtnCut
+{
+  RtChunk ch;
+  u64 pixelPitch;
+  u64 ndBits;       // (T)noData as raw bits of the element's type
+  u32 ndIsNaN;      // float / double only: an element is invalid when it is a NaN (ndBits is not looked at)
+};
+struct RtnPaste
+{
+  RwChunk cw;
+  u64 fillBits;     // what an invalid pixel gets, raw bits of the element's type
+  u64 maskRowPitch;
+};
+
+// dt: the raster's data type (the compare is by `==` / `v != v` for the float types, on the raw pattern for integers).  One launch.
+void launchRasterCutNoData(const void* dRaster, void* dStage, u8* dStageMask, const RtnCut& cn, int dt, hipStream_t st);
+void launchWindowPasteNoData(const void* dStage, const u8* dStageMask, void* dWindow, u8* dWindowMask, const RtnPaste& pn, u32 elemBytes, hipStream_t st);
+
 }    // namespace lerc

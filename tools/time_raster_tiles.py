@@ -50,6 +50,18 @@ the numbers are recorded in DESIGN.md 8.3 and profiles/raster_window_time.txt.
 (a) and (b) alternate inside one loop of REPS; the arenas of (a) and (b) are compared byte for byte before anything is timed, every
 window against the slice.  No pass mark: the report says where (a) is slower than (b) or a window slower than the whole decode.  It
 goes to FILE (default profiles/raster_depth_layouts_time.txt) and to stdout; the table is recorded in DESIGN.md 8.4.
+
+`python tools/time_raster_tiles.py nodata [FILE]` times the noData raster calls (include/lerc_amd_nodata.h) on 8192 x 8192 float32 at
+0.01 with NaN holes and 16384 x 16384 uint16 lossless with 65535 for no data, tiles of 256 x 256, about 10 % holes, both ways:
+
+  (a) lerc_amd_encode_raster_tiles_device_nodata / lerc_amd_decode_raster_window_device_nodata (the whole raster as the window)
+  (b) what a caller did before: valid = (raster != noData) (or ~isnan) as a uint8 tensor plus the masked strided encode; back, the
+      masked decode plus a fill of noData where the valid bytes say 0 -- the torch operations inside the timed region
+  (c) the float raster with its NaN holes through the existing call without a mask (encode only, fewer runs: its tiles go one by one)
+
+(a) and (b) alternate inside one loop of REPS; their arenas are compared byte for byte and their pixels bit for bit (NaN by isnan)
+before anything is timed.  No pass mark: the report says where (a) is slower than (b).  It goes to FILE (default
+profiles/raster_nodata_time.txt) and to stdout; the table is recorded in DESIGN.md 8.3.
 """
 import os
 import statistics
@@ -325,6 +337,139 @@ def depth(out_path):
     return 0
 
 
+def nodata(out_path):
+    """the noData raster calls (include/lerc_amd_nodata.h) against what a caller did before, see the module's text"""
+    import numpy as np
+    import torch
+    from lerc_amd import api, synth
+    assert torch.cuda.is_available(), "needs a GPU"
+    tile = (TILE, TILE)
+    codec = api.DeviceCodec(torch.cuda.current_stream().cuda_stream)
+    lines = []
+
+    def say(text):
+        lines.append(text)
+        print(text, flush=True)
+
+    say("noData raster calls against a torch-made mask + the masked calls -- %s; tiles of %d x %d, packed arenas, about 10 %% holes; the ways "
+        "alternating, median [interquartile range] of %d, ms" % (torch.cuda.get_device_name(0), TILE, TILE, REPS))
+    slower = []
+    for name, size, e in (("float32", 8192, E), ("uint16", 16384, 0.0)):
+        terrain = synth.c2_float32(8192, 8192, device="cuda:0")
+        if size > 8192:
+            terrain = terrain.repeat(size // 8192, size // 8192) + torch.arange(size, device="cuda", dtype=torch.float32)[:, None] * 0.01
+        yy = torch.arange(size, device="cuda", dtype=torch.float32)[:, None]
+        xx = torch.arange(size, device="cuda", dtype=torch.float32)[None, :]
+        f = torch.sin(yy / 97.0) * torch.cos(xx / 131.0) + 0.5 * torch.sin(yy / 41.0 + xx / 59.0)
+        holes = f > torch.quantile(f[::16, ::16].reshape(-1), 0.9)
+        del f, yy, xx
+        if name == "float32":
+            raster, nd = terrain.clone(), float("nan")
+            raster[holes] = nd
+            bits, nd_bits = raster, None
+        else:
+            lo, hi = float(terrain.min()), float(terrain.max())
+            raster, nd = ((terrain - lo) * (60000.0 / (hi - lo))).to(torch.int32).to(torch.uint16), 65535.0
+            bits, nd_bits = raster.view(torch.int16), -1    # (torch compares and fills 16-bit patterns as int16: a view, no copy)
+            bits[holes] = nd_bits
+        del terrain
+        share = float(holes.float().mean())
+        del holes
+        item = raster.element_size()
+        n = len(api.raster_tile_grid(size, size, tile))
+        cap = n * (TILE * TILE * item + TILE * TILE // 4 + 2048)
+        arena_a = torch.zeros(cap, dtype=torch.uint8, device="cuda")
+        arena_b = torch.zeros(cap, dtype=torch.uint8, device="cuda")
+        back_a, back_b = torch.zeros_like(raster), torch.zeros_like(raster)
+        valid_back = torch.zeros((size, size), dtype=torch.uint8, device="cuda")
+        say("%s, %d x %d (%.0f MiB), maxZErr %g, %d tiles, %.1f %% holes, noData %s" % (name, size, size, raster.numel() * item / 2 ** 20, e, n, 100 * share, nd))
+        state = {}
+
+        def enc_a():
+            rc, offs, sizes, used = api.encode_raster_tiles_device_nodata(codec, raster, nd, e, tile, arena_a)
+            assert rc == 0, (rc, codec.last_error())
+            state["a"] = (offs, sizes, used)
+
+        def enc_b():
+            valid = (~torch.isnan(raster) if nd_bits is None else bits != nd_bits).to(torch.uint8)
+            rc, offs, sizes, used = api.encode_raster_tile_range_device(codec, raster, valid, e, tile, (0, 0, size // TILE, size // TILE), arena_b)
+            assert rc == 0, (rc, codec.last_error())
+            state["b"] = (offs, sizes, used)
+
+        def enc_c():
+            rc, offs, sizes, used = api.encode_raster_tile_range_device(codec, raster, None, e, tile, (0, 0, size // TILE, size // TILE), arena_b)
+            state["c"] = rc
+
+        def dec_a():
+            assert api.decode_raster_tiles_device_nodata(codec, arena_a, state["a"][0], state["a"][1], back_a, nd, tile) == 0
+
+        def dec_b():
+            assert api.decode_raster_tiles_device(codec, arena_b, state["b"][0], state["b"][1], back_b, valid_back, tile) == 0
+            (back_b if nd_bits is None else back_b.view(torch.int16)).masked_fill_(valid_back == 0, nd if nd_bits is None else nd_bits)
+
+        # blobs and pixels compared before anything is timed
+        c0 = codec.tile_batch_counters()
+        enc_a()
+        c1 = codec.tile_batch_counters()
+        enc_b()
+        assert np.array_equal(state["a"][0], state["b"][0]) and np.array_equal(state["a"][1], state["b"][1]) and state["a"][2] == state["b"][2]
+        assert torch.equal(arena_a[:state["a"][2]], arena_b[:state["b"][2]]), "the blobs of (a) and (b) differ"
+        dec_a()
+        dec_b()
+        torch.cuda.synchronize()
+        if nd_bits is None:
+            assert torch.equal(torch.isnan(back_a), torch.isnan(back_b)) and torch.equal(torch.isnan(back_a), torch.isnan(raster))
+            assert torch.equal(torch.nan_to_num(back_a), torch.nan_to_num(back_b)), "the pixels of (a) and (b) differ"
+            assert float((torch.nan_to_num(back_a) - torch.nan_to_num(raster)).abs().max()) <= e + 1e-4    # (float32 rounding beside the bound)
+        else:
+            assert torch.equal(back_a.view(torch.int16), back_b.view(torch.int16)) and torch.equal(back_a.view(torch.int16), bits)
+        say("  (a) tile batch counters of one encode: %d tiles in the batch's launches, %d one by one; %d blob bytes"
+            % (c1[0] - c0[0], c1[1] - c0[1], state["a"][2]))
+        ways = [("(a) the noData calls", enc_a, dec_a), ("(b) torch mask + masked calls, torch fill", enc_b, dec_b)]
+        res = timed_ways(torch, [w[1] for w in ways]), timed_ways(torch, [w[2] for w in ways])
+        for k, w in enumerate(ways):
+            say("  %-44s encode %8.3f [%6.3f]   decode %8.3f [%6.3f]" % (w[0], res[0][k][0], res[0][k][1], res[1][k][0], res[1][k][1]))
+        for which, r in zip(("encode", "decode"), res):
+            say("  %s: (a) / (b) = %.3f" % (which, r[0][0] / r[1][0]))
+            if r[0][0] > r[1][0]:
+                slower.append("%s %s: (a) %.3f ms is slower than (b) %.3f ms" % (name, which, r[0][0], r[1][0]))
+        if nd_bits is None:
+            c0 = codec.tile_batch_counters()
+            enc_c()
+            c1 = codec.tile_batch_counters()
+            m = timed_ways(torch, [enc_c], reps=max(3, REPS // 4), warm=1)[0]
+            say("  %-44s encode %8.3f [%6.3f]   (status %d; %d tiles in the batch's launches, %d one by one; %d runs)"
+                % ("(c) NaN holes, the unmasked call", m[0], m[1], state["c"], c1[0] - c0[0], c1[1] - c0[1], max(3, REPS // 4)))
+        del raster, bits, arena_a, arena_b, back_a, back_b, valid_back
+        torch.cuda.empty_cache()
+    say("(a) no slower than (b): %s" % ("everywhere" if not slower else "NOT everywhere:"))
+    for v in slower:
+        say("  " + v)
+    codec.close()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return 0
+
+
+def timed_ways(torch, fns, reps=REPS, warm=3):
+    """the functions alternating inside one loop -> [(median, interquartile range)] in their order"""
+    for _ in range(warm):
+        for fn in fns:
+            fn()
+    ms = [[] for _ in fns]
+    for _ in range(reps):
+        for k, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            ms[k].append(a.elapsed_time(b))
+    return [(statistics.median(m), statistics.quantiles(m, n=4)[2] - statistics.quantiles(m, n=4)[0]) for m in ms]
+
+
 def timed_pair(torch, fa, fb, reps=REPS, warm=3):
     """fa and fb alternating inside one loop -> ((median, interquartile range) of fa, of fb)"""
     for _ in range(warm):
@@ -452,6 +597,8 @@ def main():
 
 
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["nodata"]:
+        sys.exit(nodata(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "raster_nodata_time.txt")))
     if sys.argv[1:2] == ["depth"]:
         sys.exit(depth(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "raster_depth_layouts_time.txt")))
     sys.exit(interleaved() if sys.argv[1:] == ["interleaved"] else window() if sys.argv[1:] == ["window"] else main())
